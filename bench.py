@@ -1,6 +1,6 @@
 """Headline benchmark: SLQ log-det value-and-gradient for a matrix-free RBF GP kernel (BASELINE config 4).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--row-group R]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--row-group R] [--dump-outputs DIR] [--full]
 
 N > 1 either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...:
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or stand-alone: `python bench.py --gpus N` then starts
@@ -17,7 +17,11 @@ Operator: X ~ N(0,1) of shape (131072, 8), lengthscale 2, outputscale 1, noise 0
       and shards the probes over the N / R groups.
   --scaling weak: 64 probes PER GPU, probes sharded, operator replicated, one all-reduce per step.
 
-Prints ONE JSON line on rank 0 (DESIGN.md section 4 explains the fields).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (DESIGN.md section 4 explains the fields).
+--full adds what takes runs of its own: the timed steps repeated under libmfx's kernel timers (roofline, per-kernel breakdown),
+the other two arithmetic modes, the gather legs of a row group (N > 1) and the CPU baseline (N = 1).
+--dump-outputs DIR writes what the last timed step returned (estimate, spread over probes, the three gradients) as DIR/<name>.npy;
+the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 
 import argparse
@@ -52,8 +56,8 @@ def parse(argv=None):
     ap.add_argument("--probes", type=int, default=64, help="probes in total (strong) or per GPU (weak)")
     ap.add_argument("--probes-per-gpu", type=int, default=None, help="alias of --scaling weak --probes P")
     ap.add_argument("--row-group", type=int, default=0, help="strong scaling: ranks per row group (0 = all ranks: pure row sharding)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true", help="skip the timings of the other two arithmetic modes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the timings of the other two arithmetic modes")
     ap.add_argument("--cpu-sample-n", type=int, default=0, help="0 = 8192 (smaller on a host where that would exceed ~30 s per run)")
     ap.add_argument("--kernel", default="rbf", choices=["rbf", "matern32", "matern12"],
                     help="kernel family (BASELINE config 4 is the RBF kernel; the reference's UCI runs use matern32)")
@@ -66,7 +70,12 @@ def parse(argv=None):
     ap.add_argument("--gather", default="", choices=["", "grouped", "packed"],
                     help="native RCCL row group: how the iterate is all-gathered per Krylov step (include/mfx.h MFX_GATHER_*; default packed)")
     ap.add_argument("--share-gpus", action="store_true", help="(rehearsal) ranks beyond the visible GPUs share them (needs --backend gloo)")
+    ap.add_argument("--full", action="store_true", help="also the kernel-timer repeat (roofline, breakdown), the other arithmetic modes, "
+                                                        "the gather legs (N > 1) and the CPU baseline (N = 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.probes_per_gpu is not None:
         args.scaling, args.probes = "weak", args.probes_per_gpu
     return args
@@ -76,6 +85,18 @@ def inv_softplus(x):
     import numpy as np
 
     return float(np.log(np.expm1(x)))
+
+
+def dump_outputs(folder, out):
+    """--dump-outputs: the (mean, std, grads) a step returns, as computed (fp64 estimate and spread, fp32 gradients)."""
+    import numpy as np
+
+    mean, std, grads = out
+    arrays = {"logdet_mean": mean, "probe_std": std}
+    arrays.update(zip(("grad_raw_lengthscale", "grad_raw_outputscale", "grad_raw_noise"), grads))
+    os.makedirs(folder, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), t.detach().cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -301,31 +322,39 @@ def main(argv=None):
         return t.item(), out
 
     # The timed region runs WITHOUT libmfx's per-launch hipEvent timers (they also switch the hipGraph replay off and cost 2.5 % at
-    # the per-rank size of the 8-way shard, profiles/r03b_*): `ms_per_step` / `value` are timer-free for every N.  The same steps
-    # (same seeds) are then repeated with the timers on: the roofline figures and `breakdown_ms_per_step` come from that pass,
-    # and its wall time is reported next to the headline.
+    # the per-rank size of the 8-way shard, profiles/r03b_*): `ms_per_step` / `value` are timer-free for every N.  With --full the
+    # same steps (same seeds) are then repeated with the timers on: the roofline figures and `breakdown_ms_per_step` come from that
+    # pass, and its wall time is reported next to the headline.
     step = make_step(args.precision)
     for w in range(args.warmup):
         step(100 + w)
     fence()
     elapsed, out = timed(step, args.steps, 0)
-    _lib.timing_reset()
-    _lib.timing_enable(True)
-    elapsed_timers, _ = timed(step, args.steps, 0)
-    _lib.timing_enable(False)
-    apply_ms, apply_cnt = _lib.timing_read(0)
-    grad_ms, grad_cnt = _lib.timing_read(1)
-    vec_ms, vec_cnt = _lib.timing_read(2)
-    comm_ms, comm_cnt = _lib.timing_read(3)
-    _lib.timing_reset()
-
-    # Every gather leg of the row group in the SAME process group, so that one `bench.py --gpus N` line carries all of them (the
-    # driver runs one command per N): the native communicator's packed and grouped all-gather (include/mfx.h MFX_GATHER_*) and the
-    # torch.distributed callbacks (what MFX_NATIVE_COMM=0 selects).  Per leg: 1 warm-up + 2 timed steps without kernel timers, then
-    # one step with them for the all-gather's own time.  The headline above is the leg named in `config.parallelism`.
-    gather_legs = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     rccl_view = None
-    if world > 1 and layout.comm is not None:
+    if world > 1 and layout.native:
+        try:
+            rccl_view = layout.comm.rccl_count()  # (ranks, rank) from ncclCommCount / ncclCommUserRank: RCCL's own view of the row group
+        except Exception as exc:  # noqa: BLE001
+            rccl_view = (f"unavailable ({exc})", None)
+    if args.full:
+        _lib.timing_reset()
+        _lib.timing_enable(True)
+        elapsed_timers, _ = timed(step, args.steps, 0)
+        _lib.timing_enable(False)
+        apply_ms, apply_cnt = _lib.timing_read(0)
+        grad_ms, grad_cnt = _lib.timing_read(1)
+        vec_ms, vec_cnt = _lib.timing_read(2)
+        comm_ms, comm_cnt = _lib.timing_read(3)
+        _lib.timing_reset()
+
+    # --full: every gather leg of the row group in the SAME process group, so that one `bench.py --gpus N --full` line carries all of
+    # them: the native communicator's packed and grouped all-gather (include/mfx.h MFX_GATHER_*) and the torch.distributed callbacks
+    # (what MFX_NATIVE_COMM=0 selects).  Per leg: 1 warm-up + 2 timed steps without kernel timers, then one step with them for the
+    # all-gather's own time.  The headline above is the leg named in `config.parallelism`.
+    gather_legs = None
+    if args.full and world > 1 and layout.comm is not None:
         from matfree_extensions.distributed import RowComm
 
         def leg(comm_obj):
@@ -349,10 +378,6 @@ def main(argv=None):
 
         gather_legs = {}
         if layout.native:
-            try:
-                rccl_view = layout.comm.rccl_count()  # (ranks, rank) from ncclCommCount / ncclCommUserRank: RCCL's own view of the row group
-            except Exception as exc:  # noqa: BLE001
-                rccl_view = (f"unavailable ({exc})", None)
             headline = layout.comm.gather
             for mode_name in ("packed", "grouped"):
                 layout.comm.set_gather(mode_name)
@@ -361,7 +386,7 @@ def main(argv=None):
         try_leg("torch_distributed_callbacks", RowComm(n, layout.comm.group))
 
     modes = {args.precision: 1e3 * elapsed / args.steps}
-    if not args.no_modes:
+    if args.full and not args.no_modes:
         for mode in MODES:
             if mode != args.precision:
                 t, _ = timed(make_step(mode), 2, 1)
@@ -370,26 +395,9 @@ def main(argv=None):
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = p_total * args.steps / elapsed
-        # dominant kernel: the Gram matvec.  Algorithmic flops per launch: the contraction 2 rows n p on this rank (what the matrix
-        # cores must deliver); distance + exp are extra work priced in DESIGN.md.
         rows_local = layout.comm.nrows if layout.comm is not None else n
-        flops_launch = 2.0 * rows_local * n * count
-        avg_ms = apply_ms / max(apply_cnt, 1)
-        achieved = flops_launch / (avg_ms * 1e-3) / 1e12 if apply_cnt else 0.0
         split = args.precision.startswith("f16x3")
-        peak = MFMA_F16_PEAK_TFLOPS if split else MFMA_F32_PEAK_TFLOPS
-        kernel = ("k_rbf_fat_apply (Gram matvec, one wave per SIMD; fp32 emulated by 3 f16 MFMA products, distances included; "
-                  "pre-pass and split reduction inside the timed span)" if split else "k_rbf_mfma_apply (Gram matvec, exact fp32 MFMA)")
-        # HBM-side bytes per launch: NOT measured in this run (PMC counters need rocprofv3 around the process) -- read from the file
-        # tools/prof_traffic.sh wrote, which names the commit and the command it was collected on (`traffic_source`)
-        traffic, traffic_source = None, None
-        tfile = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tfile) and world == 1:
-            tj = json.load(open(tfile))
-            traffic = tj.get("k_rbf_fat_apply_hbm_bytes_per_launch" if split else "k_rbf_mfma_apply_hbm_bytes_per_launch")
-            traffic_source = f"profiles/traffic.json @ {tj.get('commit', 'unknown commit')} ({tj.get('command', 'command not recorded')}); read from the file, not measured in this run"
         mean, std, grads = out
-        batch = count * k
         if layout.native:
             collectives = (f"libmfx -> RCCL (native, {layout.comm.gather} gather); ranks in the communicator libmfx itself holds "
                            f"(ncclCommCount) = {rccl_view[0]}")
@@ -403,7 +411,6 @@ def main(argv=None):
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
-            "ms_per_step_with_kernel_timers": 1e3 * elapsed_timers / args.steps,
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
@@ -422,6 +429,28 @@ def main(argv=None):
                 "rccl_comm_ranks": rccl_view[0] if rccl_view else None,
                 "gram_precision": args.precision, "kernel": args.kernel,
             },
+            "result": {"logdet_mean": float(mean), "probe_std": float(std), "grad": [float(g) for g in grads]},
+        }
+    if rank == 0 and args.full:
+        # dominant kernel: the Gram matvec.  Algorithmic flops per launch: the contraction 2 rows n p on this rank (what the matrix
+        # cores must deliver); distance + exp are extra work priced in DESIGN.md.
+        flops_launch = 2.0 * rows_local * n * count
+        avg_ms = apply_ms / max(apply_cnt, 1)
+        achieved = flops_launch / (avg_ms * 1e-3) / 1e12 if apply_cnt else 0.0
+        peak = MFMA_F16_PEAK_TFLOPS if split else MFMA_F32_PEAK_TFLOPS
+        kernel = ("k_rbf_fat_apply (Gram matvec, one wave per SIMD; fp32 emulated by 3 f16 MFMA products, distances included; "
+                  "pre-pass and split reduction inside the timed span)" if split else "k_rbf_mfma_apply (Gram matvec, exact fp32 MFMA)")
+        # HBM-side bytes per launch: NOT measured in this run (PMC counters need rocprofv3 around the process) -- read from the file
+        # tools/prof_traffic.sh wrote, which names the commit and the command it was collected on (`traffic_source`)
+        traffic, traffic_source = None, None
+        tfile = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tfile) and world == 1:
+            tj = json.load(open(tfile))
+            traffic = tj.get("k_rbf_fat_apply_hbm_bytes_per_launch" if split else "k_rbf_mfma_apply_hbm_bytes_per_launch")
+            traffic_source = f"profiles/traffic.json @ {tj.get('commit', 'unknown commit')} ({tj.get('command', 'command not recorded')}); read from the file, not measured in this run"
+        batch = count * k
+        line.update({
+            "ms_per_step_with_kernel_timers": 1e3 * elapsed_timers / args.steps,
             "modes": {"ms_per_step": modes,
                       "note": "same process, same inputs; the timed mode has --steps steps, the others 2 steps after 1 warm-up"},
             "roofline": {
@@ -467,10 +496,10 @@ def main(argv=None):
                                  / max(vec_ms / args.steps * 1e-3, 1e-12),
                 "peak_GBps": HBM_PEAK_GBS,
             },
-            "result": {"logdet_mean": float(mean), "probe_std": float(std), "grad": [float(g) for g in grads]},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
+    if rank == 0:
         print(json.dumps(line))
     if world > 1:
         # the native communicator goes before the process group does (ncclCommDestroy from __del__ at interpreter shutdown would run

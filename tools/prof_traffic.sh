@@ -13,12 +13,12 @@ cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/prof_traffic
 rm -rf $OUT && mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -- python3 $R/bench.py --steps 1 --warmup 0 --k $K --no-cpu-baseline --no-modes > $OUT/$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -- python3 $R/bench.py --steps 1 --warmup 0 --k $K --full --no-cpu-baseline --no-modes > $OUT/$c.log 2>&1
 done
 python3 - $OUT $K $COMMIT <<'PY'
 import csv, glob, json, sys, collections
 out, k, commit = sys.argv[1:4]
-res = {"commit": commit, "command": f"bench.py --steps 1 --warmup 0 --k {k} --no-cpu-baseline --no-modes", "krylov_depth": int(k),
+res = {"commit": commit, "command": f"bench.py --steps 1 --warmup 0 --k {k} --full --no-cpu-baseline --no-modes", "krylov_depth": int(k),
        "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes; counter unit KB; per launch averages.  gfx950 correction: "
                "FETCH_SIZE doubled (wide 16-B/lane streams are tallied at half, MI355X_MICROARCH.md HBM section).  Both counters sit on the "
                "L2's memory side (fabric requests: L2 misses), Infinity-Cache hits INCLUDED -- `hbm_bytes_per_launch` = 2 FETCH + WRITE is an "
