@@ -121,6 +121,10 @@ int op_vjp_params(const mfx_operator* op, const void* L, int64_t ldl, const void
                   int64_t batch, const mfx_op_grads* grads, void* ws, int64_t ws_bytes,
                   hipStream_t stream, int64_t inner = 1);
 
+// grads->x (the input gradient of a kernel-Gram operator) is refused before any launch: MFX_ERR_INVALID on other operators,
+// MFX_ERR_UNSUPPORTED on row blocks (nrows > 0) and on the row-sharded drivers (sharded = true)
+int check_grads_x(const mfx_operator* op, const mfx_op_grads* grads, bool sharded);
+
 int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m);
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);

@@ -950,6 +950,7 @@ int mfx_op_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, in
 int mfx_op_vjp_params(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr,
                       int64_t batch, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(op && L && R && grads, MFX_ERR_INVALID, "null argument");
+  MFX_TRY(check_grads_x(op, grads, false));
   MFX_REQUIRE(op->kind != MFX_OP_CALLBACK, MFX_ERR_UNSUPPORTED, "callback operators own their parameter gradients");
   hipStream_t s = static_cast<hipStream_t>(stream);
   ScopedTimer t(1, s);
@@ -1019,6 +1020,7 @@ int mfx_arnoldi_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p,
                         int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(Q && H && r && c && dH && dv && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(reortho == MFX_REORTHO_NONE || reortho == MFX_REORTHO_FULL, MFX_ERR_INVALID, "bad reortho flag %d", reortho);
+  MFX_TRY(check_grads_x(op, grads, false));
   MFX_DRIVER_PROLOGUE();
   GraphKey key = driver_key(2, op, n, k, p, grads, ws, ws_bytes, stream);
   key.add(Q).add(H).add(r).add(c).add(dQ).add(dH).add(dr).add(dc).add(reortho).add(dv).add(Lambda);
@@ -1077,6 +1079,7 @@ int mfx_arnoldi_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
                                 void* Lambda, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(Q && Qfull && H && r && c && dH && dv && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(reortho == MFX_REORTHO_NONE || reortho == MFX_REORTHO_FULL, MFX_ERR_INVALID, "bad reortho flag %d", reortho);
+  MFX_TRY(check_grads_x(op, grads, true));
   MFX_SHARDED_PROLOGUE();
   if (op->dtype == MFX_F32)
     return arnoldi_adjoint_t<float>(op, nrows, k, p, (const float*)Q, (const float*)H, (const float*)r, (const float*)c,
@@ -1101,6 +1104,7 @@ int mfx_lanczos_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
                                 const void* dbeta, void* dv, void* Lambda, void* Lambdafull, const mfx_op_grads* grads, void* ws,
                                 int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && dv && Lambda && Lambdafull, MFX_ERR_INVALID, "null argument");
+  MFX_TRY(check_grads_x(op, grads, true));
   MFX_SHARDED_PROLOGUE();
   if (op->dtype == MFX_F32)
     return lanczos_adjoint_t<float>(op, nrows, k, p, (const float*)xs, (const float*)alpha, (const float*)beta, (const float*)vnorm,
@@ -1128,6 +1132,7 @@ int mfx_lanczos_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p,
                         const void* beta, const void* vnorm, const void* dxs, const void* dalpha, const void* dbeta,
                         void* dv, void* Lambda, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && dv && Lambda, MFX_ERR_INVALID, "null argument");
+  MFX_TRY(check_grads_x(op, grads, false));
   MFX_DRIVER_PROLOGUE();
   GraphKey key = driver_key(4, op, n, k, p, grads, ws, ws_bytes, stream);
   key.add(xs).add(alpha).add(beta).add(vnorm).add(dxs).add(dalpha).add(dbeta).add(dv).add(Lambda);

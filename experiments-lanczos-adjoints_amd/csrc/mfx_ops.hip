@@ -482,6 +482,172 @@ __global__ __launch_bounds__(256) void k_rbf_grad_wide(const T* __restrict__ xs,
     out[dpad + tid - kWideGC] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Input sweep: the gradient of G = sum_b L_b^T K R_b = sum_ij S_ij K_ij with respect to the raw inputs X.  With xs = X / l,
+// dist_aj = |xs_a - xs_j|^2 and dK/d dist = -s wl / 2 (kernel_eval's weight, all three kernels):
+//   dG/dX_ac = -(s / l_c) sum_j (S_aj + S_ja) wl_aj (xs_ac - xs_jc)
+// Where the distance is clamped (dist <= 0: the diagonal, duplicated points) the term is 0 -- the reference's max(0, .) passes no
+// gradient there.  One row a per thread: S_aj and S_ja of a tile of kGradTJ columns in two register accumulators, the row's d sums
+// in registers (double), written once.  Every output row depends only on its own row of S + S^T: no cross-workgroup reduction,
+// deterministic.  gx (n, d) row-major is accumulated into.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int DPAD>
+__global__ __launch_bounds__(256) void k_rbf_grad_x(const T* __restrict__ xs, const T* __restrict__ sq, int64_t n, int d,
+                                                    int ard, int kind, const T* __restrict__ L, int64_t ldl,
+                                                    const T* __restrict__ R, int64_t ldr, int64_t batch,
+                                                    const T* __restrict__ ls, const T* __restrict__ outputscale,
+                                                    T* __restrict__ gx) {
+  __shared__ __attribute__((aligned(16))) T xj[kGradTJ][DPAD];
+  __shared__ T sqj[kGradTJ];
+  __shared__ T rj[kGradBC][kGradTJ];
+  __shared__ T lj[kGradBC][kGradTJ];
+  const int tid = threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < n;
+  const int64_t ic = live ? i : n - 1;
+  T xi[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) xi[c] = xs[ic * DPAD + c];
+  const T sqi = sq[ic];
+  double g[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) g[c] = 0.0;
+  for (int64_t j0 = 0; j0 < n; j0 += kGradTJ) {
+    T Sa[kGradTJ], St[kGradTJ];  // S_ij and S_ji of this row i and the tile's columns j
+#pragma unroll
+    for (int jj = 0; jj < kGradTJ; ++jj) Sa[jj] = St[jj] = T(0);
+    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
+      __syncthreads();
+      for (int t = tid; t < kGradBC * kGradTJ; t += 256) {
+        const int q = t / kGradTJ, jj = t % kGradTJ;
+        const bool in = bt0 + q < batch && j0 + jj < n;
+        rj[q][jj] = in ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
+        lj[q][jj] = in ? L[(bt0 + q) * ldl + j0 + jj] : T(0);
+      }
+      __syncthreads();
+      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
+      for (int q = 0; q < qmax; ++q) {
+        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
+        const T r = live ? R[(bt0 + q) * ldr + i] : T(0);
+#pragma unroll
+        for (int jj = 0; jj < kGradTJ; ++jj) {
+          Sa[jj] += l * rj[q][jj];
+          St[jj] += r * lj[q][jj];
+        }
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < kGradTJ * DPAD; t += 256) {
+      const int64_t gi = j0 * DPAD + t;
+      (&xj[0][0])[t] = gi < n * DPAD ? xs[gi] : T(0);
+    }
+    if (tid < kGradTJ) sqj[tid] = (j0 + tid < n) ? sq[j0 + tid] : T(0);
+    __syncthreads();
+#pragma unroll
+    for (int jj = 0; jj < kGradTJ; ++jj) {
+      if (j0 + jj >= n || j0 + jj == i) continue;
+      T dot = T(0);
+#pragma unroll
+      for (int c = 0; c < DPAD; ++c) dot += xi[c] * xj[jj][c];
+      const T dist = sqi + sqj[jj] - T(2) * dot;
+      if (!(dist > T(0))) continue;  // clamped: no gradient
+      T kv, wl;
+      kernel_eval<T>(kind, dist, kv, wl);
+      const T w = (Sa[jj] + St[jj]) * wl;
+#pragma unroll
+      for (int c = 0; c < DPAD; ++c) g[c] += (double)(w * (xi[c] - xj[jj][c]));
+    }
+  }
+  if (!live) return;
+  const double s = (double)outputscale[0];
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c)
+    if (c < d) gx[i * d + c] += (T)(-s / (double)ls[ard ? c : 0] * g[c]);
+}
+
+constexpr int kWideXJ = 8;  // columns per tile, input sweep (S_ij and S_ji: twice the accumulators of the parameter sweep)
+
+// the input sweep for wide inputs (d > 32): as k_rbf_grad_x with the distances of wide_dots; the row's d sums do not fit a thread's
+// registers, so the grid's second axis selects kWideGC of them (S and the distances are re-evaluated per selection, as in
+// k_rbf_grad_wide)
+template <typename T>
+__global__ __launch_bounds__(256) void k_rbf_grad_x_wide(const T* __restrict__ xs, const T* __restrict__ sq, int64_t n, int dpad,
+                                                         int d, int ard, int kind, const T* __restrict__ L, int64_t ldl,
+                                                         const T* __restrict__ R, int64_t ldr, int64_t batch,
+                                                         const T* __restrict__ ls, const T* __restrict__ outputscale,
+                                                         T* __restrict__ gx) {
+  constexpr int CH = Wide<T>::CH;
+  __shared__ __attribute__((aligned(16))) T xiT[CH][256];
+  __shared__ __attribute__((aligned(16))) T xjT[CH][kWideXJ];
+  __shared__ __attribute__((aligned(16))) T xjg[kWideXJ][kWideGC];
+  __shared__ T sqj[kWideXJ];
+  __shared__ T rj[kGradBC][kWideXJ];
+  __shared__ T lj[kGradBC][kWideXJ];
+  const int tid = threadIdx.x;
+  const int gc = (int)blockIdx.y;  // dimensions gc * 32 .. gc * 32 + 31
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < n;
+  const int64_t ic = live ? i : n - 1;
+  const T sqi = sq[ic];
+  T xig[kWideGC];
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) xig[c] = xs[ic * dpad + gc * kWideGC + c];
+  double g[kWideGC];
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) g[c] = 0.0;
+  for (int64_t j0 = 0; j0 < n; j0 += kWideXJ) {
+    T Sa[kWideXJ], St[kWideXJ];
+#pragma unroll
+    for (int jj = 0; jj < kWideXJ; ++jj) Sa[jj] = St[jj] = T(0);
+    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
+      __syncthreads();
+      for (int t = tid; t < kGradBC * kWideXJ; t += 256) {
+        const int q = t / kWideXJ, jj = t % kWideXJ;
+        const bool in = bt0 + q < batch && j0 + jj < n;
+        rj[q][jj] = in ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
+        lj[q][jj] = in ? L[(bt0 + q) * ldl + j0 + jj] : T(0);
+      }
+      __syncthreads();
+      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
+      for (int q = 0; q < qmax; ++q) {
+        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
+        const T r = live ? R[(bt0 + q) * ldr + i] : T(0);
+#pragma unroll
+        for (int jj = 0; jj < kWideXJ; ++jj) {
+          Sa[jj] += l * rj[q][jj];
+          St[jj] += r * lj[q][jj];
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < kWideXJ) sqj[tid] = (j0 + tid < n) ? sq[j0 + tid] : T(0);
+    for (int t = tid; t < kWideXJ * kWideGC; t += 256) {
+      const int jj = t / kWideGC, c = t % kWideGC;
+      xjg[jj][c] = (j0 + jj < n) ? xs[(j0 + jj) * dpad + gc * kWideGC + c] : T(0);
+    }
+    T dot[kWideXJ];
+    wide_dots<T, kWideXJ>(xs, n, dpad, xs, ic, j0, xiT, xjT, dot);  // (its barriers publish sqj / xjg too)
+#pragma unroll
+    for (int jj = 0; jj < kWideXJ; ++jj) {
+      if (j0 + jj >= n || j0 + jj == i) continue;
+      const T dist = sqi + sqj[jj] - T(2) * dot[jj];
+      if (!(dist > T(0))) continue;
+      T kv, wl;
+      kernel_eval<T>(kind, dist, kv, wl);
+      const T w = (Sa[jj] + St[jj]) * wl;
+#pragma unroll
+      for (int c = 0; c < kWideGC; ++c) g[c] += (double)(w * (xig[c] - xjg[jj][c]));
+    }
+  }
+  if (!live) return;
+  const double s = (double)outputscale[0];
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) {
+    const int col = gc * kWideGC + c;
+    if (col < d) gx[i * d + col] += (T)(-s / (double)ls[ard ? col : 0] * g[c]);
+  }
+}
+
 // grads += factors * sum_blocks partial  (chain to the constrained parameters l, s, noise)
 template <typename T>
 __global__ __launch_bounds__(256) void k_rbf_grad_final(const double* __restrict__ partial, int64_t nblocks, int dpad, int d,
@@ -771,6 +937,46 @@ static int rbf_grad(const mfx_operator* op, const T* L, int64_t ldl, const T* R,
   return MFX_OK;
 }
 
+// grads->x += dG/dX (the input sweep above).  VALU kernels for every dtype, mode and d: k_rbf_grad_x up to d = 32, k_rbf_grad_x_wide
+// beyond.  Whole operator only (the caller refuses row blocks).
+template <typename T>
+static int rbf_grad_x(const mfx_operator* op, const T* L, int64_t ldl, const T* R, int64_t ldr, int64_t batch,
+                      const mfx_op_grads* grads, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  const int dpad = rbf_dpad(op->d);
+  MFX_REQUIRE(dpad > 0, MFX_ERR_UNSUPPORTED, "RBF operator supports d <= 1024 (got %d)", op->d);
+  RbfWs w;
+  MFX_REQUIRE(rbf_carve(op, ws, ws_bytes, &w, batch) <= ws_bytes && ws, MFX_ERR_WORKSPACE, "RBF workspace too small");
+  MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
+  const unsigned nblocks = (unsigned)((op->n + 255) / 256);
+#define MFX_RBF_GRAD_X(D)                                                                                                    \
+  k_rbf_grad_x<T, D><<<nblocks, 256, 0, stream>>>((const T*)w.xs, (const T*)w.sq, op->n, op->d, op->ard, op->kernel_fn, L, ldl, \
+                                                  R, ldr, batch, (const T*)op->lengthscale, (const T*)op->outputscale,      \
+                                                  (T*)grads->x)
+  switch (dpad) {
+    case 4: MFX_RBF_GRAD_X(4); break;
+    case 8: MFX_RBF_GRAD_X(8); break;
+    case 12: MFX_RBF_GRAD_X(12); break;
+    case 16: MFX_RBF_GRAD_X(16); break;
+    case 32: MFX_RBF_GRAD_X(32); break;
+    default:
+      k_rbf_grad_x_wide<T><<<dim3(nblocks, (unsigned)(dpad / kWideGC)), 256, 0, stream>>>(
+          (const T*)w.xs, (const T*)w.sq, op->n, dpad, op->d, op->ard, op->kernel_fn, L, ldl, R, ldr, batch,
+          (const T*)op->lengthscale, (const T*)op->outputscale, (T*)grads->x);
+      break;
+  }
+#undef MFX_RBF_GRAD_X
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+int check_grads_x(const mfx_operator* op, const mfx_op_grads* grads, bool sharded) {
+  if (!op || !grads || !grads->x) return MFX_OK;
+  MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_INVALID, "the input gradient (grads->x) needs a kernel-Gram operator");
+  MFX_REQUIRE(!sharded && op->nrows == 0, MFX_ERR_UNSUPPORTED,
+              "the input gradient (grads->x) is not available on row blocks or row-sharded drivers");
+  return MFX_OK;
+}
+
 // ================================================================================================
 // dispatch
 // ================================================================================================
@@ -854,6 +1060,7 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
   const int64_t row0 = op_row0(op), nrow = op_nrows(op);
   MFX_REQUIRE(row0 >= 0 && nrow >= 1 && row0 + nrow <= n, MFX_ERR_INVALID, "row block [%lld, +%lld) outside the operator (n = %lld)",
               (long long)row0, (long long)nrow, (long long)n);
+  MFX_TRY(check_grads_x(op, grads, false));
   switch (op->kind) {
     case MFX_OP_DENSE:
       if (!grads->dense_a) return MFX_OK;
@@ -868,9 +1075,16 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
                                                                          batch, (T*)grads->val, row0, nrow);
       MFX_CHECK_LAUNCH();
       return MFX_OK;
-    case MFX_OP_RBF:
-      if (!grads->lengthscale && !grads->outputscale && !grads->noise) return MFX_OK;
-      return rbf_grad<T>(op, L, ldl, R, ldr, batch, inner, grads, ws, ws_bytes, stream);
+    case MFX_OP_RBF: {
+      const bool params = grads->lengthscale || grads->outputscale || grads->noise;
+      if (!grads->x) {
+        if (!params) return MFX_OK;
+        return rbf_grad<T>(op, L, ldl, R, ldr, batch, inner, grads, ws, ws_bytes, stream);
+      }
+      PrepScope prep_scope;  // one k_rbf_prep for both sweeps
+      if (params) MFX_TRY(rbf_grad<T>(op, L, ldl, R, ldr, batch, inner, grads, ws, ws_bytes, stream));
+      return rbf_grad_x<T>(op, L, ldl, R, ldr, batch, grads, ws, ws_bytes, stream);
+    }
     default:
       set_error("unknown operator kind %d", op->kind);
       return MFX_ERR_UNSUPPORTED;

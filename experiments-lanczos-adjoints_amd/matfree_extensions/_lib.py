@@ -105,6 +105,7 @@ class OpGrads(C.Structure):
         ("lengthscale", C.c_void_p),
         ("outputscale", C.c_void_p),
         ("noise", C.c_void_p),
+        ("x", C.c_void_p),
     ]
 
 

@@ -31,7 +31,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .operators import CallbackOp, DenseOp, RowShardedOp, _PtrRegistry, as_operator
+from .operators import CallbackOp, DenseOp, RowShardedOp, _PtrRegistry, as_operator, differentiable_inputs
 
 
 def hessenberg(
@@ -58,7 +58,7 @@ def hessenberg(
         if V.is_complex():
             if sharded:
                 raise NotImplementedError("complex Arnoldi on a row-sharded operator")
-            if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params)):
+            if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params, *differentiable_inputs(op))):
                 raise NotImplementedError("complex Arnoldi is forward only: detach the inputs (the adjoint system is real)")
             second_pass = (reortho_vjp if reortho_vjp != "match" else reortho_vjp) != "none"  # Q1, as below
             Qkn, H, r, c = _complex_forward(op, int(krylov_depth), second_pass, V, params)
@@ -73,7 +73,7 @@ def hessenberg(
         # Q1 (arnoldi.py:26): the forward always sees `reortho_vjp`
         reortho_fwd = reortho_vjp if reortho_vjp != "match" else reortho_vjp
         second_pass = reortho_fwd != "none"
-        wants_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params))
+        wants_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params, *differentiable_inputs(op)))
         if not custom_vjp and not sharded and wants_grad:  # autodiff THROUGH the loop: the reference's baseline (_autodiff.py)
             from . import _autodiff
 

@@ -130,9 +130,20 @@ def hutchinson_custom_vjp(integrand_fun, /, sample_fun):
     class _Fn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, key_holder, *parameters):
-            key = key_holder[0]
-            with torch.no_grad():
-                value = _tree_mean(_map_over_samples(integrand_fun, sample_fun(key), parameters))
+            key, grad_wanted = key_holder
+            if grad_wanted:  # the backward below differentiates w.r.t. `parameters` only: refuse what the integrand closes over
+                with torch.enable_grad():
+                    detached = [q.detach() if torch.is_tensor(q) else q for q in parameters]
+                    value = _tree_mean(_map_over_samples(integrand_fun, sample_fun(key), detached))
+                if torch.is_tensor(value) and value.requires_grad:
+                    raise NotImplementedError(
+                        "hutchinson_custom_vjp differentiates the integrand with respect to its parameters only, but the integrand "
+                        "closes over a tensor that requires grad (e.g. the inputs X of a kernel-Gram operator); use "
+                        "hutchinson.hutchinson, or pass that tensor as a parameter")
+                value = value.detach() if torch.is_tensor(value) else value
+            else:
+                with torch.no_grad():
+                    value = _tree_mean(_map_over_samples(integrand_fun, sample_fun(key), parameters))
             if not torch.is_tensor(value):
                 raise TypeError("hutchinson_custom_vjp supports tensor-valued integrands")
             ctx.key_bwd = split(key, 2)[1]
@@ -156,7 +167,7 @@ def hutchinson_custom_vjp(integrand_fun, /, sample_fun):
             return (None, *out)
 
     def sample(key, *parameters):
-        return _Fn.apply((key,), *parameters)
+        return _Fn.apply((key, torch.is_grad_enabled()), *parameters)
 
     return sample
 

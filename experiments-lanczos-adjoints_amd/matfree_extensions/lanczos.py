@@ -22,7 +22,7 @@ import warnings
 import torch
 
 from . import _lib, arnoldi
-from .operators import CallbackOp, RowShardedOp, _PtrRegistry, as_operator
+from .operators import CallbackOp, RowShardedOp, _PtrRegistry, as_operator, differentiable_inputs, with_inputs
 
 
 def _vec_norm(V, matvec):
@@ -78,7 +78,7 @@ def _tridiag_reortho_none(matvec, krylov_depth, /, *, custom_vjp):
             raise ValueError(f"row-sharded operator: expected this rank's {op.comm.nrows} rows of the start vector, got {V.shape[-1]}")
         if k < 1 or k > n:
             raise ValueError(f"Parameter depth {k} is outside the expected range")
-        wants_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params))
+        wants_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params, *differentiable_inputs(op)))
         if sharded:  # vectors are row shards, alpha / beta replicated (mfx_lanczos_*_sharded)
             cparams = op.constrain(*params)
             xs, alpha, beta = _LanczosShardedFn.apply(op, k, custom_vjp, V, *cparams)
@@ -383,7 +383,7 @@ def integrand_spd_custom_vjp_reuse(matfun, order, matvec, /, *, reortho: str = "
             raise TypeError("integrand_spd_custom_vjp_reuse: pytree start vectors are not supported")
         batched = v0_flat.dim() == 2
         V = v0_flat if batched else v0_flat[None]
-        out = _ReuseFn.apply(op, matfun, int(order), reortho, V, *parameters)
+        out = _ReuseFn.apply(op, matfun, int(order), reortho, len(parameters), V, *parameters, *differentiable_inputs(op))
         return out if batched else out[0]
 
     quadform.batched = True
@@ -392,7 +392,9 @@ def integrand_spd_custom_vjp_reuse(matfun, order, matvec, /, *, reortho: str = "
 
 class _ReuseFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, op, matfun, order, reortho, V, *parameters):
+    def forward(ctx, op, matfun, order, reortho, nparams, V, *parameters):
+        # parameters: the matvec's nparams parameters, then the tensors the operator closes over (differentiable_inputs)
+        parameters = parameters[:nparams]
         with torch.no_grad():
             scale = torch.linalg.vector_norm(V, dim=-1)
             U = V / scale[:, None]
@@ -405,9 +407,9 @@ class _ReuseFn(torch.autograd.Function):
             sol = torch.einsum("pia,pa->pi", evecs, dfx * evecs[:, 0, :])  # lanczos.py:116
             w1 = scale[:, None] ** 2 * torch.einsum("pin,pi->pn", basis, sol)  # lanczos.py:117
         ctx.op = op
-        ctx.nparams = len(parameters)
-        ctx.save_for_backward(w1, U, *[q for q in parameters if torch.is_tensor(q)])
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in parameters]
+        ctx.nparams = nparams
+        ctx.save_for_backward(w1, U, *[q for q in parameters if torch.is_tensor(q)], *differentiable_inputs(op))
+        ctx.nontensor = [None if torch.is_tensor(q) else q for q in parameters] + [None] * len(differentiable_inputs(op))
         return scale**2 * value
 
     @staticmethod
@@ -419,8 +421,9 @@ class _ReuseFn(torch.autograd.Function):
         with torch.enable_grad():
             live = [q.detach().requires_grad_(True) if torch.is_tensor(q) and q.is_floating_point() else q for q in params]
             diff = [q for q in live if torch.is_tensor(q) and q.requires_grad]
-            fx = (ctx.op(w2, *live) * w1 * gout[:, None]).sum()  # (A(p) w2)^T w1, lanczos.py:128
+            op = with_inputs(ctx.op, live[ctx.nparams:])  # (the inputs X of a kernel-Gram operator, when they need a gradient)
+            fx = (op(w2, *live[: ctx.nparams]) * w1 * gout[:, None]).sum()  # (A(p) w2)^T w1, lanczos.py:128
             grads = torch.autograd.grad(fx, diff, allow_unused=True)
         it = iter(grads)
         out = [next(it) if (torch.is_tensor(q) and q.requires_grad) else None for q in live]
-        return (None, None, None, None, torch.zeros_like(w2), *out)
+        return (None, None, None, None, None, torch.zeros_like(w2), *out)

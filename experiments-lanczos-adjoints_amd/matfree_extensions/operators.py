@@ -11,6 +11,8 @@ whole Krylov loop, the transposed matvec and the parameter-gradient sweep run as
   CsrOp(crow, col, n)               params = (values,)            experiments/benchmarks/.../suite_sparse/benchmark.py:64-68
   RbfGramOp(X, noise_minval=...)    params = (raw_lengthscale, raw_outputscale, raw_noise)
                                                                   util/gp_util.py:151-201,225-226,525-549
+                                    (and X itself when X.requires_grad: the reference's closure conversion
+                                    makes the inputs its lazy kernel closes over differentiable too)
   CallbackOp(fn)                    any Python ``fn(v, *params)`` (torch ops); per-step host control
 
 ``op.bind(*params)`` freezes the parameters into a zero-argument-parameter matvec (what the GP code
@@ -19,6 +21,7 @@ hands to ``krylov_logdet_slq``, util/gp_util.py:555-557) while keeping them diff
 
 from __future__ import annotations
 
+import copy
 import ctypes as C
 
 import torch
@@ -77,6 +80,13 @@ class BoundOp:
         return self.op(v, *self.params)
 
 
+def _refuse_input_grad(op):
+    if isinstance(op, RbfGramOp) and op.X.requires_grad:
+        raise NotImplementedError("the gradient with respect to the kernel inputs X is not available on row-sharded operators "
+                                  "(it needs the whole (n, d) gradient all-reduced and the halo of X); pass X.detach(), or shard "
+                                  "the probes instead of the rows")
+
+
 class RowShardedOp:
     """A native operator whose rows -- and the rows of every Krylov vector -- are sharded over the ranks of a
     ``distributed.RowComm``.  Hand it to ``lanczos.tridiag(reortho="full")`` / ``arnoldi.hessenberg`` /
@@ -86,6 +96,7 @@ class RowShardedOp:
     def __init__(self, op, comm, exchange="auto"):
         if not isinstance(op, NativeOp):
             raise TypeError("row sharding needs a native operator (DenseOp, CsrOp, RbfGramOp)")
+        _refuse_input_grad(op)
         self.op, self.comm = op, comm
         # sparse operators: neighbour exchange of the entries this rank's rows read (the halo of a stencil) instead of
         # all-gathering the whole iterate; plans for A and A^T (collective: every rank of the row group builds them here)
@@ -101,6 +112,7 @@ class RowShardedOp:
         return BoundOp(self, params)
 
     def constrain(self, *params):
+        _refuse_input_grad(self.op)
         return self.op.constrain(*params)
 
     def __call__(self, v, *params):
@@ -261,6 +273,10 @@ class RbfGramOp(NativeOp):
       "f16x3-matvec"     split matvec, exact fp32 gradient GEMM: the most accurate mode against fp64;
       "fp32"             exact fp32 MFMA everywhere.
     fp64 operators ignore it.
+
+    X may require grad (deep-kernel inputs ``net(features)``, learned warpings): ``constrain`` then returns X as a fourth
+    tensor, so every autograd Function of the package returns its gradient (libmfx's input sweep, ``mfx_op_grads.x``)
+    and it reaches the caller's tensor through ``X.contiguous()``.  Not on row-sharded operators.
     """
 
     kind = _lib.OP_RBF
@@ -288,12 +304,14 @@ class RbfGramOp(NativeOp):
             raise ValueError(f"raw_lengthscale must have shape () or ({self.d},)")
         s = softplus(raw_outputscale).to(dt).reshape(1)
         nz = (self.noise_minval + softplus(raw_noise)).to(dt).reshape(1)
+        if self.X.requires_grad:
+            return (ls.contiguous(), s, nz, self.X)
         return (ls.contiguous(), s, nz)
 
     def size(self, *_):
         return self.n
 
-    def fill(self, desc, ls, s, nz):
+    def fill(self, desc, ls, s, nz, X=None):
         if self.X.dtype != ls.dtype:
             raise TypeError("RbfGramOp: X and the hyper-parameters must share a dtype")
         _check_dtype(desc, self.X, "RbfGramOp: the inputs X")
@@ -322,10 +340,14 @@ class RbfGramOp(NativeOp):
                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(V.device)))
         return y if v.dim() == 2 else y[0]
 
-    def new_grads(self, ls, s, nz):
+    def new_grads(self, ls, s, nz, X=None):
         g = (torch.zeros_like(ls), torch.zeros_like(s), torch.zeros_like(nz))
         st = _lib.OpGrads()
         st.lengthscale, st.outputscale, st.noise = (t.data_ptr() for t in g)
+        if X is not None:  # X carried as a constrained tensor: the input sweep writes dG/dX (n, d)
+            gx = torch.zeros_like(X, memory_format=torch.contiguous_format)
+            st.x = gx.data_ptr()
+            g = (*g, gx)
         return st, g
 
 
@@ -428,6 +450,20 @@ class CallbackOp:
 
 
 KernelGramOp = RbfGramOp  # the operator covers the reference's three stationary kernels
+
+
+def differentiable_inputs(op):
+    """Tensors an operator closes over that need a gradient: RbfGramOp's X when it requires grad, else ()."""
+    return (op.X,) if isinstance(op, RbfGramOp) and op.X.requires_grad else ()
+
+
+def with_inputs(op, inputs):
+    """A shallow copy of ``op`` that closes over ``inputs`` (ordered as differentiable_inputs returns them) instead."""
+    if not inputs:
+        return op
+    new = copy.copy(op)
+    (new.X,) = inputs
+    return new
 
 
 def as_operator(matvec):

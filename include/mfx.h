@@ -126,14 +126,22 @@ typedef struct mfx_operator {
 
 /* Parameter-gradient outputs (device pointers, ACCUMULATED into, caller zero-fills).  NULL = skip.
  *   dense_a (n, n) row-major, leading dimension = n;  val (nnz);
- *   lengthscale (d if ard else 1), outputscale (1), noise (1).
- * d/dtheta of  sum_b L_b^T A(theta) R_b   (arnoldi.py:207-209, lanczos.py:328-329). */
+ *   lengthscale (d if ard else 1), outputscale (1), noise (1);
+ *   x (n, d) row-major in the operator's dtype: the gradient with respect to the raw kernel inputs X of a kernel-Gram operator
+ *     (the reference differentiates the inputs its lazy kernel closes over, arnoldi.py:21-23, util/gp_util.py:221-231).
+ *     Every entry point that takes grads honours it (mfx_op_vjp_params, mfx_arnoldi_adjoint, mfx_lanczos_adjoint; the PCG backward
+ *     goes through mfx_op_vjp_params).  Refused before any launch: MFX_ERR_INVALID on any other operator kind, MFX_ERR_UNSUPPORTED
+ *     on a row block (nrows > 0) and on the row-sharded drivers.  grads->x == NULL runs exactly the kernels of the other fields.
+ * d/dtheta of  sum_b L_b^T A(theta) R_b   (arnoldi.py:207-209, lanczos.py:328-329).
+ * The struct grew by `x` at the end without a version bump (MFX_VERSION stays 201): C callers must zero-fill it
+ * (mfx_op_grads g = {0}; or memset) so that fields they do not know are NULL. */
 typedef struct mfx_op_grads {
   void* dense_a;
   void* val;
   void* lengthscale;
   void* outputscale;
   void* noise;
+  void* x;
 } mfx_op_grads;
 
 const char* mfx_last_error(void);
