@@ -765,6 +765,27 @@ int mfx_gram_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, co
   return op_cross_apply(op, xnew, m, v, ldv, y, ldy, p, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
+int mfx_gram_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const void* u, int64_t ldu, void* y,
+                           int64_t ldy, int64_t p, void* ws, int64_t ws_bytes, void* stream) {
+  MFX_REQUIRE(op && xnew && u && y, MFX_ERR_INVALID, "mfx_gram_cross_apply_t: null argument");
+  MFX_REQUIRE(op->n >= 1 && m >= 1 && p >= 1 && ldu >= m && ldy >= op->n, MFX_ERR_INVALID, "mfx_gram_cross_apply_t: bad sizes");
+  MFX_REQUIRE(p <= 65535 * 8, MFX_ERR_UNSUPPORTED, "too many vectors per call");
+  return op_cross_apply_t(op, xnew, m, u, ldu, y, ldy, p, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+int64_t mfx_gram_cross_vjp_workspace_bytes(const mfx_operator* op, int64_t m, int64_t batch) {
+  if (!op || op->kind != MFX_OP_RBF || m <= 0 || batch <= 0) return -1;
+  return rbf_cross_vjp_ws_bytes(op, m) + 256;
+}
+
+int mfx_gram_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl, const void* R,
+                       int64_t ldr, int64_t batch, const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes,
+                       void* stream) {
+  MFX_REQUIRE(op && xnew && L && R && grads, MFX_ERR_INVALID, "mfx_gram_cross_vjp: null argument");
+  MFX_REQUIRE(op->n >= 1 && m >= 1 && batch >= 1 && ldl >= m && ldr >= op->n, MFX_ERR_INVALID, "mfx_gram_cross_vjp: bad sizes");
+  return op_cross_vjp(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
 int mfx_partial_cholesky(const mfx_operator* op, int64_t rank, int pivot, int with_noise, void* lt, void* pivots,
                          void* success, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(op && lt && pivots && success, MFX_ERR_INVALID, "mfx_partial_cholesky: null argument");

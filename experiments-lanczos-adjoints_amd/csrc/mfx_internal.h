@@ -128,6 +128,13 @@ int check_grads_x(const mfx_operator* op, const mfx_op_grads* grads, bool sharde
 int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m);
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);
+// the transpose K(X, X_new) u of op_cross_apply (same workspace) and its VJP sweeps (workspace rbf_cross_vjp_ws_bytes); both
+// refuse other operator kinds, row blocks and null operator data before any launch
+int op_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const void* u, int64_t ldu, void* y, int64_t ldy,
+                     int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);
+int64_t rbf_cross_vjp_ws_bytes(const mfx_operator* op, int64_t m);
+int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl, const void* R, int64_t ldr,
+                 int64_t batch, const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream);
 
 #ifdef __HIPCC__
 // ---- wave64 / workgroup reductions -------------------------------------------------------------

@@ -309,8 +309,9 @@ constexpr int kWideTJ = 32;   // columns per tile, matvec
 constexpr int kWideGJ = 16;   // columns per tile, parameter sweep
 constexpr int kWideGC = 32;   // ARD dimensions a workgroup of the sweep accumulates (blockIdx.y selects them)
 
-// dot[jj] += <x_i, x_j> over all chunks of the padded d axis; TJ columns j0 .. j0 + TJ
-template <typename T, int TJ>
+// dot[jj] += <x_i, x_j> over all chunks of the padded d axis; TJ columns j0 .. j0 + TJ.  TAG only separates instantiations: the
+// cross sweep takes its own (sharing k_rbf_grad_wide's <double, 16> reordered two registers of that kernel's code)
+template <typename T, int TJ, int TAG = 0>
 __device__ __forceinline__ void wide_dots(const T* __restrict__ xs, int64_t n, int dpad, const T* __restrict__ xrow, int64_t ic,
                                           int64_t j0, T (*xiT)[256], T (*xjT)[TJ], T (&dot)[TJ]) {
   constexpr int CH = Wide<T>::CH;
@@ -676,6 +677,267 @@ __global__ __launch_bounds__(256) void k_rbf_grad_final(const double* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Cross-covariance VJP: the gradient of G = sum_b L_b^T K(P, Q) R_b = sum_oj S_oj K_oj (S_oj = sum_b L_b[o] R_b[j], never
+// materialised) for two DIFFERENT point sets, the OWNER rows P (mo) and the columns Q (nc).  The posterior mean's
+// y = K(X_new, X) v with cotangent ybar is owner = X_new (L = ybar, R = v); its X gradient is the same sum with owner = X
+// (L = v, R = ybar).  With xs = x / l, dist = |xs_o - xs_j|^2 as k_rbf_apply computes it and dK/d dist = -s wl / 2:
+//   d/ds   = sum S_oj K_oj / s                      d/dl_c = (s / l_c) sum S_oj wl_oj (xs_oc - xs_jc)^2 (scalar l: w dist)
+//   d/dP_oc = -(s / l_c) sum_j S_oj wl_oj (xs_oc - xs_jc)
+// No noise term.  Pairs with dist <= 0 (a test point equal to a training point) add nothing to the l and P terms (the
+// reference's max(0, .), as in k_rbf_grad_x).  One owner row per thread, the other set's columns streamed through LDS in
+// tiles; the column range is split over the grid's y axis (z for the wide form) so that a small owner set (a handful of
+// acquisition points) still fills the chip.  go != null (a single split): go (mo, d) += the row's sums directly; else
+// gpart (splits, mo, DPAD) gets the per-split fp64 sums and k_rbf_cross_gx_final adds them up in split order.  THETA: the
+// workgroup's l / s sums go to partial (splits x blocks, DPAD + 2) in k_rbf_grad_final's layout (noise slot 0).  No atomics
+// anywhere: bitwise reproducible.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int DPAD, bool THETA, bool GX>
+__global__ __launch_bounds__(256) void k_rbf_cross_grad(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
+                                                        const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
+                                                        int64_t chunk, int d, int ard, int kind, const T* __restrict__ L,
+                                                        int64_t ldl, const T* __restrict__ R, int64_t ldr, int64_t batch,
+                                                        const T* __restrict__ ls, const T* __restrict__ outputscale,
+                                                        T* __restrict__ go, double* __restrict__ gpart,
+                                                        double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) T xj[kGradTJ][DPAD];
+  __shared__ T sqj[kGradTJ];
+  __shared__ T rj[kGradBC][kGradTJ];
+  __shared__ double red[4][DPAD + 2];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < mo;
+  const bool wave_live = (int64_t)blockIdx.x * 256 + wid * 64 < mo;  // (uniform per wave: dead waves only stage tiles)
+  const int64_t ic = live ? i : mo - 1;
+  const int64_t jb = (int64_t)blockIdx.y * chunk;
+  const int64_t je = jb + chunk < nc ? jb + chunk : nc;
+  T xi[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) xi[c] = xo[ic * DPAD + c];
+  const T sqi = sqo[ic];
+  double gt[DPAD + 2];  // THETA: [0..DPAD) lengthscale dims (scalar: [0]), [DPAD] outputscale, [DPAD + 1] noise (stays 0)
+  double gx[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD + 2; ++c) gt[c] = 0.0;
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) gx[c] = 0.0;
+  for (int64_t j0 = jb; j0 < je; j0 += kGradTJ) {
+    T S[kGradTJ];
+#pragma unroll
+    for (int jj = 0; jj < kGradTJ; ++jj) S[jj] = T(0);
+    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
+      __syncthreads();
+      for (int t = tid; t < kGradBC * kGradTJ; t += 256) {
+        const int q = t / kGradTJ, jj = t % kGradTJ;
+        rj[q][jj] = (bt0 + q < batch && j0 + jj < je) ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
+      }
+      __syncthreads();
+      if (!wave_live) continue;
+      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
+      for (int q = 0; q < qmax; ++q) {
+        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
+#pragma unroll
+        for (int jj = 0; jj < kGradTJ; ++jj) S[jj] += l * rj[q][jj];
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < kGradTJ * DPAD; t += 256) {
+      const int64_t gi = j0 * DPAD + t;
+      (&xj[0][0])[t] = gi < je * DPAD ? xc[gi] : T(0);
+    }
+    if (tid < kGradTJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
+    __syncthreads();
+    if (!wave_live) continue;
+#pragma unroll
+    for (int jj = 0; jj < kGradTJ; ++jj) {
+      if (j0 + jj >= je) continue;
+      T dot = T(0);
+#pragma unroll
+      for (int c = 0; c < DPAD; ++c) dot += xi[c] * xj[jj][c];
+      const T raw = sqi + sqj[jj] - T(2) * dot;
+      const T dist = raw > T(0) ? raw : T(0);
+      T kv, wl;
+      kernel_eval<T>(kind, dist, kv, wl);
+      if (THETA) gt[DPAD] += (double)(S[jj] * kv);
+      if (!(raw > T(0))) continue;  // clamped: no l or input gradient
+      const T w = S[jj] * wl;
+      if (THETA) {
+        if (ard) {
+#pragma unroll
+          for (int c = 0; c < DPAD; ++c) {
+            const T df = xi[c] - xj[jj][c];
+            gt[c] += (double)(w * df * df);
+          }
+        } else {
+          gt[0] += (double)(w * dist);
+        }
+      }
+      if (GX) {
+#pragma unroll
+        for (int c = 0; c < DPAD; ++c) gx[c] += (double)(w * (xi[c] - xj[jj][c]));
+      }
+    }
+  }
+  if (THETA) {
+#pragma unroll
+    for (int c = 0; c < DPAD + 2; ++c) {
+      const double v = wave_sum(live ? gt[c] : 0.0);
+      if (lane == 0) red[wid][c] = v;
+    }
+    __syncthreads();
+    if (tid < DPAD + 2)
+      partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (DPAD + 2) + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  }
+  if (!GX || !live) return;
+  if (go) {
+    const double s = (double)outputscale[0];
+#pragma unroll
+    for (int c = 0; c < DPAD; ++c)
+      if (c < d) go[i * d + c] += (T)(-s / (double)ls[ard ? c : 0] * gx[c]);
+  } else if (gpart) {
+#pragma unroll
+    for (int c = 0; c < DPAD; ++c) gpart[((int64_t)blockIdx.y * mo + i) * DPAD + c] = gx[c];
+  }
+}
+
+// the cross sweep for wide inputs (d > 32): as k_rbf_cross_grad with the distances of wide_dots; blockIdx.y selects kWideGC of
+// the row's d sums (ARD lengthscale and input gradient; a scalar lengthscale without input gradient has one selection, as in
+// k_rbf_grad_wide), blockIdx.z is the column split
+template <typename T, bool THETA, bool GX>
+__global__ __launch_bounds__(256) void k_rbf_cross_grad_wide(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
+                                                             const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
+                                                             int64_t chunk, int dpad, int d, int ard, int kind,
+                                                             const T* __restrict__ L, int64_t ldl, const T* __restrict__ R,
+                                                             int64_t ldr, int64_t batch, const T* __restrict__ ls,
+                                                             const T* __restrict__ outputscale, T* __restrict__ go,
+                                                             double* __restrict__ gpart, double* __restrict__ partial) {
+  constexpr int CH = Wide<T>::CH;
+  __shared__ __attribute__((aligned(16))) T xiT[CH][256];
+  __shared__ __attribute__((aligned(16))) T xjT[CH][kWideGJ];
+  __shared__ __attribute__((aligned(16))) T xjg[kWideGJ][kWideGC];
+  __shared__ T sqj[kWideGJ];
+  __shared__ T rj[kGradBC][kWideGJ];
+  __shared__ double red[4][kWideGC + 2];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int gc = (int)blockIdx.y;  // dimensions gc * 32 .. gc * 32 + 31
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < mo;
+  const bool wave_live = (int64_t)blockIdx.x * 256 + wid * 64 < mo;
+  const int64_t ic = live ? i : mo - 1;
+  const int64_t jb = (int64_t)blockIdx.z * chunk;
+  const int64_t je = jb + chunk < nc ? jb + chunk : nc;
+  const bool sel = ard || GX;  // this selection's 32 dimensions are needed
+  const T sqi = sqo[ic];
+  T xig[kWideGC];
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) xig[c] = sel ? xo[ic * dpad + gc * kWideGC + c] : T(0);
+  double gt[kWideGC + 2];  // THETA: [0 .. 32) this selection's lengthscale dims (scalar: [0]); [32] outputscale; [33] noise
+  double gx[kWideGC];
+#pragma unroll
+  for (int c = 0; c < kWideGC + 2; ++c) gt[c] = 0.0;
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) gx[c] = 0.0;
+  for (int64_t j0 = jb; j0 < je; j0 += kWideGJ) {
+    T S[kWideGJ];
+#pragma unroll
+    for (int jj = 0; jj < kWideGJ; ++jj) S[jj] = T(0);
+    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
+      __syncthreads();
+      for (int t = tid; t < kGradBC * kWideGJ; t += 256) {
+        const int q = t / kWideGJ, jj = t % kWideGJ;
+        rj[q][jj] = (bt0 + q < batch && j0 + jj < je) ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
+      }
+      __syncthreads();
+      if (!wave_live) continue;
+      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
+      for (int q = 0; q < qmax; ++q) {
+        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
+#pragma unroll
+        for (int jj = 0; jj < kWideGJ; ++jj) S[jj] += l * rj[q][jj];
+      }
+    }
+    __syncthreads();
+    if (tid < kWideGJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
+    if (sel)
+      for (int t = tid; t < kWideGJ * kWideGC; t += 256) {
+        const int jj = t / kWideGC, c = t % kWideGC;
+        xjg[jj][c] = (j0 + jj < je) ? xc[(j0 + jj) * dpad + gc * kWideGC + c] : T(0);
+      }
+    T dot[kWideGJ];
+    wide_dots<T, kWideGJ, 1>(xc, je, dpad, xo, ic, j0, xiT, xjT, dot);  // (its barriers publish sqj / xjg too)
+    if (!wave_live) continue;
+#pragma unroll
+    for (int jj = 0; jj < kWideGJ; ++jj) {
+      if (j0 + jj >= je) continue;
+      const T raw = sqi + sqj[jj] - T(2) * dot[jj];
+      const T dist = raw > T(0) ? raw : T(0);
+      T kv, wl;
+      kernel_eval<T>(kind, dist, kv, wl);
+      if (THETA && gc == 0) gt[kWideGC] += (double)(S[jj] * kv);
+      if (!(raw > T(0))) continue;
+      const T w = S[jj] * wl;
+      if (THETA) {
+        if (ard) {
+#pragma unroll
+          for (int c = 0; c < kWideGC; ++c) {
+            const T df = xig[c] - xjg[jj][c];
+            gt[c] += (double)(w * df * df);
+          }
+        } else if (gc == 0) {
+          gt[0] += (double)(w * dist);
+        }
+      }
+      if (GX) {
+#pragma unroll
+        for (int c = 0; c < kWideGC; ++c) gx[c] += (double)(w * (xig[c] - xjg[jj][c]));
+      }
+    }
+  }
+  if (THETA) {
+#pragma unroll
+    for (int c = 0; c < kWideGC + 2; ++c) {
+      const double v = wave_sum(live ? gt[c] : 0.0);
+      if (lane == 0) red[wid][c] = v;
+    }
+    __syncthreads();
+    double* out = partial + ((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * (dpad + 2);
+    if (ard) {
+      if (tid < kWideGC) out[gc * kWideGC + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    } else if (gc == 0) {
+      if (tid == 0) out[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+      for (int c = 1 + tid; c < dpad; c += 256) out[c] = 0.0;  // (the columns k_rbf_grad_final sums and drops)
+    }
+    if (gc == 0 && tid >= kWideGC && tid < kWideGC + 2)
+      out[dpad + tid - kWideGC] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  }
+  if (!GX || !live) return;
+  if (go) {
+    const double s = (double)outputscale[0];
+#pragma unroll
+    for (int c = 0; c < kWideGC; ++c) {
+      const int col = gc * kWideGC + c;
+      if (col < d) go[i * d + col] += (T)(-s / (double)ls[ard ? col : 0] * gx[c]);
+    }
+  } else if (gpart) {
+#pragma unroll
+    for (int c = 0; c < kWideGC; ++c) gpart[((int64_t)blockIdx.z * mo + i) * dpad + gc * kWideGC + c] = gx[c];
+  }
+}
+
+// go (mo, d) += -(s / l_c) * sum over the splits of gpart (splits, mo, dpad), in split order
+template <typename T>
+__global__ __launch_bounds__(256) void k_rbf_cross_gx_final(const double* __restrict__ gpart, int64_t nsplit, int64_t mo, int dpad,
+                                                            int d, int ard, const T* __restrict__ ls,
+                                                            const T* __restrict__ outputscale, T* __restrict__ go) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= mo * d) return;
+  const int64_t o = e / d;
+  const int c = (int)(e % d);
+  double acc = 0.0;
+  for (int64_t q = 0; q < nsplit; ++q) acc += gpart[(q * mo + o) * dpad + c];
+  go[e] += (T)(-(double)outputscale[0] / (double)ls[ard ? c : 0] * acc);
+}
+
 constexpr int kRbfMaxD = 1024;  // wide inputs (d > 32): padded to a multiple of 32, k_rbf_apply_wide / k_rbf_grad_wide
 static int rbf_dpad(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 12 ? 12 : d <= 16 ? 16 : d <= kRbfMaxD ? (d + 31) / 32 * 32 : -1; }
 
@@ -975,6 +1237,240 @@ int check_grads_x(const mfx_operator* op, const mfx_op_grads* grads, bool sharde
   MFX_REQUIRE(!sharded && op->nrows == 0, MFX_ERR_UNSUPPORTED,
               "the input gradient (grads->x) is not available on row blocks or row-sharded drivers");
   return MFX_OK;
+}
+
+// the refusals shared by the transposed cross matvec and the cross VJP (before any launch)
+static int check_cross_op(const mfx_operator* op) {
+  MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_UNSUPPORTED, "cross-covariance matvec needs a kernel-Gram operator");
+  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "unsupported dtype %d", op->dtype);
+  MFX_REQUIRE(op->x && op->lengthscale && op->outputscale, MFX_ERR_INVALID, "RBF operator with null pointers");
+  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "the cross-covariance transpose and VJP need the whole operator (no row block)");
+  MFX_REQUIRE(rbf_dpad(op->d) > 0, MFX_ERR_UNSUPPORTED, "RBF operator supports d <= 1024 (got %d)", op->d);
+  return MFX_OK;
+}
+
+// y (p, n) = K(X, X_new) u, u (p, m): the forward kernels with the roles swapped -- rows from the prepared X, columns from the
+// prepared X_new, row0 = -1 (no self distances, no noise).  The noise argument of the kernels is not read in that mode.
+template <typename T>
+static int rbf_cross_apply_t(const mfx_operator* op, const T* xnew, int64_t m, const T* u, int64_t ldu, T* y, int64_t ldy,
+                             int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  const int dpad = rbf_dpad(op->d);
+  RbfWs w;
+  const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
+  Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
+  T* xr = (T*)cv.take(m * dpad * sizeof(T));
+  T* sqr = (T*)cv.take(m * sizeof(T));
+  MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "cross-Gram workspace too small");
+  MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
+  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
+                                                                xr, sqr);
+  MFX_CHECK_LAUNCH();
+  const T *s = (const T*)op->outputscale, *xrow = (const T*)w.xs, *sqrow = (const T*)w.sq;
+  const int64_t nrow = op->n;
+  const unsigned gx = (unsigned)((nrow + 255) / 256);
+  if (dpad <= 32) {
+#define MFX_RBF_T_LAUNCH(D, PB)                                                                                                \
+  k_rbf_apply<T, D, PB><<<dim3(gx, (unsigned)((p + PB - 1) / PB)), 256, 0, stream>>>(xr, sqr, m, s, s, u, ldu, y, ldy, p,      \
+                                                                                      op->kernel_fn, xrow, sqrow, nrow, -1)
+#define MFX_RBF_T_D(D)              \
+  if (p == 1) {                     \
+    MFX_RBF_T_LAUNCH(D, 1);         \
+  } else if (p == 2) {              \
+    MFX_RBF_T_LAUNCH(D, 2);         \
+  } else if (p <= 4) {              \
+    MFX_RBF_T_LAUNCH(D, 4);         \
+  } else {                          \
+    MFX_RBF_T_LAUNCH(D, 8);         \
+  }
+    switch (dpad) {
+      case 4: MFX_RBF_T_D(4); break;
+      case 8: MFX_RBF_T_D(8); break;
+      case 12: MFX_RBF_T_D(12); break;
+      case 16: MFX_RBF_T_D(16); break;
+      default: MFX_RBF_T_D(32); break;
+    }
+#undef MFX_RBF_T_D
+#undef MFX_RBF_T_LAUNCH
+  } else {
+#define MFX_RBF_T_LAUNCH(PB)                                                                                                      \
+  k_rbf_apply_wide<T, PB><<<dim3(gx, (unsigned)((p + PB - 1) / PB)), 256, 0, stream>>>(xr, sqr, m, dpad, s, s, u, ldu, y, ldy, p, \
+                                                                                        op->kernel_fn, xrow, sqrow, nrow, -1)
+    if (p == 1) {
+      MFX_RBF_T_LAUNCH(1);
+    } else if (p <= 4 || sizeof(T) == 8) {
+      MFX_RBF_T_LAUNCH(4);
+    } else {
+      if constexpr (sizeof(T) == 4) MFX_RBF_T_LAUNCH(8);
+    }
+#undef MFX_RBF_T_LAUNCH
+  }
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+int op_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const void* u, int64_t ldu, void* y, int64_t ldy,
+                     int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  MFX_TRY(check_cross_op(op));
+  ScopedTimer t(0, stream);
+  if (op->dtype == MFX_F32)
+    return rbf_cross_apply_t<float>(op, (const float*)xnew, m, (const float*)u, ldu, (float*)y, ldy, p, ws, ws_bytes, stream);
+  return rbf_cross_apply_t<double>(op, (const double*)xnew, m, (const double*)u, ldu, (double*)y, ldy, p, ws, ws_bytes, stream);
+}
+
+// Column split of the cross sweep: enough workgroups (owner blocks x selections x splits) to fill the chip, every split at
+// least kCrossMinCols columns, whole tiles of 16 columns (kGradTJ == kWideGJ).  A split count >= 2 routes the owner gradient
+// through per-split fp64 partials.
+constexpr int64_t kCrossFill = 1024;    // 4 workgroups per CU of the 256
+constexpr int64_t kCrossMinCols = 128;
+struct CrossPlan {
+  int64_t gx, gy, chunk;
+};
+static CrossPlan cross_plan(int64_t mo, int64_t nc, int64_t sel) {
+  CrossPlan c;
+  c.gx = (mo + 255) / 256;
+  int64_t gy = (kCrossFill + c.gx * sel - 1) / (c.gx * sel);
+  const int64_t maxy = (nc + kCrossMinCols - 1) / kCrossMinCols;
+  gy = gy < maxy ? gy : maxy;
+  gy = gy > 1 ? gy : 1;
+  c.chunk = ((nc + gy - 1) / gy + kGradTJ - 1) / kGradTJ * kGradTJ;
+  c.gy = (nc + c.chunk - 1) / c.chunk;
+  return c;
+}
+
+// bytes past rbf_carve: X_new prepared, the l / s partials, the per-split owner partials.  Sized with one selection, the most
+// splits any launch of rbf_cross_vjp makes (more selections only lower the split count).
+static int64_t cross_vjp_extra(const mfx_operator* op, int64_t m, int64_t* theta_bytes, int64_t* gpart_bytes) {
+  const int dpad = rbf_dpad(op->d) > 0 ? rbf_dpad(op->d) : 1;
+  int64_t tb = 0, gb = 0;
+  const int64_t owners[2][2] = {{m, op->n}, {op->n, m}};
+  for (const auto& oc : owners) {
+    const CrossPlan pl = cross_plan(oc[0], oc[1], 1);
+    const int64_t t = pl.gx * pl.gy * (dpad + 2) * (int64_t)sizeof(double);
+    const int64_t g = pl.gy > 1 ? pl.gy * oc[0] * dpad * (int64_t)sizeof(double) : 0;
+    tb = t > tb ? t : tb;
+    gb = g > gb ? g : gb;
+  }
+  if (theta_bytes) *theta_bytes = tb;
+  if (gpart_bytes) *gpart_bytes = gb;
+  const size_t es = dtype_size(op->dtype);
+  return align_up(m * dpad * es, 256) + align_up(m * es, 256) + align_up(tb, 256) + align_up(gb, 256);
+}
+
+int64_t rbf_cross_vjp_ws_bytes(const mfx_operator* op, int64_t m) {
+  return rbf_carve(op, nullptr, 0, nullptr) + cross_vjp_extra(op, m, nullptr, nullptr);
+}
+
+// one sweep with owner rows (xo, sqo, mo) against the columns (xc, sqc, nc); S = L^T R with L (batch, mo), R (batch, nc).
+// The l / s sums and the owner gradient share one sweep where both sets of fp64 sums fit the registers (d <= 16); at padded
+// d = 32 and for wide inputs the shared form spills (34 registers at DPAD 32 in fp32), so there they are two sweeps.
+template <typename T>
+static int cross_sweep(const mfx_operator* op, int dpad, const T* xo, const T* sqo, int64_t mo, const T* xc, const T* sqc, int64_t nc,
+                       const T* L, int64_t ldl, const T* R, int64_t ldr, int64_t batch, bool theta, T* go, double* gpart,
+                       double* partial, int64_t* nblocks, hipStream_t stream) {
+  const bool shared = dpad < 32;
+  if (theta && go && !shared) {
+    MFX_TRY(cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, L, ldl, R, ldr, batch, true, nullptr, gpart, partial, nblocks, stream));
+    return cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, L, ldl, R, ldr, batch, false, go, gpart, partial, nblocks, stream);
+  }
+  const int64_t sel = dpad > 32 && (op->ard || go) ? dpad / kWideGC : 1;
+  const CrossPlan pl = cross_plan(mo, nc, sel);
+  T* gdirect = pl.gy == 1 ? go : nullptr;
+  double* gp = go && pl.gy > 1 ? gpart : nullptr;
+  if (theta) *nblocks = pl.gx * pl.gy;
+  const T *ls = (const T*)op->lengthscale, *s = (const T*)op->outputscale;
+  if (dpad <= 32) {
+    const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+#define MFX_CROSS_GRAD(D, TH, GX)                                                                                               \
+  k_rbf_cross_grad<T, D, TH, GX><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, op->d, op->ard, op->kernel_fn, L, ldl, \
+                                                           R, ldr, batch, ls, s, gdirect, gp, partial)
+#define MFX_CROSS_GRAD_D(D)                      \
+  if (!go) {                                     \
+    MFX_CROSS_GRAD(D, true, false);              \
+  } else if (!theta) {                           \
+    MFX_CROSS_GRAD(D, false, true);              \
+  } else {                                       \
+    if constexpr (D < 32) MFX_CROSS_GRAD(D, true, true); \
+  }
+    switch (dpad) {
+      case 4: MFX_CROSS_GRAD_D(4); break;
+      case 8: MFX_CROSS_GRAD_D(8); break;
+      case 12: MFX_CROSS_GRAD_D(12); break;
+      case 16: MFX_CROSS_GRAD_D(16); break;
+      default: MFX_CROSS_GRAD_D(32); break;
+    }
+#undef MFX_CROSS_GRAD_D
+#undef MFX_CROSS_GRAD
+  } else {
+    const dim3 grid((unsigned)pl.gx, (unsigned)sel, (unsigned)pl.gy);
+#define MFX_CROSS_GRAD_W(TH, GX)                                                                                          \
+  k_rbf_cross_grad_wide<T, TH, GX><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, dpad, op->d, op->ard,    \
+                                                             op->kernel_fn, L, ldl, R, ldr, batch, ls, s, gdirect, gp, partial)
+    if (!go) {
+      MFX_CROSS_GRAD_W(true, false);
+    } else {
+      MFX_CROSS_GRAD_W(false, true);
+    }
+#undef MFX_CROSS_GRAD_W
+  }
+  MFX_CHECK_LAUNCH();
+  if (gp) {
+    k_rbf_cross_gx_final<T><<<(unsigned)((mo * op->d + 255) / 256), 256, 0, stream>>>(gp, pl.gy, mo, dpad, op->d, op->ard, ls, s, go);
+    MFX_CHECK_LAUNCH();
+  }
+  return MFX_OK;
+}
+
+// grads->lengthscale / outputscale += d/dtheta sum_b L_b^T K(X_new, X) R_b, grads->x += d/dX, gxnew += d/dX_new (each if non-null).
+// Owner X_new carries its own gradient and the l / s partials; owner X runs only for grads->x (and then carries the partials
+// when X_new's gradient is not asked for, so that a (theta, X) request is two sweeps, not three).
+template <typename T>
+static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const T* L, int64_t ldl, const T* R, int64_t ldr,
+                         int64_t batch, const mfx_op_grads* grads, T* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  const int dpad = rbf_dpad(op->d);
+  RbfWs w;
+  const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
+  int64_t tb = 0, gb = 0;
+  cross_vjp_extra(op, m, &tb, &gb);
+  Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
+  T* xr = (T*)cv.take(m * dpad * sizeof(T));
+  T* sqr = (T*)cv.take(m * sizeof(T));
+  double* partial = (double*)cv.take(tb);
+  double* gpart = (double*)cv.take(gb);
+  MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "cross-covariance VJP workspace too small");
+  const bool theta = grads->lengthscale || grads->outputscale;
+  T* gx = (T*)grads->x;
+  if (!theta && !gx && !gxnew) return MFX_OK;
+  MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
+  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
+                                                                xr, sqr);
+  MFX_CHECK_LAUNCH();
+  const T *xs = (const T*)w.xs, *sq = (const T*)w.sq;
+  int64_t nblocks = 0;
+  if (gxnew || (theta && !gx))
+    MFX_TRY(cross_sweep<T>(op, dpad, xr, sqr, m, xs, sq, op->n, L, ldl, R, ldr, batch, theta, gxnew, gpart, partial, &nblocks, stream));
+  if (gx)
+    MFX_TRY(cross_sweep<T>(op, dpad, xs, sq, op->n, xr, sqr, m, R, ldr, L, ldl, batch, theta && !gxnew, gx, gpart, partial, &nblocks,
+                           stream));
+  if (theta) {
+    k_rbf_grad_final<T><<<dpad + 2, 256, 0, stream>>>(partial, nblocks, dpad, op->d, op->ard, (const T*)op->lengthscale,
+                                                      (const T*)op->outputscale, (T*)grads->lengthscale, (T*)grads->outputscale,
+                                                      nullptr, nullptr);
+    MFX_CHECK_LAUNCH();
+  }
+  return MFX_OK;
+}
+
+int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl, const void* R, int64_t ldr,
+                 int64_t batch, const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  MFX_TRY(check_cross_op(op));
+  MFX_REQUIRE(!grads->dense_a && !grads->val, MFX_ERR_INVALID,
+              "the cross-covariance VJP fills the kernel-Gram fields only (dense_a / val must be NULL)");
+  ScopedTimer t(1, stream);
+  if (op->dtype == MFX_F32)
+    return rbf_cross_vjp<float>(op, (const float*)xnew, m, (const float*)L, ldl, (const float*)R, ldr, batch, grads, (float*)gxnew,
+                                ws, ws_bytes, stream);
+  return rbf_cross_vjp<double>(op, (const double*)xnew, m, (const double*)L, ldl, (const double*)R, ldr, batch, grads,
+                               (double*)gxnew, ws, ws_bytes, stream);
 }
 
 // ================================================================================================

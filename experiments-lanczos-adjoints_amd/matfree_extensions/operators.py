@@ -173,6 +173,64 @@ class _ApplyFn(torch.autograd.Function):
         return (None, None, dv if ctx.vdim == 2 else dv[0], *grads)
 
 
+class _CrossApplyFn(torch.autograd.Function):
+    """y = K(xnew, X) v; backward = K(X, xnew) dy (mfx_gram_cross_apply_t) and one mfx_gram_cross_vjp call for the lengthscale,
+    outputscale, xnew and X gradients -- each computed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, op, xnew, v, *cparams):
+        _lib.require_device(xnew, v, *cparams)
+        V = (v if v.dim() == 2 else v[None]).contiguous()
+        xnew = xnew.contiguous()
+        if xnew.dim() != 2 or xnew.shape[1] != op.d or V.shape[1] != op.n:
+            raise ValueError(f"cross_apply: xnew {tuple(xnew.shape)}, v {tuple(v.shape)} do not match X {tuple(op.X.shape)}")
+        m, p = xnew.shape[0], V.shape[0]
+        desc = op.descriptor(cparams, V.dtype, op.n)
+        lib = _lib.get()
+        ws = _lib.scratch(int(lib.mfx_gram_cross_workspace_bytes(C.byref(desc), m)), V.device)
+        y = torch.empty((p, m), dtype=V.dtype, device=V.device)
+        _lib.check(lib.mfx_gram_cross_apply(C.byref(desc), _lib.ptr(xnew), m, _lib.ptr(V), op.n, _lib.ptr(y), m, p,
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(V.device)))
+        ctx.op, ctx.vdim = op, v.dim()
+        ctx.save_for_backward(xnew, V, *cparams)
+        return y if v.dim() == 2 else y[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        xnew, V, *cparams = ctx.saved_tensors
+        op, lib = ctx.op, _lib.get()
+        need = ctx.needs_input_grad  # (op, xnew, v, lengthscale, outputscale, noise[, X])
+        DY = (dy if dy.dim() == 2 else dy[None]).contiguous()
+        (p, n), m = V.shape, xnew.shape[0]
+        desc = op.descriptor(cparams, V.dtype, n)
+        stream = _lib.stream_ptr(V.device)
+        dv = gxnew = gls = gs = gx = None
+        if need[2]:
+            ws = _lib.scratch(int(lib.mfx_gram_cross_workspace_bytes(C.byref(desc), m)), V.device)
+            dv = torch.empty_like(V)
+            _lib.check(lib.mfx_gram_cross_apply_t(C.byref(desc), _lib.ptr(xnew), m, _lib.ptr(DY), m, _lib.ptr(dv), n, p,
+                                                  _lib.ptr(ws), ws.numel(), stream))
+            dv = dv if ctx.vdim == 2 else dv[0]
+        want_x = len(need) > 6 and need[6]
+        if need[1] or need[3] or need[4] or want_x:
+            st = _lib.OpGrads()
+            if need[3]:
+                gls = torch.zeros_like(cparams[0])
+                st.lengthscale = gls.data_ptr()
+            if need[4]:
+                gs = torch.zeros_like(cparams[1])
+                st.outputscale = gs.data_ptr()
+            if want_x:
+                gx = torch.zeros_like(cparams[3], memory_format=torch.contiguous_format)
+                st.x = gx.data_ptr()
+            if need[1]:
+                gxnew = torch.zeros_like(xnew)
+            ws = _lib.scratch(int(lib.mfx_gram_cross_vjp_workspace_bytes(C.byref(desc), m, p)), V.device)
+            _lib.check(lib.mfx_gram_cross_vjp(C.byref(desc), _lib.ptr(xnew), m, _lib.ptr(DY), m, _lib.ptr(V), n, p, C.byref(st),
+                                              _lib.ptr(gxnew), _lib.ptr(ws), ws.numel(), stream))
+        return (None, gxnew, dv, gls, gs, None, *((gx,) if len(cparams) > 3 else ()))
+
+
 class DenseOp(NativeOp):
     """matvec(v, A) = A @ v."""
 
@@ -323,22 +381,10 @@ class RbfGramOp(NativeOp):
 
     def cross_apply(self, xnew, v, *params):
         """K(xnew, X) v (no noise term): the prior cross-covariance matvec of the posterior mean
-        (util/gp_util.py:299-305).  xnew (m, d), v (n,) or (p, n) -> (m,) or (p, m).  Not differentiable."""
-        with torch.no_grad():
-            cparams = self.constrain(*params)
-            _lib.require_device(xnew, v, *cparams)
-            V = (v if v.dim() == 2 else v[None]).contiguous()
-            xnew = xnew.to(self.X.dtype).contiguous()
-            if xnew.dim() != 2 or xnew.shape[1] != self.d or V.shape[1] != self.n:
-                raise ValueError(f"cross_apply: xnew {tuple(xnew.shape)}, v {tuple(v.shape)} do not match X {tuple(self.X.shape)}")
-            m, p = xnew.shape[0], V.shape[0]
-            desc = self.descriptor(cparams, V.dtype, self.n)
-            lib = _lib.get()
-            ws = _lib.scratch(int(lib.mfx_gram_cross_workspace_bytes(C.byref(desc), m)), V.device)
-            y = torch.empty((p, m), dtype=V.dtype, device=V.device)
-            _lib.check(lib.mfx_gram_cross_apply(C.byref(desc), _lib.ptr(xnew), m, _lib.ptr(V), self.n, _lib.ptr(y), m, p,
-                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(V.device)))
-        return y if v.dim() == 2 else y[0]
+        (util/gp_util.py:299-305).  xnew (m, d), v (n,) or (p, n) -> (m,) or (p, m).  Differentiable with respect to xnew,
+        v, the lengthscale and outputscale parameters and X (when X.requires_grad); the noise gets no gradient here."""
+        cparams = self.constrain(*params)
+        return _CrossApplyFn.apply(self, xnew.to(self.X.dtype), v, *cparams)
 
     def new_grads(self, ls, s, nz, X=None):
         g = (torch.zeros_like(ls), torch.zeros_like(s), torch.zeros_like(nz))

@@ -386,6 +386,23 @@ int64_t mfx_gram_cross_workspace_bytes(const mfx_operator* op, int64_t m);
 int mfx_gram_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv,
                          void* y, int64_t ldy, int64_t p, void* ws, int64_t ws_bytes, void* stream);
 
+/* The reverse mode of mfx_gram_cross_apply (the gradient of the posterior mean).
+ * mfx_gram_cross_apply_t: y (p, n) = K(X, X_new) u with u (p, m), the transpose of mfx_gram_cross_apply (its VJP with
+ *   respect to v); workspace: mfx_gram_cross_workspace_bytes.
+ * mfx_gram_cross_vjp: with G = sum_b L_b^T K(X_new, X) R_b, L (batch, m), R (batch, n), ACCUMULATES
+ *   grads->lengthscale, grads->outputscale += dG/dtheta;  grads->x (n, d) += dG/dX;  gxnew (m, d) += dG/dX_new
+ *   (each if non-NULL; grads->noise is not touched: the cross-covariance has no noise term).  Pairs whose distance is
+ *   <= 0 add nothing to the lengthscale and input terms.  Deterministic (no atomics).
+ * Both refuse before any launch: a non-Gram operator (MFX_ERR_UNSUPPORTED, as mfx_gram_cross_apply), null or
+ * inconsistent sizes / leading dimensions and grads->dense_a / grads->val set (MFX_ERR_INVALID), a row block
+ * (nrows > 0: MFX_ERR_UNSUPPORTED), a short workspace (MFX_ERR_WORKSPACE). */
+int mfx_gram_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const void* u, int64_t ldu,
+                           void* y, int64_t ldy, int64_t p, void* ws, int64_t ws_bytes, void* stream);
+int64_t mfx_gram_cross_vjp_workspace_bytes(const mfx_operator* op, int64_t m, int64_t batch);
+int mfx_gram_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl,
+                       const void* R, int64_t ldr, int64_t batch, const mfx_op_grads* grads, void* gxnew,
+                       void* ws, int64_t ws_bytes, void* stream);
+
 /* Per-kernel-class device timing with hipEvents recorded on the caller's stream (no host syncs
  * while enabled; events are read back in mfx_timing_read, which synchronises the events).
  * classes: 0 = operator apply, 1 = operator parameter-gradient sweep, 2 = Krylov vector kernels. */
