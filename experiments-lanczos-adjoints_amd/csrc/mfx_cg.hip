@@ -786,6 +786,18 @@ int mfx_gram_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, cons
   return op_cross_vjp(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
+int64_t mfx_gram_cross_vjp_dense_workspace_bytes(const mfx_operator* op, int64_t m) {
+  if (!op || op->kind != MFX_OP_RBF || m <= 0) return -1;
+  return rbf_cross_vjp_ws_bytes(op, m) + 256;
+}
+
+int mfx_gram_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds,
+                             const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes, void* stream) {
+  MFX_REQUIRE(op && xnew && S && grads, MFX_ERR_INVALID, "mfx_gram_cross_vjp_dense: null argument");
+  MFX_REQUIRE(op->n >= 1 && m >= 1 && lds >= op->n, MFX_ERR_INVALID, "mfx_gram_cross_vjp_dense: bad sizes");
+  return op_cross_vjp_dense(op, xnew, m, S, lds, grads, gxnew, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
 int mfx_partial_cholesky(const mfx_operator* op, int64_t rank, int pivot, int with_noise, void* lt, void* pivots,
                          void* success, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(op && lt && pivots && success, MFX_ERR_INVALID, "mfx_partial_cholesky: null argument");

@@ -135,6 +135,9 @@ int op_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const 
 int64_t rbf_cross_vjp_ws_bytes(const mfx_operator* op, int64_t m);
 int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl, const void* R, int64_t ldr,
                  int64_t batch, const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream);
+// the same gradient for a dense weight matrix S (m, n), leading dimension lds (workspace rbf_cross_vjp_ws_bytes)
+int op_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds, const mfx_op_grads* grads,
+                       void* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream);
 
 #ifdef __HIPCC__
 // ---- wave64 / workgroup reductions -------------------------------------------------------------

@@ -938,6 +938,244 @@ __global__ __launch_bounds__(256) void k_rbf_cross_gx_final(const double* __rest
   go[e] += (T)(-(double)outputscale[0] / (double)ls[ard ? c : 0] * acc);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Cross-covariance sweep with a DENSE weight matrix: the gradient of G = sum_aj S_aj K(Xn_a, X_j) for S (m, n), leading dimension
+// lds, given as it is (the predictive variance's S_aj = -2 vbar_a W_aj is diagonal in any batch, so the factored form of
+// k_rbf_cross_grad would need batch = m and an m-long inner loop per entry).  Formulas, kernel_eval weights, the dist <= 0 rule,
+// the column split, the fp64 partials and their fixed-order finals are those of k_rbf_cross_grad / k_rbf_cross_grad_wide; only
+// the S tile is read instead of formed.  TRANS = false: the owners are the rows of S (Xn, X̄n); TRANS = true: the owners are its
+// columns (X, X̄).
+// ------------------------------------------------------------------------------------------------
+
+// S of one owner row against the tile's columns j0 .. j0 + TJ (columns >= je read as 0).  Owner = a row of S: the thread's own TJ
+// consecutive entries, no other thread reads them, so they go straight to registers as 16-byte vector loads (vec: S and lds keep
+// every row's tile 16-byte aligned; the tile is whole) -- an LDS round trip would only add a write, a barrier and a read.  Otherwise,
+// and for the tail tile, scalar loads.  Owner = a column of S: entry (j, i), consecutive owners in consecutive lanes, coalesced.
+template <typename T, bool TRANS, int TJ>
+__device__ __forceinline__ void dense_tile(const T* __restrict__ S, int64_t lds, bool live, int64_t i, int64_t j0, int64_t je,
+                                           int vec, T (&s)[TJ]) {
+#pragma unroll
+  for (int jj = 0; jj < TJ; ++jj) s[jj] = T(0);
+  if (!live) return;
+  if (TRANS) {
+#pragma unroll
+    for (int jj = 0; jj < TJ; ++jj)
+      if (j0 + jj < je) s[jj] = S[(j0 + jj) * lds + i];
+  } else {
+    const T* row = S + i * lds + j0;
+    if (vec && j0 + TJ <= je) {
+      constexpr int V = 16 / (int)sizeof(T);
+#pragma unroll
+      for (int u = 0; u < TJ / V; ++u) {
+        const Pack<T, V> p = load_pack<T, V>(row + u * V);
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[u * V + e] = p.v[e];
+      }
+    } else {
+#pragma unroll
+      for (int jj = 0; jj < TJ; ++jj)
+        if (j0 + jj < je) s[jj] = row[jj];
+    }
+  }
+}
+
+// d <= 32: k_rbf_cross_grad with the S tile of dense_tile (loaded before the tile's barriers, so that its latency hides behind the
+// staging of the column points)
+template <typename T, int DPAD, bool THETA, bool GX, bool TRANS>
+__global__ __launch_bounds__(256) void k_rbf_cross_grad_dense(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
+                                                              const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
+                                                              int64_t chunk, int d, int ard, int kind, const T* __restrict__ S,
+                                                              int64_t lds, int vec, const T* __restrict__ ls,
+                                                              const T* __restrict__ outputscale, T* __restrict__ go,
+                                                              double* __restrict__ gpart, double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) T xj[kGradTJ][DPAD];
+  __shared__ T sqj[kGradTJ];
+  __shared__ double red[4][DPAD + 2];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < mo;
+  const bool wave_live = (int64_t)blockIdx.x * 256 + wid * 64 < mo;
+  const int64_t ic = live ? i : mo - 1;
+  const int64_t jb = (int64_t)blockIdx.y * chunk;
+  const int64_t je = jb + chunk < nc ? jb + chunk : nc;
+  T xi[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) xi[c] = xo[ic * DPAD + c];
+  const T sqi = sqo[ic];
+  double gt[DPAD + 2];  // THETA: [0..DPAD) lengthscale dims (scalar: [0]), [DPAD] outputscale, [DPAD + 1] noise (stays 0)
+  double gx[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD + 2; ++c) gt[c] = 0.0;
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) gx[c] = 0.0;
+  for (int64_t j0 = jb; j0 < je; j0 += kGradTJ) {
+    T Sv[kGradTJ];
+    dense_tile<T, TRANS, kGradTJ>(S, lds, live, i, j0, je, vec, Sv);
+    __syncthreads();
+    for (int t = tid; t < kGradTJ * DPAD; t += 256) {
+      const int64_t gi = j0 * DPAD + t;
+      (&xj[0][0])[t] = gi < je * DPAD ? xc[gi] : T(0);
+    }
+    if (tid < kGradTJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
+    __syncthreads();
+    if (!wave_live) continue;
+#pragma unroll
+    for (int jj = 0; jj < kGradTJ; ++jj) {
+      if (j0 + jj >= je) continue;
+      T dot = T(0);
+#pragma unroll
+      for (int c = 0; c < DPAD; ++c) dot += xi[c] * xj[jj][c];
+      const T raw = sqi + sqj[jj] - T(2) * dot;
+      const T dist = raw > T(0) ? raw : T(0);
+      T kv, wl;
+      kernel_eval<T>(kind, dist, kv, wl);
+      if (THETA) gt[DPAD] += (double)(Sv[jj] * kv);
+      if (!(raw > T(0))) continue;  // clamped: no l or input gradient
+      const T w = Sv[jj] * wl;
+      if (THETA) {
+        if (ard) {
+#pragma unroll
+          for (int c = 0; c < DPAD; ++c) {
+            const T df = xi[c] - xj[jj][c];
+            gt[c] += (double)(w * df * df);
+          }
+        } else {
+          gt[0] += (double)(w * dist);
+        }
+      }
+      if (GX) {
+#pragma unroll
+        for (int c = 0; c < DPAD; ++c) gx[c] += (double)(w * (xi[c] - xj[jj][c]));
+      }
+    }
+  }
+  if (THETA) {
+#pragma unroll
+    for (int c = 0; c < DPAD + 2; ++c) {
+      const double v = wave_sum(live ? gt[c] : 0.0);
+      if (lane == 0) red[wid][c] = v;
+    }
+    __syncthreads();
+    if (tid < DPAD + 2)
+      partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (DPAD + 2) + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  }
+  if (!GX || !live) return;
+  if (go) {
+    const double s = (double)outputscale[0];
+#pragma unroll
+    for (int c = 0; c < DPAD; ++c)
+      if (c < d) go[i * d + c] += (T)(-s / (double)ls[ard ? c : 0] * gx[c]);
+  } else if (gpart) {
+#pragma unroll
+    for (int c = 0; c < DPAD; ++c) gpart[((int64_t)blockIdx.y * mo + i) * DPAD + c] = gx[c];
+  }
+}
+
+// d > 32: k_rbf_cross_grad_wide with the S tile of dense_tile (blockIdx.y selects 32 dimensions, blockIdx.z is the column split)
+template <typename T, bool THETA, bool GX, bool TRANS>
+__global__ __launch_bounds__(256) void k_rbf_cross_grad_dense_wide(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
+                                                                   const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
+                                                                   int64_t chunk, int dpad, int d, int ard, int kind,
+                                                                   const T* __restrict__ S, int64_t lds, int vec,
+                                                                   const T* __restrict__ ls, const T* __restrict__ outputscale,
+                                                                   T* __restrict__ go, double* __restrict__ gpart,
+                                                                   double* __restrict__ partial) {
+  constexpr int CH = Wide<T>::CH;
+  __shared__ __attribute__((aligned(16))) T xiT[CH][256];
+  __shared__ __attribute__((aligned(16))) T xjT[CH][kWideGJ];
+  __shared__ __attribute__((aligned(16))) T xjg[kWideGJ][kWideGC];
+  __shared__ T sqj[kWideGJ];
+  __shared__ double red[4][kWideGC + 2];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int gc = (int)blockIdx.y;  // dimensions gc * 32 .. gc * 32 + 31
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < mo;
+  const bool wave_live = (int64_t)blockIdx.x * 256 + wid * 64 < mo;
+  const int64_t ic = live ? i : mo - 1;
+  const int64_t jb = (int64_t)blockIdx.z * chunk;
+  const int64_t je = jb + chunk < nc ? jb + chunk : nc;
+  const bool sel = ard || GX;
+  const T sqi = sqo[ic];
+  T xig[kWideGC];
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) xig[c] = sel ? xo[ic * dpad + gc * kWideGC + c] : T(0);
+  double gt[kWideGC + 2];
+  double gx[kWideGC];
+#pragma unroll
+  for (int c = 0; c < kWideGC + 2; ++c) gt[c] = 0.0;
+#pragma unroll
+  for (int c = 0; c < kWideGC; ++c) gx[c] = 0.0;
+  for (int64_t j0 = jb; j0 < je; j0 += kWideGJ) {
+    T Sv[kWideGJ];
+    dense_tile<T, TRANS, kWideGJ>(S, lds, live, i, j0, je, vec, Sv);
+    __syncthreads();
+    if (tid < kWideGJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
+    if (sel)
+      for (int t = tid; t < kWideGJ * kWideGC; t += 256) {
+        const int jj = t / kWideGC, c = t % kWideGC;
+        xjg[jj][c] = (j0 + jj < je) ? xc[(j0 + jj) * dpad + gc * kWideGC + c] : T(0);
+      }
+    T dot[kWideGJ];
+    wide_dots<T, kWideGJ, 2>(xc, je, dpad, xo, ic, j0, xiT, xjT, dot);  // (its barriers publish sqj / xjg too)
+    if (!wave_live) continue;
+#pragma unroll
+    for (int jj = 0; jj < kWideGJ; ++jj) {
+      if (j0 + jj >= je) continue;
+      const T raw = sqi + sqj[jj] - T(2) * dot[jj];
+      const T dist = raw > T(0) ? raw : T(0);
+      T kv, wl;
+      kernel_eval<T>(kind, dist, kv, wl);
+      if (THETA && gc == 0) gt[kWideGC] += (double)(Sv[jj] * kv);
+      if (!(raw > T(0))) continue;
+      const T w = Sv[jj] * wl;
+      if (THETA) {
+        if (ard) {
+#pragma unroll
+          for (int c = 0; c < kWideGC; ++c) {
+            const T df = xig[c] - xjg[jj][c];
+            gt[c] += (double)(w * df * df);
+          }
+        } else if (gc == 0) {
+          gt[0] += (double)(w * dist);
+        }
+      }
+      if (GX) {
+#pragma unroll
+        for (int c = 0; c < kWideGC; ++c) gx[c] += (double)(w * (xig[c] - xjg[jj][c]));
+      }
+    }
+  }
+  if (THETA) {
+#pragma unroll
+    for (int c = 0; c < kWideGC + 2; ++c) {
+      const double v = wave_sum(live ? gt[c] : 0.0);
+      if (lane == 0) red[wid][c] = v;
+    }
+    __syncthreads();
+    double* out = partial + ((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * (dpad + 2);
+    if (ard) {
+      if (tid < kWideGC) out[gc * kWideGC + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    } else if (gc == 0) {
+      if (tid == 0) out[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+      for (int c = 1 + tid; c < dpad; c += 256) out[c] = 0.0;
+    }
+    if (gc == 0 && tid >= kWideGC && tid < kWideGC + 2)
+      out[dpad + tid - kWideGC] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  }
+  if (!GX || !live) return;
+  if (go) {
+    const double s = (double)outputscale[0];
+#pragma unroll
+    for (int c = 0; c < kWideGC; ++c) {
+      const int col = gc * kWideGC + c;
+      if (col < d) go[i * d + col] += (T)(-s / (double)ls[ard ? col : 0] * gx[c]);
+    }
+  } else if (gpart) {
+#pragma unroll
+    for (int c = 0; c < kWideGC; ++c) gpart[((int64_t)blockIdx.z * mo + i) * dpad + gc * kWideGC + c] = gx[c];
+  }
+}
+
 constexpr int kRbfMaxD = 1024;  // wide inputs (d > 32): padded to a multiple of 32, k_rbf_apply_wide / k_rbf_grad_wide
 static int rbf_dpad(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 12 ? 12 : d <= 16 ? 16 : d <= kRbfMaxD ? (d + 31) / 32 * 32 : -1; }
 
@@ -1471,6 +1709,132 @@ int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void
                                 ws, ws_bytes, stream);
   return rbf_cross_vjp<double>(op, (const double*)xnew, m, (const double*)L, ldl, (const double*)R, ldr, batch, grads,
                                (double*)gxnew, ws, ws_bytes, stream);
+}
+
+// cross_sweep with a dense S (m, n), lds: owner = its rows (trans = false: xo = X_new) or its columns (trans = true: xo = X).  The
+// same plan, the same split of the theta and owner sums into two launches at DPAD 32 and for wide inputs.
+template <typename T>
+static int cross_sweep_dense(const mfx_operator* op, int dpad, const T* xo, const T* sqo, int64_t mo, const T* xc, const T* sqc,
+                             int64_t nc, const T* S, int64_t lds, bool trans, bool theta, T* go, double* gpart, double* partial,
+                             int64_t* nblocks, hipStream_t stream) {
+  const bool shared = dpad < 32;
+  if (theta && go && !shared) {
+    MFX_TRY(cross_sweep_dense<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, S, lds, trans, true, nullptr, gpart, partial, nblocks, stream));
+    return cross_sweep_dense<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, S, lds, trans, false, go, gpart, partial, nblocks, stream);
+  }
+  const int64_t sel = dpad > 32 && (op->ard || go) ? dpad / kWideGC : 1;
+  const CrossPlan pl = cross_plan(mo, nc, sel);
+  T* gdirect = pl.gy == 1 ? go : nullptr;
+  double* gp = go && pl.gy > 1 ? gpart : nullptr;
+  if (theta) *nblocks = pl.gx * pl.gy;
+  // the row form's 16-byte loads: every tile starts at a multiple of 16 columns, so an aligned S and lds keep each tile aligned
+  const int vec = !trans && (uintptr_t)S % 16 == 0 && (lds * (int64_t)sizeof(T)) % 16 == 0;
+  const T *ls = (const T*)op->lengthscale, *s = (const T*)op->outputscale;
+  if (dpad <= 32) {
+    const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+#define MFX_DENSE_GRAD(D, TH, GX, TR)                                                                                           \
+  k_rbf_cross_grad_dense<T, D, TH, GX, TR><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, op->d, op->ard,          \
+                                                                     op->kernel_fn, S, lds, vec, ls, s, gdirect, gp, partial)
+#define MFX_DENSE_GRAD_T(D, TH, GX)  \
+  if (trans) {                       \
+    MFX_DENSE_GRAD(D, TH, GX, true); \
+  } else {                           \
+    MFX_DENSE_GRAD(D, TH, GX, false); \
+  }
+#define MFX_DENSE_GRAD_D(D)                                  \
+  if (!go) {                                                 \
+    MFX_DENSE_GRAD_T(D, true, false);                        \
+  } else if (!theta) {                                       \
+    MFX_DENSE_GRAD_T(D, false, true);                        \
+  } else {                                                   \
+    if constexpr (D < 32) { MFX_DENSE_GRAD_T(D, true, true); } \
+  }
+    switch (dpad) {
+      case 4: MFX_DENSE_GRAD_D(4); break;
+      case 8: MFX_DENSE_GRAD_D(8); break;
+      case 12: MFX_DENSE_GRAD_D(12); break;
+      case 16: MFX_DENSE_GRAD_D(16); break;
+      default: MFX_DENSE_GRAD_D(32); break;
+    }
+#undef MFX_DENSE_GRAD_D
+#undef MFX_DENSE_GRAD_T
+#undef MFX_DENSE_GRAD
+  } else {
+    const dim3 grid((unsigned)pl.gx, (unsigned)sel, (unsigned)pl.gy);
+#define MFX_DENSE_GRAD_W(TH, GX, TR)                                                                                          \
+  k_rbf_cross_grad_dense_wide<T, TH, GX, TR><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, dpad, op->d, op->ard, \
+                                                                       op->kernel_fn, S, lds, vec, ls, s, gdirect, gp, partial)
+    if (!go) {
+      if (trans) {
+        MFX_DENSE_GRAD_W(true, false, true);
+      } else {
+        MFX_DENSE_GRAD_W(true, false, false);
+      }
+    } else {
+      if (trans) {
+        MFX_DENSE_GRAD_W(false, true, true);
+      } else {
+        MFX_DENSE_GRAD_W(false, true, false);
+      }
+    }
+#undef MFX_DENSE_GRAD_W
+  }
+  MFX_CHECK_LAUNCH();
+  if (gp) {
+    k_rbf_cross_gx_final<T><<<(unsigned)((mo * op->d + 255) / 256), 256, 0, stream>>>(gp, pl.gy, mo, dpad, op->d, op->ard, ls, s, go);
+    MFX_CHECK_LAUNCH();
+  }
+  return MFX_OK;
+}
+
+// grads->lengthscale / outputscale += d/dtheta sum_aj S_aj K(X_new_a, X_j), grads->x += d/dX, gxnew += d/dX_new (each if non-null),
+// with rbf_cross_vjp's workspace and its order of sweeps: owner X_new for gxnew (and theta), owner X for grads->x
+template <typename T>
+static int rbf_cross_vjp_dense(const mfx_operator* op, const T* xnew, int64_t m, const T* S, int64_t lds, const mfx_op_grads* grads,
+                               T* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  const int dpad = rbf_dpad(op->d);
+  RbfWs w;
+  const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
+  int64_t tb = 0, gb = 0;
+  cross_vjp_extra(op, m, &tb, &gb);
+  Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
+  T* xr = (T*)cv.take(m * dpad * sizeof(T));
+  T* sqr = (T*)cv.take(m * sizeof(T));
+  double* partial = (double*)cv.take(tb);
+  double* gpart = (double*)cv.take(gb);
+  MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "dense cross-covariance VJP workspace too small");
+  const bool theta = grads->lengthscale || grads->outputscale;
+  T* gx = (T*)grads->x;
+  if (!theta && !gx && !gxnew) return MFX_OK;
+  MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
+  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
+                                                                xr, sqr);
+  MFX_CHECK_LAUNCH();
+  const T *xs = (const T*)w.xs, *sq = (const T*)w.sq;
+  int64_t nblocks = 0;
+  if (gxnew || (theta && !gx))
+    MFX_TRY(cross_sweep_dense<T>(op, dpad, xr, sqr, m, xs, sq, op->n, S, lds, false, theta, gxnew, gpart, partial, &nblocks, stream));
+  if (gx)
+    MFX_TRY(cross_sweep_dense<T>(op, dpad, xs, sq, op->n, xr, sqr, m, S, lds, true, theta && !gxnew, gx, gpart, partial, &nblocks,
+                                 stream));
+  if (theta) {
+    k_rbf_grad_final<T><<<dpad + 2, 256, 0, stream>>>(partial, nblocks, dpad, op->d, op->ard, (const T*)op->lengthscale,
+                                                      (const T*)op->outputscale, (T*)grads->lengthscale, (T*)grads->outputscale,
+                                                      nullptr, nullptr);
+    MFX_CHECK_LAUNCH();
+  }
+  return MFX_OK;
+}
+
+int op_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds, const mfx_op_grads* grads,
+                       void* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  MFX_TRY(check_cross_op(op));
+  MFX_REQUIRE(!grads->dense_a && !grads->val, MFX_ERR_INVALID,
+              "the cross-covariance VJP fills the kernel-Gram fields only (dense_a / val must be NULL)");
+  ScopedTimer t(1, stream);
+  if (op->dtype == MFX_F32)
+    return rbf_cross_vjp_dense<float>(op, (const float*)xnew, m, (const float*)S, lds, grads, (float*)gxnew, ws, ws_bytes, stream);
+  return rbf_cross_vjp_dense<double>(op, (const double*)xnew, m, (const double*)S, lds, grads, (double*)gxnew, ws, ws_bytes, stream);
 }
 
 // ================================================================================================

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+import math
 
 import torch
 
@@ -114,6 +115,10 @@ class RowShardedOp:
     def constrain(self, *params):
         _refuse_input_grad(self.op)
         return self.op.constrain(*params)
+
+    def posterior_variance(self, *args, **kwargs):
+        raise NotImplementedError("the predictive variance is not available on row-sharded operators (it needs K(X, xs) and the "
+                                  "solves on the whole operator); use the operator itself")
 
     def __call__(self, v, *params):
         """this rank's rows of A v from the row shard of v (gathers v first; not differentiable -- the Krylov drivers
@@ -229,6 +234,97 @@ class _CrossApplyFn(torch.autograd.Function):
             _lib.check(lib.mfx_gram_cross_vjp(C.byref(desc), _lib.ptr(xnew), m, _lib.ptr(DY), m, _lib.ptr(V), n, p, C.byref(st),
                                               _lib.ptr(gxnew), _lib.ptr(ws), ws.numel(), stream))
         return (None, gxnew, dv, gls, gs, None, *((gx,) if len(cparams) > 3 else ()))
+
+
+def _kappa0(kind, dtype):
+    """k(x, x) / s: the kernel's own value at distance 0, with the reference's eps inside the square roots (util/gp_util.py:69-148)."""
+    if kind == "rbf":
+        return 1.0
+    r = math.sqrt(torch.finfo(dtype).eps)
+    return (1.0 + r) * math.exp(-r) if kind == "matern32" else math.exp(-r)
+
+
+def _cat_info(parts):
+    """per-chunk solve info dicts -> one dict, the per-right-hand-side tensors concatenated in test-point order"""
+    out = {}
+    for key in parts[0]:
+        vals = [p[key] for p in parts]
+        out[key] = torch.cat(vals) if all(torch.is_tensor(v) and v.dim() > 0 for v in vals) else vals
+    return out
+
+
+class _PosteriorVarFn(torch.autograd.Function):
+    """var_a = s kappa(0) - b_a^T A^-1 b_a with b_a = K(X, xs_a), A = K + noise I.  Forward: per chunk of test points, B = K(xs_c, X)
+    (mfx_gram_cross_apply_t against the identity), W = solve(A, B) without grad, q = rowwise <B, W>.  Backward, with W kept from the
+    forward (d var_a = d(s kappa(0)) - 2 w_a^T db_a + w_a^T dA w_a: no adjoint solve): mfx_gram_cross_vjp_dense with S = -2 vbar W
+    and mfx_op_vjp_params with L = vbar W, R = W -- each only for the gradients asked for."""
+
+    @staticmethod
+    def forward(ctx, op, bound, solve, chunk, info, xs, *cparams):
+        _lib.require_device(xs, *cparams)
+        xs = xs.contiguous()
+        (m, _), n, dt, dev = xs.shape, op.n, xs.dtype, xs.device
+        desc = op.descriptor(cparams, dt, n)
+        lib, stream = _lib.get(), _lib.stream_ptr(dev)
+        keep = any(ctx.needs_input_grad[5:])
+        W = torch.empty((m, n), dtype=dt, device=dev) if keep else None
+        q = torch.empty((m,), dtype=dt, device=dev)
+        parts = []
+        for a0 in range(0, m, chunk):
+            c = min(chunk, m - a0)
+            eye = torch.eye(c, dtype=dt, device=dev)
+            B = torch.empty((c, n), dtype=dt, device=dev)
+            ws = _lib.scratch(int(lib.mfx_gram_cross_workspace_bytes(C.byref(desc), c)), dev)
+            _lib.check(lib.mfx_gram_cross_apply_t(C.byref(desc), _lib.ptr(xs[a0 : a0 + c]), c, _lib.ptr(eye), c, _lib.ptr(B), n, c,
+                                                  _lib.ptr(ws), ws.numel(), stream))
+            Wc, sinfo = solve(bound, B)
+            q[a0 : a0 + c] = (B * Wc).sum(-1)
+            if keep:
+                W[a0 : a0 + c] = Wc
+            parts.append(sinfo)
+        info["solve"] = _cat_info(parts)
+        ctx.op, ctx.kappa0 = op, _kappa0(op.kernel, dt)
+        ctx.save_for_backward(xs, W, *cparams)
+        return cparams[1] * ctx.kappa0 - q
+
+    @staticmethod
+    def backward(ctx, vbar):
+        xs, W, *cparams = ctx.saved_tensors
+        op, lib = ctx.op, _lib.get()
+        need = ctx.needs_input_grad  # (op, bound, solve, chunk, info, xs, lengthscale, outputscale, noise[, X])
+        want_x = len(need) > 9 and need[9]
+        (m, n), dev = W.shape, W.device
+        desc = op.descriptor(cparams, W.dtype, n)
+        stream = _lib.stream_ptr(dev)
+        vbar = vbar.contiguous()
+        gxs = gls = gs = gn = gx = None
+        if need[6]:
+            gls = torch.zeros_like(cparams[0])
+        if need[7]:
+            gs = torch.zeros_like(cparams[1])
+        if need[8]:
+            gn = torch.zeros_like(cparams[2])
+        if want_x:
+            gx = torch.zeros_like(cparams[3], memory_format=torch.contiguous_format)
+        S = None
+        if need[5] or need[6] or need[7] or want_x:  # -2 w_a^T db_a: the cross sweep with the dense weights S = -2 vbar W
+            gxs = torch.zeros_like(xs) if need[5] else None
+            S = W * (-2.0 * vbar)[:, None]
+            st = _lib.OpGrads()
+            st.lengthscale, st.outputscale, st.x = (None if t is None else t.data_ptr() for t in (gls, gs, gx))
+            ws = _lib.scratch(int(lib.mfx_gram_cross_vjp_dense_workspace_bytes(C.byref(desc), m)), dev)
+            _lib.check(lib.mfx_gram_cross_vjp_dense(C.byref(desc), _lib.ptr(xs), m, _lib.ptr(S), n, C.byref(st), _lib.ptr(gxs),
+                                                    _lib.ptr(ws), ws.numel(), stream))
+        if need[6] or need[7] or need[8] or want_x:  # w_a^T dA w_a: the Gram parameter sweep with L = vbar W, R = W, batch m
+            L = S.mul_(-0.5) if S is not None else W * vbar[:, None]  # (scaling by -2, then -1/2, is exact: L == vbar W bitwise)
+            st = _lib.OpGrads()
+            st.lengthscale, st.outputscale, st.noise, st.x = (None if t is None else t.data_ptr() for t in (gls, gs, gn, gx))
+            ws = _lib.workspace(desc, n, 1, m, dev)
+            _lib.check(lib.mfx_op_vjp_params(C.byref(desc), _lib.ptr(L), n, _lib.ptr(W), n, m, C.byref(st), _lib.ptr(ws), ws.numel(),
+                                             stream))
+        if gs is not None:
+            gs += ctx.kappa0 * vbar.sum()
+        return (None, None, None, None, None, gxs, gls, gs, gn, *((gx,) if len(cparams) > 3 else ()))
 
 
 class DenseOp(NativeOp):
@@ -385,6 +481,27 @@ class RbfGramOp(NativeOp):
         v, the lengthscale and outputscale parameters and X (when X.requires_grad); the noise gets no gradient here."""
         cparams = self.constrain(*params)
         return _CrossApplyFn.apply(self, xnew.to(self.X.dtype), v, *cparams)
+
+    def posterior_variance(self, xs, solve, *params, chunk=64, return_info=False):
+        """The latent predictive variance s kappa(0) - diag(K(xs, X) A^-1 K(X, xs)), A = K(X, X) + noise I, at the test points xs
+        (m, d) -> (m,), where kappa(0) is the kernel's value at distance 0 (1 for RBF; the Matern forms keep the reference's eps).
+        Not clamped: rounding can make a value slightly negative.
+
+        solve(A, B) -> (W, info) is any solver of cg.* (a pcg.* solver with its preconditioner bound in a lambda); it runs without
+        grad on batches of at most ``chunk`` right-hand sides B = K(xs_c, X) (c, n).  Differentiable with respect to xs, the three
+        parameters and X (when X.requires_grad) without another solve: the backward reuses the solutions W.  When a gradient is
+        required W is kept from the forward to the backward: m * n elements of X's dtype (1024 test points against 131 072
+        training points in fp32: 512 MiB), plus as much again during the backward.  return_info=True returns (variance, info) with
+        info["solve"] the solver's info per right-hand side, in test-point order."""
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"posterior_variance: chunk must be >= 1, got {chunk}")
+        if xs.dim() != 2 or xs.shape[1] != self.d or xs.shape[0] < 1:
+            raise ValueError(f"posterior_variance: xs {tuple(xs.shape)} must be (m >= 1, {self.d})")
+        cparams = self.constrain(*params)
+        info = {}
+        var = _PosteriorVarFn.apply(self, self.bind(*params), solve, chunk, info, xs.to(self.X.dtype), *cparams)
+        return (var, info) if return_info else var
 
     def new_grads(self, ls, s, nz, X=None):
         g = (torch.zeros_like(ls), torch.zeros_like(s), torch.zeros_like(nz))

@@ -366,3 +366,65 @@ def likelihood_condition_p(matvec, solve_p, *, precondition, constrain):
         return condition_partial
 
     return likelihood, {"raw_noise": torch.empty(())}
+
+
+def _predictive_variance(cov_matvec, solve, xs, noise, observation_noise, chunk):
+    """the clamped predictive variance of likelihood_condition_var[_p] and its info"""
+    latent, info = cov_matvec.op.posterior_variance(xs, solve, *cov_matvec.params, chunk=chunk, return_info=True)
+    clamped = latent < 0
+    var = latent.clamp_min(0.0)
+    if observation_noise:
+        var = var + noise.to(var.dtype)
+    return var, {"variance_solve": info["solve"], "num_clamped": clamped.sum()}
+
+
+def _check_chunk(chunk):
+    if int(chunk) < 1:
+        raise ValueError(f"chunk must be >= 1, got {chunk}")
+    return int(chunk)
+
+
+def likelihood_condition_var(matvec, solve, *, constrain, observation_noise=False, chunk=64):
+    """likelihood_condition with the predictive variance: condition(xs, targets) -> ((mean, variance), info).
+
+    mean is likelihood_condition's.  variance = max(0, s kappa(0) - diag(K(xs, X) A^-1 K(X, xs))) (RbfGramOp.posterior_variance,
+    ``chunk`` test points per batched solve), plus the noise when observation_noise (the variance of a noisy observation; the noise
+    then gets its gradient).  info = {"solve": the mean's solve info, "variance_solve": the solver's info per test point,
+    "num_clamped": how many variances were negative by rounding and clamped to 0}."""
+    chunk = _check_chunk(chunk)
+
+    def likelihood(inputs, mean, kernel, params: dict):
+        cov_matvec = _native_cov(matvec, inputs, kernel, constrain, params["raw_noise"])
+        noise = constrain(params["raw_noise"])
+
+        def condition_partial(xs, targets):
+            weights, info = solve(cov_matvec, targets - _mean_array(mean, inputs))
+            mu = _mean_array(mean, xs) + cov_matvec.op.cross_apply(xs, weights, *cov_matvec.params)
+            var, vinfo = _predictive_variance(cov_matvec, solve, xs, noise, observation_noise, chunk)
+            return (mu, var), {"solve": info, **vinfo}
+
+        return condition_partial
+
+    return likelihood, {"raw_noise": torch.empty(())}
+
+
+def likelihood_condition_var_p(matvec, solve_p, *, precondition, constrain, observation_noise=False, chunk=64):
+    """likelihood_condition_p with the predictive variance, as likelihood_condition_var (the variance solves take the same
+    preconditioner as the mean's)."""
+    chunk = _check_chunk(chunk)
+
+    def likelihood(inputs, mean, kernel, params: dict):
+        cov_matvec = _native_cov(matvec, inputs, kernel, constrain, params["raw_noise"])
+        noise = constrain(params["raw_noise"])
+        pre, _info = precondition(low_rank.without_noise(cov_matvec), len(inputs))
+
+        def condition_partial(xs, targets):
+            weights, info = solve_p(cov_matvec, targets - _mean_array(mean, inputs), P=pre.bind(noise))
+            mu = _mean_array(mean, xs) + cov_matvec.op.cross_apply(xs, weights, *cov_matvec.params)
+            var, vinfo = _predictive_variance(cov_matvec, lambda A, B: solve_p(A, B, P=pre.bind(noise)), xs, noise,
+                                              observation_noise, chunk)
+            return (mu, var), {"solve": info, **vinfo}
+
+        return condition_partial
+
+    return likelihood, {"raw_noise": torch.empty(())}

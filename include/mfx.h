@@ -403,6 +403,18 @@ int mfx_gram_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, cons
                        const void* R, int64_t ldr, int64_t batch, const mfx_op_grads* grads, void* gxnew,
                        void* ws, int64_t ws_bytes, void* stream);
 
+/* The cross-covariance VJP for a DENSE weight matrix (the gradient of the GP predictive variance, whose weights
+ * S_aj = -2 vbar_a W_aj are diagonal in any batch of the factored form above).
+ * mfx_gram_cross_vjp_dense: with G = sum_{a<m, j<n} S[a * lds + j] K(X_new_a, X_j), S (m, n) in the operator's dtype, ACCUMULATES
+ *   grads->lengthscale, grads->outputscale += dG/dtheta;  grads->x (n, d) += dG/dX;  gxnew (m, d) += dG/dX_new
+ *   (each if non-NULL; grads->noise is not touched).  The formulas, the distance <= 0 rule and the determinism of
+ *   mfx_gram_cross_vjp.  Workspace: mfx_gram_cross_vjp_dense_workspace_bytes.
+ * Refuses before any launch, with mfx_gram_cross_vjp's codes: a non-Gram operator or a row block (MFX_ERR_UNSUPPORTED), null
+ * arguments, m < 1, lds < n, grads->dense_a / grads->val set (MFX_ERR_INVALID), a short workspace (MFX_ERR_WORKSPACE). */
+int64_t mfx_gram_cross_vjp_dense_workspace_bytes(const mfx_operator* op, int64_t m);
+int mfx_gram_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds,
+                             const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes, void* stream);
+
 /* Per-kernel-class device timing with hipEvents recorded on the caller's stream (no host syncs
  * while enabled; events are read back in mfx_timing_read, which synchronises the events).
  * classes: 0 = operator apply, 1 = operator parameter-gradient sweep, 2 = Krylov vector kernels. */
