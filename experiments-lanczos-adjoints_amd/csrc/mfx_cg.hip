@@ -646,6 +646,7 @@ int mfx_pcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n,
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
   MFX_REQUIRE(maxiter >= 0 && miniter >= 0, MFX_ERR_INVALID, "negative iteration count");
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
+  MFX_CHECK_KERNEL_FN(op);
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   CgWs w;
@@ -688,6 +689,7 @@ int mfx_pcg_solve_sharded(const mfx_operator* op, const mfx_comm* comm, const vo
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
   MFX_REQUIRE(maxiter >= 0 && miniter >= 0, MFX_ERR_INVALID, "negative iteration count");
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
+  MFX_CHECK_KERNEL_FN(op);
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   CgWs w;
@@ -711,6 +713,7 @@ int mfx_pcg_solve_reortho(const mfx_operator* op, const void* b, int64_t ldb, in
   MFX_REQUIRE(num_matvecs >= 1 && num_matvecs <= 1024, MFX_ERR_INVALID, "num_matvecs %lld outside [1, 1024]",
               (long long)num_matvecs);
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
+  MFX_CHECK_KERNEL_FN(op);
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   const int64_t kdim = (precond_lt && rank > num_matvecs) ? rank : num_matvecs;
@@ -760,6 +763,7 @@ int64_t mfx_gram_cross_workspace_bytes(const mfx_operator* op, int64_t m) {
 int mfx_gram_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y,
                          int64_t ldy, int64_t p, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(op && xnew && v && y, MFX_ERR_INVALID, "mfx_gram_cross_apply: null argument");
+  MFX_CHECK_KERNEL_FN(op);
   MFX_REQUIRE(m >= 1 && p >= 1 && ldv >= op->n && ldy >= m, MFX_ERR_INVALID, "mfx_gram_cross_apply: bad sizes");
   MFX_REQUIRE(p <= 65535 * 8, MFX_ERR_UNSUPPORTED, "too many vectors per call");
   return op_cross_apply(op, xnew, m, v, ldv, y, ldy, p, ws, ws_bytes, static_cast<hipStream_t>(stream));
@@ -803,6 +807,7 @@ int mfx_partial_cholesky(const mfx_operator* op, int64_t rank, int pivot, int wi
   MFX_REQUIRE(op && lt && pivots && success, MFX_ERR_INVALID, "mfx_partial_cholesky: null argument");
   MFX_REQUIRE(op->kind == MFX_OP_DENSE || op->kind == MFX_OP_RBF, MFX_ERR_UNSUPPORTED,
               "partial Cholesky needs element access: dense or kernel-Gram operators only");
+  MFX_CHECK_KERNEL_FN(op);
   MFX_REQUIRE(rank <= op->n, MFX_ERR_INVALID, "Rank exceeds n: %lld >= %lld.", (long long)rank, (long long)op->n);
   MFX_REQUIRE(rank >= 1, MFX_ERR_INVALID, "Rank must be positive, but %lld < 1.", (long long)rank);
   MFX_REQUIRE(rank <= 1024, MFX_ERR_UNSUPPORTED, "rank %lld > 1024 (the preconditioner applies at most 1024 columns)", (long long)rank);

@@ -39,6 +39,12 @@ void set_error(const char* fmt, ...);
     if (_rc != MFX_OK) return _rc; \
   } while (0)
 
+// Gram operators: kernel_fn must name a family this build evaluates.  The device code picks the family with a chain of
+// tests whose last branch is Matern-1/2, so an unknown value has to be refused on the host, before any launch.
+#define MFX_CHECK_KERNEL_FN(op)                                                                                       \
+  MFX_REQUIRE((op)->kind != MFX_OP_RBF || ((op)->kernel_fn >= MFX_KERNEL_RBF && (op)->kernel_fn <= MFX_KERNEL_MATERN52), \
+              MFX_ERR_INVALID, "unknown kernel_fn %d", (op)->kernel_fn)
+
 // ---- device-side timing of kernel classes (hipEvents on the caller's stream) -------------------
 struct ScopedTimer {
   int cls;

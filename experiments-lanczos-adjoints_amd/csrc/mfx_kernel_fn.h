@@ -1,4 +1,5 @@
-// libmfx: the stationary kernel families of the Gram operator (util/gp_util.py:69-184; kinds = MFX_KERNEL_*).
+// libmfx: the stationary kernel families of the Gram operator (util/gp_util.py:69-184, plus nu = 5/2;
+// kinds = MFX_KERNEL_*).
 #pragma once
 #include "mfx_internal.h"
 
@@ -24,6 +25,12 @@ __device__ __forceinline__ void kernel_eval(int kind, T dist, T& kv, T& wl) {
     const T e = exp_neg(r);
     kv = (T(1) + r) * e;
     wl = T(3) * e;
+  } else if (kind == MFX_KERNEL_MATERN52) {
+    // (1 + r + r^2 / 3) exp(-r), r = sqrt(5 s + eps); the weight (5/3) (1 + r) exp(-r) has no division and no kink at 0
+    const T r = sqrt(T(5) * dist + dtype_eps<T>());
+    const T e = exp_neg(r);
+    kv = (T(1) + r * (T(1) + r * T(1.0 / 3.0))) * e;
+    wl = T(5.0 / 3.0) * (T(1) + r) * e;
   } else {
     const T r = sqrt(dist + dtype_eps<T>());
     const T e = exp_neg(r);

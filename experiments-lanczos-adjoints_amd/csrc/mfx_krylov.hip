@@ -920,6 +920,7 @@ static int check_common(const mfx_operator* op, int64_t n, int64_t k, int64_t p)
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_UNSUPPORTED, "unsupported dtype %d", op->dtype);
   MFX_REQUIRE(n >= 1 && p >= 1, MFX_ERR_INVALID, "n=%lld, p=%lld must be positive", (long long)n, (long long)p);
   MFX_REQUIRE(op->n == n, MFX_ERR_INVALID, "operator size %lld != n=%lld", (long long)op->n, (long long)n);
+  MFX_CHECK_KERNEL_FN(op);
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_INVALID, "the Krylov drivers take the whole operator (nrows = 0); row shards go through mfx_*_sharded");
   MFX_REQUIRE(k >= 1 && k <= n, MFX_ERR_INVALID, "Parameter depth %lld is outside the expected range", (long long)k);
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "p=%lld exceeds the grid limit 65535", (long long)p);
@@ -941,6 +942,7 @@ int64_t mfx_workspace_bytes(const mfx_operator* op, int64_t n, int64_t k, int64_
 int mfx_op_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t p,
                  int transpose, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(op && x && y, MFX_ERR_INVALID, "null argument");
+  MFX_CHECK_KERNEL_FN(op);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (op->kind == MFX_OP_CALLBACK) return op_apply_cb(op, transpose ? 1 : 0, x, ldx, nullptr, 0, y, ldy, p, s);
   ScopedTimer t(0, s);
@@ -950,6 +952,7 @@ int mfx_op_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, in
 int mfx_op_vjp_params(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr,
                       int64_t batch, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(op && L && R && grads, MFX_ERR_INVALID, "null argument");
+  MFX_CHECK_KERNEL_FN(op);
   MFX_TRY(check_grads_x(op, grads, false));
   MFX_REQUIRE(op->kind != MFX_OP_CALLBACK, MFX_ERR_UNSUPPORTED, "callback operators own their parameter gradients");
   hipStream_t s = static_cast<hipStream_t>(stream);

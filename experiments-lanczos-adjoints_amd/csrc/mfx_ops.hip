@@ -1379,6 +1379,7 @@ int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m) {
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream) {
   MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_UNSUPPORTED, "cross-covariance matvec needs a kernel-Gram operator");
+  MFX_CHECK_KERNEL_FN(op);
   ScopedTimer t(0, stream);
   if (op->dtype == MFX_F32)
     return rbf_cross_apply<float>(op, (const float*)xnew, m, (const float*)v, ldv, (float*)y, ldy, p, ws, ws_bytes, stream);
@@ -1482,6 +1483,7 @@ static int check_cross_op(const mfx_operator* op) {
   MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_UNSUPPORTED, "cross-covariance matvec needs a kernel-Gram operator");
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "unsupported dtype %d", op->dtype);
   MFX_REQUIRE(op->x && op->lengthscale && op->outputscale, MFX_ERR_INVALID, "RBF operator with null pointers");
+  MFX_CHECK_KERNEL_FN(op);
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "the cross-covariance transpose and VJP need the whole operator (no row block)");
   MFX_REQUIRE(rbf_dpad(op->d) > 0, MFX_ERR_UNSUPPORTED, "RBF operator supports d <= 1024 (got %d)", op->d);
   return MFX_OK;
@@ -1889,6 +1891,7 @@ static int op_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int
     case MFX_OP_RBF:
       MFX_REQUIRE(op->x && op->lengthscale && op->outputscale && op->noise, MFX_ERR_INVALID,
                   "RBF operator with null pointers");
+      MFX_CHECK_KERNEL_FN(op);
       return rbf_apply<T>(op, x, ldx, y, ldy, p, ws, ws_bytes, stream);  // symmetric: transpose ignored
     default:
       set_error("unknown operator kind %d", op->kind);
@@ -1936,6 +1939,7 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
       MFX_CHECK_LAUNCH();
       return MFX_OK;
     case MFX_OP_RBF: {
+      MFX_CHECK_KERNEL_FN(op);
       const bool params = grads->lengthscale || grads->outputscale || grads->noise;
       if (!grads->x) {
         if (!params) return MFX_OK;

@@ -15,9 +15,13 @@ constexpr float kNegHalfLog2e = -0.72134752044448170368f;
 
 // Matern kernels: the distance product is scaled by log2(e)^2 (x 3 for nu = 3/2), so that r' = sqrt(t) is already
 // log2(e) * r:  K = exp2(-r') [nu = 1/2],  (1 + r'/log2(e)) exp2(-r') [nu = 3/2]   (util/gp_util.py:69-148)
+// nu = 5/2: the product is scaled by 5 log2(e)^2 and K = (1 + ln2 r' + ln2^2/3 r'^2) exp2(-r'): one fma more than nu = 3/2
 constexpr float kLog2e = 1.44269504088896340736f;
 constexpr float kLn2 = 0.69314718055994530942f;
+constexpr float kLn2Sq3 = 0.16015100250400667f;  // ln(2)^2 / 3
 constexpr float kEpsF32 = 1.1920928955078125e-7f;
+// factor of the squared distance inside the distance product, per Matern family (RBF uses kNegHalfLog2e)
+template <int KIND> constexpr float matern_nu2() { return KIND == MFX_KERNEL_MATERN52 ? 5.f : (KIND == MFX_KERNEL_MATERN32 ? 3.f : 1.f); }
 // K / outputscale from t = factor * dist (un-clamped), shift = log2 of an optional power-of-two scale of K
 // sqrt as ONE v_sqrt_f32 (1 ulp): __builtin_sqrtf expands to a 16-instruction correctly-rounded sequence, which made
 // the Matern Gram matvec 2.5x the RBF one (every VALU instruction per kernel entry is paid in full here).
@@ -25,6 +29,7 @@ template <int KIND>
 __device__ __forceinline__ float matern_from_t(float t, float shift) {
   const float rp = __builtin_amdgcn_sqrtf(fmaxf(t, 0.f) + kEpsF32 * kLog2e * kLog2e);
   const float e = __builtin_amdgcn_exp2f(shift - rp);
+  if constexpr (KIND == MFX_KERNEL_MATERN52) return e * fmaf(rp, fmaf(rp, kLn2Sq3, kLn2), 1.f);
   return KIND == MFX_KERNEL_MATERN32 ? fmaf(e * rp, kLn2, e) : e;
 }
 // the same from te = t + eps log2(e)^2 (the eps rides in the distance product): max(t, 0) + eps' == max(t + eps', eps'),
@@ -34,6 +39,7 @@ template <int KIND>
 __device__ __forceinline__ float matern_from_te(float te, float scale) {
   const float rp = __builtin_amdgcn_sqrtf(__builtin_amdgcn_fmed3f(te, kEpsC, 3.0e38f));
   const float e = __builtin_amdgcn_exp2f(-rp);
+  if constexpr (KIND == MFX_KERNEL_MATERN52) return e * fmaf(rp, fmaf(rp, kLn2Sq3 * scale, kLn2 * scale), scale);
   return KIND == MFX_KERNEL_MATERN32 ? e * fmaf(rp, kLn2 * scale, scale) : e * scale;
 }
 

@@ -35,12 +35,21 @@ constexpr int kGLd = kGM + 4;  // padded row of the transposed S tile: conflict-
 
 
 __device__ __forceinline__ float dist_factor(int kind) {  // multiplies the squared distance inside the MFMA product
-  return kind == MFX_KERNEL_RBF ? -0.72134752044448170368f : (kind == MFX_KERNEL_MATERN32 ? 3.f : 1.f) * kLog2e * kLog2e;
+  return kind == MFX_KERNEL_RBF ? -0.72134752044448170368f
+                                : (kind == MFX_KERNEL_MATERN52 ? 5.f : (kind == MFX_KERNEL_MATERN32 ? 3.f : 1.f)) * kLog2e * kLog2e;
 }
 
-// epilogue of the gradient GEMMs: K_ij / outputscale and the lengthscale weight from the clamped squared distance
+// epilogue of the gradient GEMMs: K_ij / outputscale and the lengthscale weight from the clamped squared distance.
+// M52: Matern-5/2 has instances of its own (a fourth runtime branch cost the 256 x 256 split tile 12 B of scratch and the
+// padded-64 exact sweep 6 more parked registers); the other three families share one instance and branch on `kind`.
+template <bool M52>
 __device__ __forceinline__ void grad_weights(int kind, float dist, float& kv, float& wl) {
-  if (kind == MFX_KERNEL_RBF) {
+  if constexpr (M52) {
+    const float r = __builtin_amdgcn_sqrtf(5.f * dist + kEpsF32);
+    const float e = __builtin_amdgcn_exp2f(-kLog2e * r);
+    kv = fmaf(r, fmaf(r, 1.f / 3.f, 1.f), 1.f) * e;
+    wl = fmaf(r, 5.f / 3.f, 5.f / 3.f) * e;
+  } else if (kind == MFX_KERNEL_RBF) {
     kv = __builtin_amdgcn_exp2f(-0.72134752044448170368f * dist);
     wl = kv;
   } else if (kind == MFX_KERNEL_MATERN32) {
@@ -206,8 +215,9 @@ __global__ __launch_bounds__(256, 2) void k_rbf_mfma_apply(const float* __restri
           for (int r = 0; r < 16; ++r) {
             float tv = kd[r];
             if (diag_blk && l31 == (r & 3) + 8 * (r >> 2) + 4 * lhi) tv = 0.f;
-            kd[r] = kind == MFX_KERNEL_MATERN32 ? matern_from_t<MFX_KERNEL_MATERN32>(tv, 0.f)
-                                                : matern_from_t<MFX_KERNEL_MATERN12>(tv, 0.f);
+            kd[r] = kind == MFX_KERNEL_MATERN52   ? matern_from_t<MFX_KERNEL_MATERN52>(tv, 0.f)
+                    : kind == MFX_KERNEL_MATERN32 ? matern_from_t<MFX_KERNEL_MATERN32>(tv, 0.f)
+                                                  : matern_from_t<MFX_KERNEL_MATERN12>(tv, 0.f);
           }
         }
 #pragma unroll
@@ -392,7 +402,7 @@ __global__ __launch_bounds__(64 * H3Waves<PK>::value, PK ? 1 : 2) void k_rbf_mfm
   constexpr int kMI = 2, kTJ = 64;
   using Tile = RbfTileH3<DPAD, NB, kTJ, !PK>;
   constexpr int KD = Tile::KD, KS = KD / 2, NKD = Tile::NKD;
-  constexpr float cfac = KIND == MFX_KERNEL_RBF ? kNegHalfLog2e : (KIND == MFX_KERNEL_MATERN32 ? 3.f : 1.f) * kLog2e * kLog2e;
+  constexpr float cfac = KIND == MFX_KERNEL_RBF ? kNegHalfLog2e : matern_nu2<KIND>() * kLog2e * kLog2e;
   extern __shared__ __attribute__((aligned(16))) char h3_smem[];
   Tile* const tile = reinterpret_cast<Tile*>(h3_smem);  // [2]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -922,7 +932,7 @@ __global__ __launch_bounds__(256) void k_pack_tiles(const float* __restrict__ xs
   constexpr int kTJ = 64;
   using Tile = RbfTileH3<DPAD, NB, kTJ>;
   constexpr int KD = Tile::KD, P = Tile::P, AROW = Tile::AROW;
-  constexpr float cfac = KIND == MFX_KERNEL_RBF ? kNegHalfLog2e : (KIND == MFX_KERNEL_MATERN32 ? 3.f : 1.f) * kLog2e * kLog2e;
+  constexpr float cfac = KIND == MFX_KERNEL_RBF ? kNegHalfLog2e : matern_nu2<KIND>() * kLog2e * kLog2e;
   const int tid = threadIdx.x;
   const int64_t t = blockIdx.x, j0 = t * kTJ, ntile = gridDim.x;
   if ((int)blockIdx.y < (int)gridDim.y - 1) {
@@ -1141,6 +1151,7 @@ static int launch_apply_h3(const mfx_operator* op, const float* xs, const float*
     case MFX_KERNEL_RBF: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_RBF>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
     case MFX_KERNEL_MATERN12: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_MATERN12>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
     case MFX_KERNEL_MATERN32: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_MATERN32>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
+    case MFX_KERNEL_MATERN52: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_MATERN52>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
     default: set_error("unknown kernel_fn %d", op->kernel_fn); return MFX_ERR_INVALID;
   }
 }
@@ -1424,8 +1435,8 @@ struct GradSmemH {
 // gradient is 9.8e-6 / 3.0e-5 off fp64, without either 2.2e-2 / 5.6e-2 (profiles/r02h_*) -- so the chunks and the master
 // accumulators are gone, which is what makes room for the 256 x 256 tile.
 
-template <int DPAD, int NBW, bool REGEPI>
-__global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restrict__ xs, const float* __restrict__ sq,
+template <int DPAD, int NBW, bool REGEPI, bool M52>
+__device__ __forceinline__ void rbf_mfma_grad_h_body(const float* __restrict__ xs, const float* __restrict__ sq,
                                                             int64_t n, int64_t npad_l, int64_t npad_r, int ard, int kind,
                                                             const _Float16* __restrict__ Lh, const _Float16* __restrict__ Ll,
                                                             const _Float16* __restrict__ Rh, const _Float16* __restrict__ Rl,
@@ -1728,7 +1739,7 @@ __global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restr
         const bool live = (i0 + il < nrow) && (j < n);
         const float s_ij = live ? sm.u.s_t[jl][il] * (sgi * sm.sgj[jl]) : 0.f;
         float kv, wl;
-        grad_weights(kind, i == j ? 0.f : dist, kv, wl);
+        grad_weights<M52>(kind, i == j ? 0.f : dist, kv, wl);
         gt[DPAD] = fmaf(s_ij, kv, gt[DPAD]);
         const float w = s_ij * wl;
         if (ard) {
@@ -1768,6 +1779,29 @@ __global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restr
   }
 }
 
+// the instance of RBF / Matern-1/2 / Matern-3/2 (runtime `kind`) and, as an overload, the Matern-5/2 one (KIND at compile time)
+template <int DPAD, int NBW, bool REGEPI>
+__global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restrict__ xs, const float* __restrict__ sq,
+                                                            int64_t n, int64_t npad_l, int64_t npad_r, int ard, int kind,
+                                                            const _Float16* __restrict__ Lh, const _Float16* __restrict__ Ll,
+                                                            const _Float16* __restrict__ Rh, const _Float16* __restrict__ Rl,
+                                                            int64_t nkb /* batch_pad / 8 */, int tiles_per_block,
+                                                            uint32_t salt_l, uint32_t salt_r, double* __restrict__ partial,
+                                                            int64_t row0, int64_t nrow, const int* __restrict__ one_product) {
+  rbf_mfma_grad_h_body<DPAD, NBW, REGEPI, false>(xs, sq, n, npad_l, npad_r, ard, kind, Lh, Ll, Rh, Rl, nkb, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
+}
+template <int DPAD, int NBW, bool REGEPI, int KIND>
+__global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restrict__ xs, const float* __restrict__ sq,
+                                                            int64_t n, int64_t npad_l, int64_t npad_r, int ard, int kind,
+                                                            const _Float16* __restrict__ Lh, const _Float16* __restrict__ Ll,
+                                                            const _Float16* __restrict__ Rh, const _Float16* __restrict__ Rl,
+                                                            int64_t nkb /* batch_pad / 8 */, int tiles_per_block,
+                                                            uint32_t salt_l, uint32_t salt_r, double* __restrict__ partial,
+                                                            int64_t row0, int64_t nrow, const int* __restrict__ one_product) {
+  static_assert(KIND == MFX_KERNEL_MATERN52 && !REGEPI, "the register epilogue is RBF only");
+  rbf_mfma_grad_h_body<DPAD, NBW, REGEPI, true>(xs, sq, n, npad_l, npad_r, ard, kind, Lh, Ll, Rh, Rl, nkb, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
+}
+
 int64_t rbf_grad_h_ws_bytes(int64_t n, int64_t batch) {
   const int64_t npad = (n + kHM - 1) / kHM * kHM, bpad = (batch + 31) / 32 * 32;
   return 4 * bpad * npad * (int64_t)sizeof(_Float16) + 3 * bpad * (int64_t)sizeof(float) + 1536;
@@ -1794,6 +1828,15 @@ static int launch_grad_h_t(const mfx_operator* op, const float* xs, const float*
                                                                     bpad / 8, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
       launched = true;
     }
+  }
+  if (!launched && op->kernel_fn == MFX_KERNEL_MATERN52) {
+    const size_t sh = sizeof(GradSmemH<DPAD, NBW, false>);
+    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad_h<DPAD, NBW, false, MFX_KERNEL_MATERN52>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    k_rbf_mfma_grad_h<DPAD, NBW, false, MFX_KERNEL_MATERN52><<<grid, 512, sh, stream>>>(
+        xs, sq, n, npad_l, npad, op->ard, op->kernel_fn, Lh, Ll, Rh, Rl, bpad / 8, tiles_per_block, salt_l, salt_r, partial, row0, nrow,
+        one_product);
+    launched = true;
   }
   if (!launched) {
     const size_t sh = sizeof(GradSmemH<DPAD, NBW, false>);
@@ -2010,8 +2053,8 @@ __device__ __forceinline__ void grad_load_stage(float4 (&ra)[4], float4 (&rb)[4]
   }
 }
 
-template <int DPAD, bool VEC4>
-__global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS, one workgroup per CU anyway */ void k_rbf_mfma_grad(const float* __restrict__ xs, const float* __restrict__ sq,
+template <int DPAD, bool VEC4, bool M52>
+__device__ __forceinline__ void rbf_mfma_grad_body(const float* __restrict__ xs, const float* __restrict__ sq,
                                                           int64_t n, int ard, int kind, const float* __restrict__ L,
                                                           int64_t ldl, const float* __restrict__ R, int64_t ldr,
                                                           int64_t batch, int tiles_per_block,
@@ -2135,7 +2178,7 @@ __global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS,
         const bool live = (i0 + il < nrow) && (j < n);
         const float s_ij = live ? sm.u.s_t[jl][il] : 0.f;
         float kv, wl;
-        grad_weights(kind, i == j ? 0.f : dist, kv, wl);
+        grad_weights<M52>(kind, i == j ? 0.f : dist, kv, wl);
         gt[DPAD] = fmaf(s_ij, kv, gt[DPAD]);
         const float w = s_ij * wl;
         if (ard) {
@@ -2170,6 +2213,25 @@ __global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS,
   }
 }
 
+// as for the split GEMM: one instance for the three runtime families, an overload for Matern-5/2
+template <int DPAD, bool VEC4>
+__global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS, one workgroup per CU anyway */ void k_rbf_mfma_grad(const float* __restrict__ xs, const float* __restrict__ sq,
+                                                          int64_t n, int ard, int kind, const float* __restrict__ L,
+                                                          int64_t ldl, const float* __restrict__ R, int64_t ldr,
+                                                          int64_t batch, int tiles_per_block,
+                                                          double* __restrict__ partial, int64_t row0, int64_t nrow) {
+  rbf_mfma_grad_body<DPAD, VEC4, false>(xs, sq, n, ard, kind, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
+}
+template <int DPAD, bool VEC4, int KIND>
+__global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS, one workgroup per CU anyway */ void k_rbf_mfma_grad(const float* __restrict__ xs, const float* __restrict__ sq,
+                                                          int64_t n, int ard, int kind, const float* __restrict__ L,
+                                                          int64_t ldl, const float* __restrict__ R, int64_t ldr,
+                                                          int64_t batch, int tiles_per_block,
+                                                          double* __restrict__ partial, int64_t row0, int64_t nrow) {
+  static_assert(KIND == MFX_KERNEL_MATERN52, "the other families share the runtime instance");
+  rbf_mfma_grad_body<DPAD, VEC4, true>(xs, sq, n, ard, kind, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
+}
+
 bool rbf_mfma_grad_supported(const mfx_operator* op, int64_t batch) {
   // from n = 2048 on even ONE (lambda, x) pair (the PCG backward of the log-marginal likelihood) is cheaper here: the cost is
   // the n^2 epilogue, which the VALU sweep pays at a quarter of the rate (16.8 vs ~4 ms at n = 36 584)
@@ -2194,7 +2256,15 @@ static int launch_grad(const mfx_operator* op, const float* xs, const float* sq,
   const size_t sh = sizeof(GradSmem<DPAD>);
   const bool vec4 = (n % 4 == 0) && (nrow % 4 == 0) && (ldl % 4 == 0) && (ldr % 4 == 0) && (reinterpret_cast<uintptr_t>(L) % 16 == 0) &&
                     (reinterpret_cast<uintptr_t>(R) % 16 == 0);
-  if (vec4) {
+  if (op->kernel_fn == MFX_KERNEL_MATERN52) {
+#define MFX_GRAD52(V4)                                                                                                        \
+  MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad<DPAD, V4, MFX_KERNEL_MATERN52>),            \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));                                    \
+  k_rbf_mfma_grad<DPAD, V4, MFX_KERNEL_MATERN52><<<grid, 256, sh, stream>>>(xs, sq, n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, \
+                                                                            tiles_per_block, partial, row0, nrow);
+    if (vec4) { MFX_GRAD52(true) } else { MFX_GRAD52(false) }
+#undef MFX_GRAD52
+  } else if (vec4) {
     MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad<DPAD, true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     k_rbf_mfma_grad<DPAD, true><<<grid, 256, sh, stream>>>(xs, sq, n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);

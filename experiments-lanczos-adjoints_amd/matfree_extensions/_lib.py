@@ -20,7 +20,7 @@ MFX_F32, MFX_F64 = 0, 1
 OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK = 0, 1, 2, 3
 REORTHO_NONE, REORTHO_FULL = 0, 1
 RBF_FP32, RBF_F16X3_MATVEC, RBF_F16X3 = 0, 1, 2
-KERNEL_RBF, KERNEL_MATERN12, KERNEL_MATERN32 = 0, 1, 2
+KERNEL_RBF, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 1, 2, 3
 
 CALLBACK_T = C.CFUNCTYPE(
     C.c_int,  # return

@@ -241,6 +241,8 @@ def _kappa0(kind, dtype):
     if kind == "rbf":
         return 1.0
     r = math.sqrt(torch.finfo(dtype).eps)
+    if kind == "matern52":
+        return (1.0 + r + r * r / 3.0) * math.exp(-r)
     return (1.0 + r) * math.exp(-r) if kind == "matern32" else math.exp(-r)
 
 
@@ -415,7 +417,8 @@ def softplus(x, beta=1.0, threshold=20.0):
 class RbfGramOp(NativeOp):
     """(K(X, X) + noise I) v with the reference's scaled-kernel parametrisation, matrix-free.
 
-    kernel: "rbf" (kernel_scaled_rbf, util/gp_util.py:151-184), "matern32" (:69-107), "matern12" (:110-148).
+    kernel: "rbf" (kernel_scaled_rbf, util/gp_util.py:151-184), "matern32" (:69-107), "matern12" (:110-148),
+    "matern52" ((1 + r + r^2 / 3) exp(-r), r = sqrt(5 s + eps); kernel_scaled_matern_52 -- not in the reference).
 
     params = (raw_lengthscale [() or (d,)], raw_outputscale (), raw_noise ());
     lengthscale = softplus(raw_l), outputscale = softplus(raw_s)         (util/gp_util.py:164-165)
@@ -436,7 +439,8 @@ class RbfGramOp(NativeOp):
     kind = _lib.OP_RBF
     _MODES = {"fp32": _lib.RBF_FP32, "f16x3-matvec": _lib.RBF_F16X3_MATVEC, "f16x3": _lib.RBF_F16X3}
 
-    _KERNELS = {"rbf": _lib.KERNEL_RBF, "matern12": _lib.KERNEL_MATERN12, "matern32": _lib.KERNEL_MATERN32}
+    _KERNELS = {"rbf": _lib.KERNEL_RBF, "matern12": _lib.KERNEL_MATERN12, "matern32": _lib.KERNEL_MATERN32,
+                "matern52": _lib.KERNEL_MATERN52}
 
     def __init__(self, X, noise_minval=0.0, precision="f16x3", kernel="rbf"):
         if X.dim() != 2:

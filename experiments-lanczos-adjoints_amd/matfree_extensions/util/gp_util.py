@@ -81,6 +81,17 @@ def kernel_scaled_matern_32(*, shape_in, shape_out):
     return _scaled_kernel(shape_in, shape_out, radial, "matern32")
 
 
+def kernel_scaled_matern_52(*, shape_in, shape_out):
+    """(1 + r + r^2 / 3) exp(-r), r = sqrt(5 |x/l - y/l|^2 + eps): the nu = 5/2 member, with the eps under the root as for
+    nu = 1/2 and 3/2 (the reference stops at 3/2).  Hot path: gram_operator(kernel="matern52")."""
+
+    def radial(s):
+        r = torch.sqrt(5.0 * s + torch.finfo(s.dtype).eps)
+        return (1 + r + r * r / 3) * torch.exp(-r)
+
+    return _scaled_kernel(shape_in, shape_out, radial, "matern52")
+
+
 def kernel_scaled_matern_12(*, shape_in, shape_out):
     """util/gp_util.py:110-148: exp(-r), r = sqrt(|x/l - y/l|^2 + eps).  Hot path: gram_operator(kernel="matern12")."""
 
@@ -223,7 +234,7 @@ def gram_matvec_sequential(*, checkpoint: bool = False, precision="f16x3"):
 
 def _native_cov(matvec, inputs, kernel, constrain, raw_noise):
     if not hasattr(kernel, "native"):
-        raise TypeError("the kernel must come from kernel_scaled_rbf / kernel_scaled_matern_32 / kernel_scaled_matern_12 "
+        raise TypeError("the kernel must come from kernel_scaled_rbf / kernel_scaled_matern_52 / kernel_scaled_matern_32 / kernel_scaled_matern_12 "
                         "(the native Gram operator evaluates it on the device)")
     if not hasattr(constrain, "minval"):
         raise TypeError("constrain must come from constraint_greater_than")

@@ -46,9 +46,10 @@ enum { MFX_RBF_FP32 = 0, MFX_RBF_F16X3_MATVEC = 1, MFX_RBF_F16X3 = 2 };
  *   MFX_KERNEL_RBF       sigma exp(-s/2)                                   kernel_scaled_rbf        :151-184
  *   MFX_KERNEL_MATERN12  sigma exp(-r),          r = sqrt(s + eps)         kernel_scaled_matern_12  :110-148
  *   MFX_KERNEL_MATERN32  sigma (1 + r) exp(-r),  r = sqrt(3 s + eps)       kernel_scaled_matern_32  :69-107
+ *   MFX_KERNEL_MATERN52  sigma (1 + r + r^2/3) exp(-r), r = sqrt(5 s + eps) kernel_scaled_matern_52  (not in the reference)
  * eps = machine epsilon of the dtype (util/gp_util.py:99,140).  The distance of a point to itself is taken as
  * exactly 0 (the reference's expanded form leaves round-off there, which sqrt amplifies to 3e-4 in fp32). */
-enum { MFX_KERNEL_RBF = 0, MFX_KERNEL_MATERN12 = 1, MFX_KERNEL_MATERN32 = 2 };
+enum { MFX_KERNEL_RBF = 0, MFX_KERNEL_MATERN12 = 1, MFX_KERNEL_MATERN32 = 2, MFX_KERNEL_MATERN52 = 3 };
 enum {
   MFX_OK = 0,
   MFX_ERR_INVALID = -1,     /* bad argument (shape, null pointer, depth out of range) */
@@ -106,7 +107,7 @@ typedef struct mfx_operator {
   int32_t d;
   int32_t ard;
   int32_t rbf_mode;  /* MFX_RBF_* arithmetic of the fp32 Gram kernels (ignored for fp64) */
-  int32_t kernel_fn; /* MFX_KERNEL_*: which stationary kernel the Gram operator evaluates */
+  int32_t kernel_fn; /* MFX_KERNEL_*: which stationary kernel the Gram operator evaluates; any other value is MFX_ERR_INVALID */
   const void* lengthscale;
   const void* outputscale;
   const void* noise;

@@ -46,7 +46,7 @@ def c1():
         print(f"C1 dense 512x512 k=20 p=1 {dt}: value {fwd:.3f} ms, value+grad {both:.3f} ms")
 
 
-def c2():
+def c2(kernel="rbf"):
     # BASELINE config 2 on its own data: all 45 730 rows of the UCI protein set, z-scored (tests/golden/uci_protein_X.npz)
     k, p = 30, 8
     X = torch.tensor(np.load(os.path.join(ROOT, "tests", "golden", "uci_protein_X.npz"))["X"], dtype=torch.float32, device=dev)
@@ -54,10 +54,10 @@ def c2():
     probes = torch.tensor(orc.rademacher(2, p, n), dtype=torch.float32, device=dev)
     for tag, shape in (("ARD", (d,)), ("scalar lengthscale", ())):
         params = [torch.zeros(shape if i == 0 else (), dtype=torch.float32, device=dev, requires_grad=True) for i in range(3)]
-        f = lanczos.integrand_spd(torch.log, k, gp_util.gram_operator(X, noise_minval=1e-4))
+        f = lanczos.integrand_spd(torch.log, k, gp_util.gram_operator(X, noise_minval=1e-4, kernel=kernel))
         fwd = timeit(lambda: f(probes, *params), reps=3, warm=1)
         both = timeit(lambda: torch.autograd.grad(f(probes, *params).sum(), params), reps=3, warm=1)
-        print(f"C2 UCI protein RBF N={n} d={d} {tag} k={k} p={p} fp32: value {fwd:.2f} ms, value+grad {both:.2f} ms")
+        print(f"C2 UCI protein {kernel} N={n} d={d} {tag} k={k} p={p} fp32: value {fwd:.2f} ms, value+grad {both:.2f} ms")
 
 
 def c3():
@@ -113,4 +113,5 @@ if __name__ == "__main__":
     import sys
 
     for name in (sys.argv[1:] or ["c1", "c2", "c3", "c5"]):
-        globals()[name]()
+        name, _, arg = name.partition(":")  # c2:matern52 runs config 2 with that kernel family
+        globals()[name](*([arg] if arg else []))

@@ -8,7 +8,7 @@ dev = torch.device("cuda:0")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 131072
 for d in (3, 8):
     X = torch.rand(n, d, device=dev) * 2 - 1
-    for kernel in ("rbf", "matern32"):
+    for kernel in ("rbf", "matern32", "matern52"):
         op = RbfGramOp(X, noise_minval=1e-4, kernel=kernel)
         params = [torch.zeros((), device=dev) for _ in range(3)]
         for p in (1, 2, 4, 8, 16, 32, 64):

@@ -1,4 +1,4 @@
-"""Gram matvec at GP-training sizes (n = 36584, d = 9, Matern-3/2 / RBF): ms per matvec vs right-hand sides."""
+"""Gram matvec at GP-training sizes (n = 36584, d = 9, Matern-3/2 and 5/2): ms per matvec vs right-hand sides."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "experiments-lanczos-adjoints_amd"))
 import torch
@@ -6,7 +6,7 @@ from matfree_extensions.operators import RbfGramOp
 dev = torch.device("cuda:0")
 for n in (9000, 16384, 36584, 65536):
     X = torch.randn(n, 9, device=dev)
-    for kernel in ("matern32",):
+    for kernel in ("matern32", "matern52"):
         op = RbfGramOp(X, noise_minval=1e-4, kernel=kernel)
         params = [torch.zeros(9, device=dev), torch.zeros((), device=dev), torch.zeros((), device=dev)]
         for p in (1, 10, 64):
