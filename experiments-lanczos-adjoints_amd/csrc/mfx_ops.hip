@@ -1966,3 +1966,223 @@ int op_vjp_params(const mfx_operator* op, const void* L, int64_t ldl, const void
 }
 
 }  // namespace mfx
+
+// ================================================================================================
+// Dense Gram block: out[a][b] = s kappa(|xa_a / l - xb_b / l|^2) written to memory (mfx_gram_block)
+//
+// A workgroup owns a 64 x 64 tile of the block.  The 64 points of xb (scaled, with their squared norms) are staged once in LDS;
+// a thread keeps ONE scaled point of xa in registers (lane = row of the tile) and evaluates the 16 columns of its wave against it
+// -- the LDS reads of a column are wave-uniform, so they broadcast.  The 64 x 64 results go through an LDS tile with a padded
+// row (65: the column writes and the row reads are both conflict-free) so that every store instruction of a wave covers 64
+// consecutive entries of one output row.  The arithmetic is k_rbf_apply's, in its order: dot product over c, |a|^2 + |b|^2 - 2 a.b,
+// clamp at 0, kernel_eval.  Entry (a, b) and entry (b, a) of a symmetric block run the same instructions on the same two numbers
+// per step (products and the sum of the two norms commute), so the block comes out bitwise symmetric without a mirror pass; its
+// diagonal takes the distance 0 itself.  No atomics, no cross-workgroup state: deterministic.
+// ================================================================================================
+namespace mfx {
+
+constexpr int kBlkT = 64;  // tile edge
+constexpr int kBlkC = 16;  // columns per thread = kBlkT / 4 waves
+
+// tile[row][col] -> out, a wave per row at a time (256-thread workgroup: rows w, w + 4, ...)
+template <typename T>
+__device__ __forceinline__ void gram_block_store(const T (*tile)[kBlkT + 1], int64_t a0, int64_t ma, int64_t b0, int64_t mb,
+                                                 T* __restrict__ out, int64_t ldo) {
+  const int col = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t b = b0 + col;
+  if (b >= mb) return;
+#pragma unroll 4
+  for (int row = w; row < kBlkT; row += 4) {
+    const int64_t a = a0 + row;
+    if (a < ma) out[a * ldo + b] = tile[row][col];
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ T gram_block_value(int kind, T s, T sqi, T sqj, T dot, bool diag) {
+  T dist = sqi + sqj - T(2) * dot;
+  dist = dist > T(0) ? dist : T(0);
+  if (diag) dist = T(0);  // a point against itself: exactly 0, as the Gram operator takes it
+  T kv, wl;
+  kernel_eval<T>(kind, dist, kv, wl);
+  return s * kv;
+}
+
+template <typename T, int DPAD>
+__global__ __launch_bounds__(256) void k_gram_block(const T* __restrict__ xa, const T* __restrict__ sqa, int64_t ma,
+                                                    const T* __restrict__ xb, const T* __restrict__ sqb, int64_t mb,
+                                                    const T* __restrict__ outputscale, int kind, int sym, T* __restrict__ out,
+                                                    int64_t ldo) {
+  __shared__ __attribute__((aligned(16))) T xj[kBlkT][DPAD];
+  __shared__ T sqj[kBlkT];
+  __shared__ T tile[kBlkT][kBlkT + 1];
+  const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
+  const int64_t a0 = (int64_t)blockIdx.y * kBlkT, b0 = (int64_t)blockIdx.x * kBlkT;
+  for (int t = tid; t < kBlkT * DPAD; t += 256) {
+    const int64_t g = b0 * DPAD + t;
+    (&xj[0][0])[t] = g < mb * DPAD ? xb[g] : T(0);
+  }
+  if (tid < kBlkT) sqj[tid] = (b0 + tid < mb) ? sqb[b0 + tid] : T(0);
+  const int64_t a = a0 + r;
+  const int64_t ac = a < ma ? a : ma - 1;
+  T xi[DPAD];
+#pragma unroll
+  for (int c = 0; c < DPAD; ++c) xi[c] = xa[ac * DPAD + c];
+  const T sqi = sqa[ac];
+  const T s = outputscale[0];
+  __syncthreads();
+#pragma unroll 4
+  for (int jj = 0; jj < kBlkC; ++jj) {
+    const int col = w * kBlkC + jj;
+    T dot = T(0);
+#pragma unroll
+    for (int c = 0; c < DPAD; ++c) dot += xi[c] * xj[col][c];
+    tile[r][col] = gram_block_value<T>(kind, s, sqi, sqj[col], dot, sym && a == b0 + col);
+  }
+  __syncthreads();
+  gram_block_store<T>(tile, a0, ma, b0, mb, out, ldo);
+}
+
+// d > 32: the d axis in chunks of Wide<T>::CH staged transposed through LDS for both point sets ([c][point], the row padded by
+// one so that the staging writes -- c fastest, as the global reads -- spread over the banks); 16 running dot products per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void k_gram_block_wide(const T* __restrict__ xa, const T* __restrict__ sqa, int64_t ma,
+                                                         const T* __restrict__ xb, const T* __restrict__ sqb, int64_t mb, int dpad,
+                                                         const T* __restrict__ outputscale, int kind, int sym,
+                                                         T* __restrict__ out, int64_t ldo) {
+  constexpr int CH = Wide<T>::CH;
+  __shared__ T xaT[CH][kBlkT + 1];
+  __shared__ T xbT[CH][kBlkT + 1];
+  __shared__ T sqj[kBlkT];
+  __shared__ T tile[kBlkT][kBlkT + 1];
+  const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
+  const int64_t a0 = (int64_t)blockIdx.y * kBlkT, b0 = (int64_t)blockIdx.x * kBlkT;
+  if (tid < kBlkT) sqj[tid] = (b0 + tid < mb) ? sqb[b0 + tid] : T(0);
+  const int64_t a = a0 + r;
+  const T sqi = sqa[a < ma ? a : ma - 1];
+  const T s = outputscale[0];
+  T dot[kBlkC];
+#pragma unroll
+  for (int jj = 0; jj < kBlkC; ++jj) dot[jj] = T(0);
+  for (int c0 = 0; c0 < dpad; c0 += CH) {
+    __syncthreads();  // the previous chunk is read no more
+    for (int t = tid; t < kBlkT * CH; t += 256) {
+      const int pt = t / CH, c = t % CH;
+      xaT[c][pt] = (a0 + pt < ma) ? xa[(a0 + pt) * dpad + c0 + c] : T(0);
+      xbT[c][pt] = (b0 + pt < mb) ? xb[(b0 + pt) * dpad + c0 + c] : T(0);
+    }
+    __syncthreads();  // (publishes sqj too)
+#pragma unroll 2
+    for (int c = 0; c < CH; ++c) {
+      const T xic = xaT[c][r];
+#pragma unroll
+      for (int jj = 0; jj < kBlkC; ++jj) dot[jj] += xic * xbT[c][w * kBlkC + jj];
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < kBlkC; ++jj) {
+    const int col = w * kBlkC + jj;
+    tile[r][col] = gram_block_value<T>(kind, s, sqi, sqj[col], dot[jj], sym && a == b0 + col);
+  }
+  __syncthreads();
+  gram_block_store<T>(tile, a0, ma, b0, mb, out, ldo);
+}
+
+// workspace: the scaled, zero-padded copies of xa and xb and their squared norms (the carve of the cross-covariance matvec for
+// its X_new, once per point set; the symmetric block leaves the second pair unused)
+struct BlockWs {
+  void *xa, *sqa, *xb, *sqb;
+};
+static int64_t gram_block_carve(const mfx_operator* op, int64_t ma, int64_t mb, void* ws, int64_t ws_bytes, BlockWs* out) {
+  const int64_t es = (int64_t)dtype_size(op->dtype);
+  const int64_t dpad = rbf_dpad(op->d) > 0 ? rbf_dpad(op->d) : 1;
+  Carver cv(ws, ws_bytes);
+  BlockWs b;
+  b.xa = cv.take(ma * dpad * es);
+  b.sqa = cv.take(ma * es);
+  b.xb = cv.take(mb * dpad * es);
+  b.sqb = cv.take(mb * es);
+  if (out) *out = b;
+  return cv.off;
+}
+
+template <typename T>
+static int gram_block_t(const mfx_operator* op, const T* xa, int64_t ma, const T* xb, int64_t mb, T* out, int64_t ldo,
+                        const BlockWs& w, hipStream_t stream) {
+  const int dpad = rbf_dpad(op->d);
+  const T* ls = (const T*)op->lengthscale;
+  const int sym = xb == nullptr;
+  T *xar = (T*)w.xa, *sqar = (T*)w.sqa;
+  k_rbf_prep<T><<<(unsigned)((ma + 255) / 256), 256, 0, stream>>>(xa, ma, op->d, dpad, ls, op->ard, xar, sqar);
+  MFX_CHECK_LAUNCH();
+  const T *xbr = xar, *sqbr = sqar;
+  if (!sym) {
+    k_rbf_prep<T><<<(unsigned)((mb + 255) / 256), 256, 0, stream>>>(xb, mb, op->d, dpad, ls, op->ard, (T*)w.xb, (T*)w.sqb);
+    MFX_CHECK_LAUNCH();
+    xbr = (const T*)w.xb;
+    sqbr = (const T*)w.sqb;
+  }
+  const dim3 grid((unsigned)((mb + kBlkT - 1) / kBlkT), (unsigned)((ma + kBlkT - 1) / kBlkT));
+  const T* s = (const T*)op->outputscale;
+#define MFX_GRAM_BLOCK(D) \
+  k_gram_block<T, D><<<grid, 256, 0, stream>>>(xar, sqar, ma, xbr, sqbr, mb, s, op->kernel_fn, sym, out, ldo)
+  switch (dpad) {
+    case 4: MFX_GRAM_BLOCK(4); break;
+    case 8: MFX_GRAM_BLOCK(8); break;
+    case 12: MFX_GRAM_BLOCK(12); break;
+    case 16: MFX_GRAM_BLOCK(16); break;
+    case 32: MFX_GRAM_BLOCK(32); break;
+    default:
+      k_gram_block_wide<T><<<grid, 256, 0, stream>>>(xar, sqar, ma, xbr, sqbr, mb, dpad, s, op->kernel_fn, sym, out, ldo);
+      break;
+  }
+#undef MFX_GRAM_BLOCK
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+// every refusal of mfx_gram_block, before any launch (op->x and op->noise are not looked at: the block has no noise term and its
+// point sets are arguments)
+static int check_gram_block(const mfx_operator* op, const void* xa, int64_t ma, const void* xb, int64_t mb, const void* out,
+                            int64_t ldo) {
+  MFX_REQUIRE(op && xa && out, MFX_ERR_INVALID, "mfx_gram_block: null argument");
+  MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_UNSUPPORTED, "mfx_gram_block needs a kernel-Gram operator");
+  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "mfx_gram_block needs the whole operator (no row block)");
+  MFX_REQUIRE(op->lengthscale && op->outputscale, MFX_ERR_INVALID, "mfx_gram_block: RBF operator with null pointers");
+  MFX_REQUIRE(ma >= 1 && mb >= 1 && ldo >= mb, MFX_ERR_INVALID, "mfx_gram_block: bad sizes (ma %lld, mb %lld, ldo %lld)",
+              (long long)ma, (long long)mb, (long long)ldo);
+  MFX_REQUIRE(xb || mb == ma, MFX_ERR_INVALID, "mfx_gram_block: the symmetric block (xb == NULL) needs mb == ma (%lld != %lld)",
+              (long long)mb, (long long)ma);
+  MFX_CHECK_KERNEL_FN(op);
+  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "unsupported dtype %d", op->dtype);
+  MFX_REQUIRE(op->d >= 1, MFX_ERR_INVALID, "mfx_gram_block: d must be >= 1 (got %d)", op->d);
+  MFX_REQUIRE(rbf_dpad(op->d) > 0, MFX_ERR_UNSUPPORTED, "RBF operator supports d <= 1024 (got %d)", op->d);
+  MFX_REQUIRE((ma + kBlkT - 1) / kBlkT <= 65535 && (mb + kBlkT - 1) / kBlkT <= 2147483647LL, MFX_ERR_UNSUPPORTED,
+              "mfx_gram_block: at most %d rows per call", 65535 * kBlkT);
+  return MFX_OK;
+}
+
+}  // namespace mfx
+
+using namespace mfx;
+
+extern "C" {
+
+int64_t mfx_gram_block_workspace_bytes(const mfx_operator* op, int64_t ma, int64_t mb) {
+  if (!op || op->kind != MFX_OP_RBF || ma <= 0 || mb <= 0) return -1;
+  return gram_block_carve(op, ma, mb, nullptr, 0, nullptr) + 256;
+}
+
+int mfx_gram_block(const mfx_operator* op, const void* xa, int64_t ma, const void* xb, int64_t mb, void* out, int64_t ldo,
+                   void* ws, int64_t ws_bytes, void* stream) {
+  MFX_TRY(check_gram_block(op, xa, ma, xb, mb, out, ldo));
+  BlockWs w;
+  MFX_REQUIRE(ws && gram_block_carve(op, ma, mb, ws, ws_bytes, &w) <= ws_bytes, MFX_ERR_WORKSPACE,
+              "mfx_gram_block: workspace too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ScopedTimer t(0, s);
+  if (op->dtype == MFX_F32) return gram_block_t<float>(op, (const float*)xa, ma, (const float*)xb, mb, (float*)out, ldo, w, s);
+  return gram_block_t<double>(op, (const double*)xa, ma, (const double*)xb, mb, (double*)out, ldo, w, s);
+}
+
+}  // extern "C"

@@ -167,6 +167,8 @@ SYMBOLS = {
     "mfx_gram_cross_vjp": (_I, [_OPP, _P, _I64, _P, _I64, _P, _I64, _I64, _GRP, _P, _P, _I64, _P]),
     "mfx_gram_cross_vjp_dense_workspace_bytes": (_I64, [_OPP, _I64]),
     "mfx_gram_cross_vjp_dense": (_I, [_OPP, _P, _I64, _P, _I64, _GRP, _P, _P, _I64, _P]),
+    "mfx_gram_block_workspace_bytes": (_I64, [_OPP, _I64, _I64]),
+    "mfx_gram_block": (_I, [_OPP, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "mfx_timing_enable": (_I, [_I]),
     "mfx_timing_reset": (_I, []),
     "mfx_timing_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -120,6 +120,10 @@ class RowShardedOp:
         raise NotImplementedError("the predictive variance is not available on row-sharded operators (it needs K(X, xs) and the "
                                   "solves on the whole operator); use the operator itself")
 
+    def posterior_covariance(self, *args, **kwargs):
+        raise NotImplementedError("the predictive covariance is not available on row-sharded operators (it needs K(X, xs) and the "
+                                  "solves on the whole operator); use the operator itself")
+
     def __call__(self, v, *params):
         """this rank's rows of A v from the row shard of v (gathers v first; not differentiable -- the Krylov drivers
         use the fused device path instead)"""
@@ -329,6 +333,145 @@ class _PosteriorVarFn(torch.autograd.Function):
         return (None, None, None, None, None, gxs, gls, gs, gn, *((gx,) if len(cparams) > 3 else ()))
 
 
+def _gram_block(op, cparams, xa, xb, out=None):
+    """K(xa, xb) (ma, mb) through mfx_gram_block, outside autograd; xb None: the symmetric block K(xa, xa).  ``out``: a contiguous
+    (ma, mb) tensor to fill (a row slice of a larger matrix)."""
+    lib, dev = _lib.get(), xa.device
+    ma, mb = xa.shape[0], (xa if xb is None else xb).shape[0]
+    desc = op.descriptor(cparams, xa.dtype, op.n)
+    if out is None:
+        out = torch.empty((ma, mb), dtype=xa.dtype, device=dev)
+    ws = _lib.scratch(int(lib.mfx_gram_block_workspace_bytes(C.byref(desc), ma, mb)), dev)
+    _lib.check(lib.mfx_gram_block(C.byref(desc), _lib.ptr(xa), ma, _lib.ptr(xb), mb, _lib.ptr(out), mb, _lib.ptr(ws), ws.numel(),
+                                  _lib.stream_ptr(dev)))
+    return out
+
+
+def _gram_block_vjp(op, cparams, xa, pts, S, gxa, gpts, gls, gs):
+    """accumulates the gradients of sum_ab S_ab k(xa_a, pts_b) into the tensors that are not None: mfx_gram_cross_vjp_dense on a
+    descriptor whose x / n are pts / len(pts) (xa takes the X_new slot).  S (ma, len(pts)) contiguous."""
+    lib, dev = _lib.get(), xa.device
+    ma, mb = S.shape
+    desc = op.descriptor(cparams, xa.dtype, mb)
+    desc.x, desc.n = pts.data_ptr(), mb
+    st = _lib.OpGrads()
+    st.lengthscale, st.outputscale, st.x = (None if t is None else t.data_ptr() for t in (gls, gs, gpts))
+    ws = _lib.scratch(int(lib.mfx_gram_cross_vjp_dense_workspace_bytes(C.byref(desc), ma)), dev)
+    _lib.check(lib.mfx_gram_cross_vjp_dense(C.byref(desc), _lib.ptr(xa), ma, _lib.ptr(S), mb, C.byref(st), _lib.ptr(gxa),
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+
+
+def _symmetric_block_vjp(op, cparams, xa, S, gxa, gls, gs):
+    """the same for the symmetric block K(xa, xa): both slots of every off-diagonal pair; the diagonal is the constant s kappa(0) of
+    the forward (distance exactly 0), so it reaches the outputscale only"""
+    off = S.clone()
+    off.diagonal().zero_()
+    gpts = torch.zeros_like(gxa) if gxa is not None else None
+    _gram_block_vjp(op, cparams, xa, xa, off, gxa, gpts, gls, gs)
+    if gxa is not None:
+        gxa += gpts
+    if gs is not None:
+        gs += _kappa0(op.kernel, xa.dtype) * S.diagonal().sum()
+
+
+class _GramBlockFn(torch.autograd.Function):
+    """K(xa, xb) (mfx_gram_block; xb None: K(xa, xa)); backward = one mfx_gram_cross_vjp_dense call with the cotangent as the dense
+    weights, on a descriptor over xb -- each gradient computed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, op, xa, xb, *cparams):
+        _lib.require_device(xa, xb, *cparams)
+        xa = xa.contiguous()
+        xb = None if xb is None else xb.contiguous()
+        out = _gram_block(op, cparams, xa, xb)
+        ctx.op, ctx.symmetric = op, xb is None
+        ctx.save_for_backward(xa, *(() if xb is None else (xb,)), *cparams)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        saved = ctx.saved_tensors
+        xa, xb, cparams = (saved[0], None, saved[1:]) if ctx.symmetric else (saved[0], saved[1], saved[2:])
+        need = ctx.needs_input_grad  # (op, xa, xb, lengthscale, outputscale, noise[, X])
+        gxa = gxb = gls = gs = None
+        if need[1] or need[2] or need[3] or need[4]:
+            S = dy.contiguous()
+            gxa = torch.zeros_like(xa) if need[1] else None
+            gls = torch.zeros_like(cparams[0]) if need[3] else None
+            gs = torch.zeros_like(cparams[1]) if need[4] else None
+            if ctx.symmetric:
+                _symmetric_block_vjp(ctx.op, cparams, xa, S, gxa, gls, gs)
+            else:
+                gxb = torch.zeros_like(xb) if need[2] else None
+                _gram_block_vjp(ctx.op, cparams, xa, xb, S, gxa, gxb, gls, gs)
+        return (None, gxa, gxb, gls, gs, None, *((None,) if len(cparams) > 3 else ()))
+
+
+class _PosteriorCovFn(torch.autograd.Function):
+    """Sigma = K(xs, xs) - B A^-1 B^T with B = K(xs, X), A = K + noise I.  Forward: per chunk of test points B_c = mfx_gram_block(xs_c, X)
+    and W_c = solve(A, B_c) without grad; then Kss = the symmetric block of xs and Sigma = Kss - (B W^T + W B^T) / 2 (two torch
+    products; the symmetrised form is bitwise symmetric whatever the solver left in W).
+    Backward, with W = B A^-1 kept from the forward and C = (Sbar + Sbar^T) / 2 (Sigma is symmetric in its arguments, so only the
+    symmetric part of the cotangent acts):
+      d Sigma = dKss - dB W^T - W dB^T + W dA W^T
+      <Sbar, dKss>       = <C, dKss>           the dense sweep with the weights C on the operator over xs (both slots)
+      -<Sbar, dB W^T + W dB^T> = <-2 C W, dB>  mfx_gram_cross_vjp_dense with S = -2 C W
+      <Sbar, W dA W^T>   = sum_a (C W)_a^T dA w_a   mfx_op_vjp_params with L = C W, R = W, batch m
+    -- no adjoint solve, and each sweep only for the gradients asked for."""
+
+    @staticmethod
+    def forward(ctx, op, bound, solve, chunk, info, xs, *cparams):
+        _lib.require_device(xs, *cparams)
+        xs = xs.contiguous()
+        (m, _), n, dt, dev = xs.shape, op.n, xs.dtype, xs.device
+        X = op.X.detach()
+        B = torch.empty((m, n), dtype=dt, device=dev)
+        W = torch.empty((m, n), dtype=dt, device=dev)
+        parts = []
+        for a0 in range(0, m, chunk):
+            c = min(chunk, m - a0)
+            _gram_block(op, cparams, xs[a0 : a0 + c], X, out=B[a0 : a0 + c])
+            W[a0 : a0 + c], sinfo = solve(bound, B[a0 : a0 + c])
+            parts.append(sinfo)
+        info["solve"] = _cat_info(parts)
+        P = B @ W.T
+        cov = _gram_block(op, cparams, xs, None) - 0.5 * (P + P.T)
+        ctx.op = op
+        ctx.save_for_backward(xs, W, *cparams)
+        return cov
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, sbar):
+        xs, W, *cparams = ctx.saved_tensors
+        op, lib = ctx.op, _lib.get()
+        need = ctx.needs_input_grad  # (op, bound, solve, chunk, info, xs, lengthscale, outputscale, noise[, X])
+        want_x = len(need) > 9 and need[9]
+        (m, n), dev = W.shape, W.device
+        gxs = torch.zeros_like(xs) if need[5] else None
+        gls = torch.zeros_like(cparams[0]) if need[6] else None
+        gs = torch.zeros_like(cparams[1]) if need[7] else None
+        gn = torch.zeros_like(cparams[2]) if need[8] else None
+        gx = torch.zeros_like(cparams[3], memory_format=torch.contiguous_format) if want_x else None
+        if not (need[5] or need[6] or need[7] or need[8] or want_x):
+            return (None,) * (6 + len(cparams))
+        Cs = 0.5 * (sbar + sbar.T)
+        CW = Cs @ W
+        if need[5] or need[6] or need[7]:  # <C, dKss>
+            _symmetric_block_vjp(op, cparams, xs, Cs, gxs, gls, gs)
+        if need[5] or need[6] or need[7] or want_x:  # <-2 C W, dB>
+            _gram_block_vjp(op, cparams, xs, op.X.detach(), CW * -2.0, gxs, gx, gls, gs)
+        if need[6] or need[7] or need[8] or want_x:  # sum_a (C W)_a^T dA w_a
+            desc = op.descriptor(cparams, W.dtype, n)
+            st = _lib.OpGrads()
+            st.lengthscale, st.outputscale, st.noise, st.x = (None if t is None else t.data_ptr() for t in (gls, gs, gn, gx))
+            ws = _lib.workspace(desc, n, 1, m, dev)
+            _lib.check(lib.mfx_op_vjp_params(C.byref(desc), _lib.ptr(CW), n, _lib.ptr(W), n, m, C.byref(st), _lib.ptr(ws), ws.numel(),
+                                             _lib.stream_ptr(dev)))
+        return (None, None, None, None, None, gxs, gls, gs, gn, *((gx,) if len(cparams) > 3 else ()))
+
+
 class DenseOp(NativeOp):
     """matvec(v, A) = A @ v."""
 
@@ -506,6 +649,42 @@ class RbfGramOp(NativeOp):
         info = {}
         var = _PosteriorVarFn.apply(self, self.bind(*params), solve, chunk, info, xs.to(self.X.dtype), *cparams)
         return (var, info) if return_info else var
+
+    def _check_points(self, what, x):
+        if x.dim() != 2 or x.shape[1] != self.d or x.shape[0] < 1:
+            raise ValueError(f"{what} {tuple(x.shape)} must be (m >= 1, {self.d})")
+
+    def gram_block(self, xa, xb, *params):
+        """The dense block K(xa, xb) of the prior kernel matrix, (ma, mb), written by mfx_gram_block: no noise term, the Gram
+        operator's conventions (inputs over the lengthscale, distance clamped at 0, eps inside Matern's square root).  xb=None:
+        the symmetric block K(xa, xa), bitwise symmetric, its diagonal s kappa(0) exactly.  Uses the operator's kernel, dtype and d
+        only -- not its X: pass ``op.X`` as xb for K(xa, X) (the gradient then reaches X through that argument).  Differentiable
+        with respect to xa, xb, the lengthscale and outputscale parameters; the noise gets no gradient."""
+        self._check_points("gram_block: xa", xa)
+        if xb is not None:
+            self._check_points("gram_block: xb", xb)
+            xb = xb.to(self.X.dtype)
+        cparams = self.constrain(*params)
+        return _GramBlockFn.apply(self, xa.to(self.X.dtype), xb, *cparams)
+
+    def posterior_covariance(self, xs, solve, *params, chunk=64, return_info=False):
+        """The joint latent predictive covariance K(xs, xs) - K(xs, X) A^-1 K(X, xs), A = K(X, X) + noise I, of the test points xs
+        (m, d) -> (m, m), bitwise symmetric; its diagonal is posterior_variance.  Not clamped or jittered: rounding can leave it
+        slightly indefinite (gp_util.posterior_samples takes a jitter).
+
+        solve(A, B) -> (W, info) as in posterior_variance, without grad on batches of at most ``chunk`` right-hand sides
+        B = K(xs_c, X), which mfx_gram_block writes directly.  Differentiable with respect to xs, the three parameters and X (when
+        X.requires_grad) without another solve.  Memory: B and W are (m, n) each and the result (m, m), in X's dtype; W is kept
+        for the backward, which holds one more (m, n) product (1024 test points against 131 072 training points in fp32: 512 MiB
+        each).  return_info=True returns (covariance, info) with info["solve"] as posterior_variance lays it out."""
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"posterior_covariance: chunk must be >= 1, got {chunk}")
+        self._check_points("posterior_covariance: xs", xs)
+        cparams = self.constrain(*params)
+        info = {}
+        cov = _PosteriorCovFn.apply(self, self.bind(*params), solve, chunk, info, xs.to(self.X.dtype), *cparams)
+        return (cov, info) if return_info else cov
 
     def new_grads(self, ls, s, nz, X=None):
         g = (torch.zeros_like(ls), torch.zeros_like(s), torch.zeros_like(nz))

@@ -439,3 +439,80 @@ def likelihood_condition_var_p(matvec, solve_p, *, precondition, constrain, obse
         return condition_partial
 
     return likelihood, {"raw_noise": torch.empty(())}
+
+
+def _predictive_covariance(cov_matvec, solve, xs, noise, observation_noise, chunk):
+    """the joint predictive covariance of likelihood_condition_cov[_p] and its info"""
+    cov, info = cov_matvec.op.posterior_covariance(xs, solve, *cov_matvec.params, chunk=chunk, return_info=True)
+    if observation_noise:
+        cov = cov + torch.diag_embed(noise.to(cov.dtype).reshape(1).expand(cov.shape[0]))
+    return cov, {"covariance_solve": info["solve"]}
+
+
+def likelihood_condition_cov(matvec, solve, *, constrain, observation_noise=False, chunk=64):
+    """likelihood_condition with the joint predictive covariance: condition(xs, targets) -> ((mean, covariance), info).
+
+    mean is likelihood_condition's.  covariance = K(xs, xs) - K(xs, X) A^-1 K(X, xs) (RbfGramOp.posterior_covariance, ``chunk``
+    test points per batched solve; (m, m), bitwise symmetric, neither clamped nor jittered), plus the noise on its diagonal when
+    observation_noise (the covariance of noisy observations; the noise then gets its gradient through that term too).
+    info = {"solve": the mean's solve info, "covariance_solve": the solver's info per test point}.  Draws: posterior_samples."""
+    chunk = _check_chunk(chunk)
+
+    def likelihood(inputs, mean, kernel, params: dict):
+        cov_matvec = _native_cov(matvec, inputs, kernel, constrain, params["raw_noise"])
+        noise = constrain(params["raw_noise"])
+
+        def condition_partial(xs, targets):
+            weights, info = solve(cov_matvec, targets - _mean_array(mean, inputs))
+            mu = _mean_array(mean, xs) + cov_matvec.op.cross_apply(xs, weights, *cov_matvec.params)
+            cov, cinfo = _predictive_covariance(cov_matvec, solve, xs, noise, observation_noise, chunk)
+            return (mu, cov), {"solve": info, **cinfo}
+
+        return condition_partial
+
+    return likelihood, {"raw_noise": torch.empty(())}
+
+
+def likelihood_condition_cov_p(matvec, solve_p, *, precondition, constrain, observation_noise=False, chunk=64):
+    """likelihood_condition_p with the joint predictive covariance, as likelihood_condition_cov (the covariance solves take the
+    same preconditioner as the mean's)."""
+    chunk = _check_chunk(chunk)
+
+    def likelihood(inputs, mean, kernel, params: dict):
+        cov_matvec = _native_cov(matvec, inputs, kernel, constrain, params["raw_noise"])
+        noise = constrain(params["raw_noise"])
+        pre, _info = precondition(low_rank.without_noise(cov_matvec), len(inputs))
+
+        def condition_partial(xs, targets):
+            weights, info = solve_p(cov_matvec, targets - _mean_array(mean, inputs), P=pre.bind(noise))
+            mu = _mean_array(mean, xs) + cov_matvec.op.cross_apply(xs, weights, *cov_matvec.params)
+            cov, cinfo = _predictive_covariance(cov_matvec, lambda A, B: solve_p(A, B, P=pre.bind(noise)), xs, noise,
+                                                observation_noise, chunk)
+            return (mu, cov), {"solve": info, **cinfo}
+
+        return condition_partial
+
+    return likelihood, {"raw_noise": torch.empty(())}
+
+
+def posterior_samples(key, mean, cov, *, num, jitter=0.0):
+    """``num`` draws mean + L eps from N(mean, cov) -> (num, m), with L = cholesky(cov + jitter I) factored in fp64 on the device
+    of ``cov`` and cast back to its dtype, and eps (num, m) standard normal drawn from ``key`` as hutchinson.sampler_normal draws
+    it (the same key gives the same draws; an explicit (num, m) tensor is taken as eps itself).  Plain torch, so differentiable
+    with respect to mean and cov.  A predictive covariance is positive semi-definite only up to rounding and the solver's
+    tolerance: a factorisation that fails raises ValueError -- pass a (larger) ``jitter``."""
+    num = int(num)
+    if num < 1:
+        raise ValueError(f"posterior_samples: num must be >= 1, got {num}")
+    if mean.dim() != 1 or cov.dim() != 2 or cov.shape != (mean.shape[0], mean.shape[0]):
+        raise ValueError(f"posterior_samples: mean {tuple(mean.shape)} and cov {tuple(cov.shape)} must be (m,) and (m, m)")
+    m = mean.shape[0]
+    shifted = cov.double() + float(jitter) * torch.eye(m, dtype=torch.float64, device=cov.device)
+    L, failed = torch.linalg.cholesky_ex(shifted)
+    if int(failed) != 0:
+        raise ValueError(f"posterior_samples: cov + jitter I is not positive definite (jitter = {jitter}; the factorisation stopped "
+                         f"at leading minor {int(failed)}); pass a larger jitter")
+    eps = hutchinson.sampler_normal(mean, num=num)(key)
+    if tuple(eps.shape) != (num, m):
+        raise ValueError(f"posterior_samples: explicit draws {tuple(eps.shape)} must be ({num}, {m})")
+    return mean + eps.to(cov.dtype) @ L.to(cov.dtype).T

@@ -416,6 +416,27 @@ int64_t mfx_gram_cross_vjp_dense_workspace_bytes(const mfx_operator* op, int64_t
 int mfx_gram_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds,
                              const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes, void* stream);
 
+/* A dense block of the kernel matrix written to memory: out[a * ldo + b] = k(xa_a, xb_b) for a < ma, b < mb -- the right-hand
+ * sides K(xs, X) and the prior block K(xs, xs) of the joint GP predictive covariance K(xs, xs) - K(xs, X) A^-1 K(X, xs).
+ *   op supplies the kernel family, dtype, d, ard, lengthscale and outputscale ONLY: there is no noise term, and op->x, op->n and
+ *   op->noise are not read.  xa (ma, d), xb (mb, d) row-major in the operator's dtype; K(xs, X) is xb = op->x, mb = op->n.
+ *   xb == NULL: the symmetric block K(xa, xa) (mb must equal ma).  Its diagonal takes the distance exactly 0, as the Gram operator
+ *   does for a point against itself (value s kappa(0)), and out[a][b] == out[b][a] bitwise.
+ * The formulas of the Gram operator (enum MFX_KERNEL_* above): inputs divided by the lengthscale, |a|^2 + |b|^2 - 2 a.b clamped
+ * at 0, eps of the dtype inside Matern's square root; every family, scalar and ARD lengthscale, fp32 and fp64, d <= 1024.  Entries
+ * of out beyond column mb of a row (ldo > mb) are not touched.  Deterministic (no atomics).  One 64 x 64 tile per workgroup,
+ * stores coalesced along b: the kernel writes ma * mb elements and reads both point sets once per tile row / column.
+ * Workspace: mfx_gram_block_workspace_bytes (the scaled copies and squared norms of both point sets; -1 for a non-Gram operator or
+ * ma, mb < 1).
+ * Refuses before any launch, with mfx_gram_cross_apply's codes: a non-Gram operator or a row block (MFX_ERR_UNSUPPORTED); null op,
+ * xa, out, lengthscale or outputscale, ma < 1, mb < 1, ldo < mb, xb == NULL with mb != ma, an unknown kernel_fn or dtype
+ * (MFX_ERR_INVALID); a short workspace (MFX_ERR_WORKSPACE).
+ * Reverse mode: the gradient of sum_ab S_ab k(xa_a, xb_b) is mfx_gram_cross_vjp_dense on an operator whose x / n are xb / mb, with
+ * xnew = xa (symmetric block: x = xa, and the xa gradient is gxnew + grads->x). */
+int64_t mfx_gram_block_workspace_bytes(const mfx_operator* op, int64_t ma, int64_t mb);
+int mfx_gram_block(const mfx_operator* op, const void* xa, int64_t ma, const void* xb, int64_t mb, void* out, int64_t ldo,
+                   void* ws, int64_t ws_bytes, void* stream);
+
 /* Per-kernel-class device timing with hipEvents recorded on the caller's stream (no host syncs
  * while enabled; events are read back in mfx_timing_read, which synchronises the events).
  * classes: 0 = operator apply, 1 = operator parameter-gradient sweep, 2 = Krylov vector kernels. */
