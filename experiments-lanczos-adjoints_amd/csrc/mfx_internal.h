@@ -84,6 +84,28 @@ constexpr int kEpt = 8;      // elements owned by one thread
 constexpr int kSlice = kBlock * kEpt;  // 2048 elements of one vector per workgroup
 
 inline int64_t num_slices(int64_t n) { return (n + kSlice - 1) / kSlice; }
+
+// ---- probe groups of the Krylov vector passes ---------------------------
+// The consecutive vector kernels between two operator applications (dots -> update -> update; dots -> combine -> update)
+// each sweep the same basis rows.  Launched for all probes at once, every pass streams the whole basis from HBM as soon as
+// it exceeds the Infinity Cache; launched group by group -- the same kernels on g probes at a time, every pass of a group
+// before the next group -- the later passes of a group can be served by the cache.  g = the largest power of two whose
+// rows of ONE pass (g * rows * n elements, twice that in the adjoint, which sweeps the adjoint states beside the basis) fit
+// this budget; g = p (one launch, exactly the ungrouped sequence) when all probes fit.
+// NOT ENABLED: 1 TiB is more than the device holds, so the rule answers p for every problem and the drivers launch exactly the
+// ungrouped sequence.  The Infinity-Cache reuse the grouping counts on has not been measured for this access pattern (DESIGN.md
+// section 3.1 says what the measurement is and what would decide); MFX_PROBE_GROUP=<g> runs any group size for that measurement.
+constexpr int64_t kProbeGroupBudgetBytes = (int64_t)1048576 << 20;
+inline int64_t probe_group_rule(int64_t n, int64_t rows, int64_t p, int64_t elem_size, int adjoint) {
+  if (p <= 1) return 1;
+  const int64_t per_probe = (rows < 1 ? 1 : rows) * n * elem_size * (adjoint ? 2 : 1);
+  if (per_probe <= 0 || p <= kProbeGroupBudgetBytes / per_probe) return p;
+  int64_t g = 1;
+  while (2 * g * per_probe <= kProbeGroupBudgetBytes) g *= 2;
+  return g < p ? g : p;
+}
+// the rule, or what MFX_PROBE_GROUP says (0 = all probes in one launch); read once per process
+int64_t probe_group(int64_t n, int64_t rows, int64_t p, int64_t elem_size, int adjoint);
 inline size_t dtype_size(int dtype) { return dtype == MFX_F64 ? 8 : 4; }
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 

@@ -558,23 +558,30 @@ static int arnoldi_forward_t(const mfx_operator* op, const T* v0, int64_t n, int
   Ctx<T> c(n, S * k, p, pick_vec<T>(n, {v0, Q, r, ws.w}), stream);
   if (comm) c.shard(comm, static_cast<T*>(ws.stage));
   c.fine();
+  // The vector kernels between two operator applications run probe group by probe group (Ctx::for_groups).  Row-sharded: every
+  // one of them ends in an all-reduce over all probes, so no two are adjacent and the sequence stays ungrouped (set_group).
+  c.set_group(probe_group(n, S * k, p, sizeof(T), 0));
   T* P1 = static_cast<T*>(ws.p1);
   T* P2 = static_cast<T*>(ws.p2);
   T* PN = static_cast<T*>(ws.pn);
   const int64_t ldq = S * k * n;
   const int64_t ldh = S * k * k;
-  auto second_slot = [&](int64_t i) -> int {  // slot S i + 1 = i * slot S i
+  auto second_slot = [&](const Ctx<T>& g, int64_t i) -> int {  // slot S i + 1 = i * slot S i
     if (S == 1) return MFX_OK;
-    k_times_i<T><<<dim3((unsigned)((n / 2 + 255) / 256), (unsigned)p), 256, 0, stream>>>(Q + S * i * n, Q + (S * i + 1) * n, ldq, n / 2);
+    k_times_i<T><<<dim3((unsigned)((n / 2 + 255) / 256), (unsigned)g.p), 256, 0, stream>>>(g.at(Q + S * i * n, ldq), g.at(Q + (S * i + 1) * n, ldq),
+                                                                                         ldq, n / 2);
     MFX_CHECK_LAUNCH();
     return MFX_OK;
   };
   MFX_TRY(zero_async(H, sizeof(T) * p * ldh, stream));
   {
     ScopedTimer t(2, stream);
-    MFX_TRY(launch_sumsq<T>(c, v0, n, PN));
-    MFX_TRY(launch_scale<T>(c, v0, n, Q, ldq, PN, nullptr, 0, nullptr, 0, cinv));  // q_0, c = 1/|v|
-    MFX_TRY(second_slot(0));
+    auto start = [&](const Ctx<T>& g) -> int {
+      MFX_TRY(launch_sumsq<T>(g, v0, n, PN));
+      MFX_TRY(launch_scale<T>(g, v0, n, Q, ldq, PN, nullptr, 0, nullptr, 0, cinv));  // q_0, c = 1/|v|
+      return second_slot(g, 0);
+    };
+    MFX_TRY(c.for_groups(start));
   }
   T* w = r;  // the running vector lives in the remainder output (arnoldi.py:75 returns it as r)
   // CSR operator, few slices: normalisation of the previous step, operator application and h = Q^T w in one launch
@@ -604,27 +611,31 @@ static int arnoldi_forward_t(const mfx_operator* op, const T* v0, int64_t n, int
       MFX_TRY(apply_any(op, 0, Q + S * i * n, ldq, nullptr, 0, w, n, p, ws.opws, ws.opws_bytes, stream));
     }
     ScopedTimer t(2, stream);
-    if (!fused) MFX_TRY(launch_dots<T>(c, Q, ldq, n, m, w, n, P1));
-    UpdateArgs<T> a{};
-    a.rows = Q; a.rows_ldb = ldq; a.row_stride = n; a.m = m;
-    a.partial_in = P1; a.s1 = T(1);
-    a.hout = H + i; a.hout_ldb = ldh; a.hout_stride = k;  // H[:, i] (arnoldi.py:99)
-    a.x = w; a.ldx = n; a.y = w; a.ldy = n;
-    a.partial_out = P2; a.partial_norm = PN;
-    if (second_pass) {
-      MFX_TRY(launch_update<T>(c, a, true, false));
-      UpdateArgs<T> a2{};
-      a2.rows = Q; a2.rows_ldb = ldq; a2.row_stride = n; a2.m = m;
-      a2.partial_in = P2; a2.s1 = T(1);  // second-pass coefficients are not added to h (arnoldi.py:92)
-      a2.x = w; a2.ldx = n; a2.y = w; a2.ldy = n; a2.partial_norm = PN;
-      MFX_TRY(launch_update<T>(c, a2, false, true));
-    } else {
-      MFX_TRY(launch_update<T>(c, a, false, true));
-    }
-    if (i + 1 < k && !fused) {  // Q2: H[k][k-1] does not exist; the last vector stays un-normalised in r
-      MFX_TRY(launch_scale<T>(c, w, n, Q + S * (i + 1) * n, ldq, PN, nullptr, 0, H + S * (i + 1) * k + i, ldh, nullptr));
-      MFX_TRY(second_slot(i + 1));
-    }
+    auto orthogonalise = [&](const Ctx<T>& g) -> int {  // every pass over Q[:, :m] of one probe group, then the next group
+      if (!fused) MFX_TRY(launch_dots<T>(g, Q, ldq, n, m, w, n, P1));
+      UpdateArgs<T> a{};
+      a.rows = Q; a.rows_ldb = ldq; a.row_stride = n; a.m = m;
+      a.partial_in = P1; a.s1 = T(1);
+      a.hout = H + i; a.hout_ldb = ldh; a.hout_stride = k;  // H[:, i] (arnoldi.py:99)
+      a.x = w; a.ldx = n; a.y = w; a.ldy = n;
+      a.partial_out = P2; a.partial_norm = PN;
+      if (second_pass) {
+        MFX_TRY(launch_update<T>(g, a, true, false));
+        UpdateArgs<T> a2{};
+        a2.rows = Q; a2.rows_ldb = ldq; a2.row_stride = n; a2.m = m;
+        a2.partial_in = P2; a2.s1 = T(1);  // second-pass coefficients are not added to h (arnoldi.py:92)
+        a2.x = w; a2.ldx = n; a2.y = w; a2.ldy = n; a2.partial_norm = PN;
+        MFX_TRY(launch_update<T>(g, a2, false, true));
+      } else {
+        MFX_TRY(launch_update<T>(g, a, false, true));
+      }
+      if (i + 1 < k && !fused) {  // Q2: H[k][k-1] does not exist; the last vector stays un-normalised in r
+        MFX_TRY(launch_scale<T>(g, w, n, Q + S * (i + 1) * n, ldq, PN, nullptr, 0, H + S * (i + 1) * k + i, ldh, nullptr));
+        MFX_TRY(second_slot(g, i + 1));
+      }
+      return MFX_OK;
+    };
+    MFX_TRY(c.for_groups(orthogonalise));
   }
   return MFX_OK;
 }
@@ -686,6 +697,7 @@ static int arnoldi_adjoint_t(const mfx_operator* op, int64_t n, int64_t k, int64
   Ctx<T> c(n, k, p, pick_vec<T>(n, {Q, r, dQ, dr, dv, Lam, ws.w}), stream);
   if (comm) c.shard(comm, static_cast<T*>(ws.stage));
   c.fine();
+  c.set_group(probe_group(n, k, p, sizeof(T), 1));  // see arnoldi_forward_t; here every pass sweeps Lambda beside Q
   T* P1 = static_cast<T*>(ws.p1);
   T* P2 = static_cast<T*>(ws.p2);
   T* lam = static_cast<T*>(ws.w);  // current lambda (p, n)
@@ -693,51 +705,64 @@ static int arnoldi_adjoint_t(const mfx_operator* op, int64_t n, int64_t k, int64
   T* Gam = static_cast<T*>(ws.small);
   T* pig = Gam + p * k * k;
   T* eta = pig + p * k * k;
-  const int64_t ldq = k * n;
+  const int64_t ldq = k * n, kk = k * k;
+  const int64_t pstride = p * (int64_t)c.kmax * c.nblk;  // one dQ column's partials of ALL probes
   const bool fused = csr_fusable<T>(op, c, 1);
+  // Lambda[:, idx] (arnoldi.py:216, leading dimension ldq) from the running lambda: what the operator of step idx is applied to
+  auto store_lambda = [&](const Ctx<T>& g, int64_t idx) -> int {
+    T* lam_idx = Lam + idx * n;
+    if (reortho == MFX_REORTHO_FULL) {
+      const int m = (int)((idx + 2 < k) ? idx + 2 : k);  // rows of P not yet masked (arnoldi.py:201); their dots are in P1
+      UpdateArgs<T> a{};
+      a.rows = Q; a.rows_ldb = ldq; a.row_stride = n; a.m = m;
+      a.partial_in = P1; a.s1 = T(1);
+      a.extra = dH + idx; a.extra_ldb = k * k; a.extra_stride = k; a.s2 = T(-1);  // - P^T (mask o dH[:, idx])
+      a.x = lam; a.ldx = n; a.y = lam_idx; a.ldy = ldq;
+      return launch_update<T>(g, a, false, false);
+    }
+    return copy_rows_async(g.at(lam_idx, ldq), sizeof(T) * ldq, g.at(lam, n), sizeof(T) * n, sizeof(T) * n, g.p, stream);
+  };
   MFX_TRY(zero_async(Gam, sizeof(T) * p * k * k, stream));
   {
     ScopedTimer t(2, stream);
-    if (dr) MFX_TRY(launch_dots<T>(c, Q, ldq, n, (int)k, dr, n, P1));
-    k_adj_setup<T><<<dim3((unsigned)p, (unsigned)k), 64, 0, stream>>>(H, dH, cinv, dc, dr ? P1 : nullptr, c.kmax, c.nblk_in, (int)k, eta, pig);
-    MFX_CHECK_LAUNCH();
-    if (dQ) {
-      const int64_t cb = ws.pb ? dq_batch_cols(n, k, p, comm) : 1;
-      T* PB = ws.pb ? static_cast<T*>(ws.pb) : P1;
-      const int64_t pstride = p * (int64_t)c.kmax * c.nblk;
-      for (int64_t col = 0; col < k; col += cb) {
-        const int nc = (int)(col + cb <= k ? cb : k - col);
-        MFX_TRY(launch_dots<T>(c, Q, ldq, n, (int)k, dQ + col * n, ldq, PB, nc, n, pstride));
-        k_pig_sub<T><<<dim3((unsigned)p, (unsigned)nc), 512, 0, stream>>>(pig, (int)k, (int)col, PB, c.kmax, c.nblk_in, pstride);  // latency-bound: 8 lanes per coefficient
-        MFX_CHECK_LAUNCH();
+    auto setup = [&](const Ctx<T>& g) -> int {
+      if (dr) MFX_TRY(launch_dots<T>(g, Q, ldq, n, (int)k, dr, n, P1));
+      k_adj_setup<T><<<dim3((unsigned)g.p, (unsigned)k), 64, 0, stream>>>(g.at(H, kk), g.at(dH, kk), g.at(cinv, 1), g.at(dc, 1),
+                                                                        dr ? g.at(P1, (int64_t)c.kmax * c.nblk_in) : nullptr, c.kmax,
+                                                                        c.nblk_in, (int)k, g.at(eta, k), g.at(pig, kk));
+      MFX_CHECK_LAUNCH();
+      if (dQ) {
+        const int64_t cb = ws.pb ? dq_batch_cols(n, k, p, comm) : 1;
+        T* PB = ws.pb ? static_cast<T*>(ws.pb) : P1;
+        for (int64_t col = 0; col < k; col += cb) {
+          const int nc = (int)(col + cb <= k ? cb : k - col);
+          MFX_TRY(launch_dots<T>(g, Q, ldq, n, (int)k, dQ + col * n, ldq, PB, nc, n, pstride));
+          k_pig_sub<T><<<dim3((unsigned)g.p, (unsigned)nc), 512, 0, stream>>>(g.at(pig, kk), (int)k, (int)col,
+                                                                            g.at(PB, (int64_t)c.kmax * c.nblk_in), c.kmax, c.nblk_in,
+                                                                            pstride);  // latency-bound: 8 lanes per coefficient
+          MFX_CHECK_LAUNCH();
+        }
       }
-    }
-    // lambda_k = dr + Q eta  (arnoldi.py:121)
-    UpdateArgs<T> a{};
-    a.rows = Q; a.rows_ldb = ldq; a.row_stride = n; a.m = (int)k;
-    a.extra = eta; a.extra_ldb = k; a.extra_stride = 1; a.s2 = T(-1);
-    a.x = dr; a.ldx = n; a.y = lam; a.ldy = n;
-    // full re-orthogonalisation: whoever produces a lambda also takes its dots with the basis (Q^T lambda, arnoldi.py:204),
-    // the first thing the next step needs -- here for step k - 1 (all k rows), then in the epilogue of k_adj_combine
-    a.partial_out = P1;
-    MFX_TRY(launch_update<T>(c, a, reortho == MFX_REORTHO_FULL, false));
+      // lambda_k = dr + Q eta  (arnoldi.py:121)
+      UpdateArgs<T> a{};
+      a.rows = Q; a.rows_ldb = ldq; a.row_stride = n; a.m = (int)k;
+      a.extra = eta; a.extra_ldb = k; a.extra_stride = 1; a.s2 = T(-1);
+      a.x = dr; a.ldx = n; a.y = lam; a.ldy = n;
+      // full re-orthogonalisation: whoever produces a lambda also takes its dots with the basis (Q^T lambda, arnoldi.py:204),
+      // the first thing the next step needs -- here for step k - 1 (all k rows), then in the epilogue of k_adj_combine
+      a.partial_out = P1;
+      MFX_TRY(launch_update<T>(g, a, reortho == MFX_REORTHO_FULL, false));
+      return store_lambda(g, k - 1);
+    };
+    MFX_TRY(c.for_groups(setup));
   }
   for (int64_t idx = k - 1; idx >= 0; --idx) {
-    T* lam_idx = Lam + idx * n;  // Lambda[:, idx] (arnoldi.py:216), leading dimension ldq
-    {
-      ScopedTimer t(2, stream);
-      if (reortho == MFX_REORTHO_FULL) {
-        const int m = (int)((idx + 2 < k) ? idx + 2 : k);  // rows of P not yet masked (arnoldi.py:201); their dots are in P1
-        UpdateArgs<T> a{};
-        a.rows = Q; a.rows_ldb = ldq; a.row_stride = n; a.m = m;
-        a.partial_in = P1; a.s1 = T(1);
-        a.extra = dH + idx; a.extra_ldb = k * k; a.extra_stride = k; a.s2 = T(-1);  // - P^T (mask o dH[:, idx])
-        a.x = lam; a.ldx = n; a.y = lam_idx; a.ldy = ldq;
-        MFX_TRY(launch_update<T>(c, a, false, false));
-      } else {
-        MFX_TRY(copy_rows_async(lam_idx, sizeof(T) * ldq, lam, sizeof(T) * n, sizeof(T) * n, p, stream));
-      }
-    }
+    T* lam_idx = Lam + idx * n;
+    // Step 0 from here on (operator, dots, combine) produces only the lambda that becomes dv; Lambda[:, 0], the last input of
+    // the parameter sweep, is already stored, and the Gamma / Pi_gamma entries of step 0 are read by no later kernel.  Without
+    // dv it is skipped -- except the application of a callback operator, which accumulates its parameter gradient inside.
+    const bool skip = idx == 0 && !dv;
+    if (skip && op->kind != MFX_OP_CALLBACK) break;
     // z = A^T lambda (+ parameter gradient for callback operators), arnoldi.py:207-209
     if (fused) {  // z = A^T lambda and z^T Q (arnoldi.py:207-212) in one launch
       CsrStepArgs<T> cs{};
@@ -749,21 +774,28 @@ static int arnoldi_adjoint_t(const mfx_operator* op, int64_t n, int64_t k, int64
     } else {
       MFX_TRY(apply_any(op, 1, lam_idx, ldq, Q + idx * n, ldq, z, n, p, ws.opws, ws.opws_bytes, stream));
     }
+    if (skip) break;
     ScopedTimer t(2, stream);
-    if (!fused) MFX_TRY(launch_dots<T>(c, Q, ldq, n, (int)(idx + 1), z, n, P2));
-    CombineArgs<T> ca{Q, Lam, H, pig, eta, r, dQ, z, P2, Gam, lam, n, (int)k, (int)idx, c.kmax, c.nblk_in, nullptr, 0, c.nblk};
-    if (reortho == MFX_REORTHO_FULL && idx > 0) {  // dots of the lambda of step idx - 1: rows min(idx + 1, k)
-      ca.partial_out = c.producer(P1);
-      ca.m_out = (int)((idx + 1 < k) ? idx + 1 : k);
-    }
-    const size_t sh = (size_t)(2 * k + 4 * ca.m_out) * sizeof(T);
-    MFX_REQUIRE(sh <= 64 * 1024, MFX_ERR_UNSUPPORTED, "Krylov depth %lld too large for the adjoint combine kernel (%zu B of LDS > 64 KiB)",
-                (long long)k, sh);
-    MFX_VEC_EPT_SWITCH(c, (k_adj_combine<T, VEC, EPT><<<c.grid(), c.wg, sh, stream>>>(ca)));
-    MFX_CHECK_LAUNCH();
-    if (ca.partial_out) MFX_TRY(c.finish(P1, c.kmax, ca.m_out));
+    auto combine = [&](const Ctx<T>& g) -> int {  // z^T Q, the combine and the next step's Lambda column of one probe group
+      if (!fused) MFX_TRY(launch_dots<T>(g, Q, ldq, n, (int)(idx + 1), z, n, P2));
+      CombineArgs<T> ca{g.at(Q, ldq), g.at(Lam, ldq), g.at(H, kk), g.at(pig, kk), g.at(eta, k), g.at(r, n), g.at(dQ, ldq), g.at(z, n),
+                        g.at(P2, (int64_t)c.kmax * c.nblk_in), g.at(Gam, kk), g.at(lam, n), n, (int)k, (int)idx, c.kmax, c.nblk_in,
+                        nullptr, 0, c.nblk};
+      if (reortho == MFX_REORTHO_FULL && idx > 0) {  // dots of the lambda of step idx - 1: rows min(idx + 1, k)
+        ca.partial_out = g.at(c.producer(P1), (int64_t)c.kmax * c.nblk);
+        ca.m_out = (int)((idx + 1 < k) ? idx + 1 : k);
+      }
+      const size_t sh = (size_t)(2 * k + 4 * ca.m_out) * sizeof(T);
+      MFX_REQUIRE(sh <= 64 * 1024, MFX_ERR_UNSUPPORTED, "Krylov depth %lld too large for the adjoint combine kernel (%zu B of LDS > 64 KiB)",
+                  (long long)k, sh);
+      MFX_VEC_EPT_SWITCH(c, (k_adj_combine<T, VEC, EPT><<<g.grid(), c.wg, sh, stream>>>(ca)));
+      MFX_CHECK_LAUNCH();
+      if (ca.partial_out) MFX_TRY(g.finish(P1, c.kmax, ca.m_out));
+      return idx > 0 ? store_lambda(g, idx - 1) : MFX_OK;
+    };
+    MFX_TRY(c.for_groups(combine));
   }
-  {
+  if (dv) {
     ScopedTimer t(2, stream);
     MFX_TRY(launch_scale<T>(c, lam, n, dv, n, nullptr, cinv, 1, nullptr, 0, nullptr));  // dv = lambda c
   }
@@ -789,6 +821,7 @@ static int lanczos_forward_t(const mfx_operator* op, const T* v0, int64_t n, int
   Ctx<T> c(n, k, p, pick_vec<T>(n, {v0, xs, ws.w}), stream);
   if (comm) c.shard(comm, static_cast<T*>(ws.stage));
   c.fine();
+  c.set_group(probe_group(n, 3, p, sizeof(T), 0));  // a step's passes touch x_{i-1}, x_i and w
   const int64_t prow = comm ? 1 : c.nblk;  // stride of a coefficient row in the partials (sharded: already summed)
   T* P1 = static_cast<T*>(ws.p1);
   T* P2 = static_cast<T*>(ws.p2);
@@ -802,8 +835,11 @@ static int lanczos_forward_t(const mfx_operator* op, const T* v0, int64_t n, int
   MFX_TRY(zero_async(P1, sizeof(T) * p * c.kmax * c.nblk, stream));
   {
     ScopedTimer t(2, stream);
-    MFX_TRY(launch_sumsq<T>(c, v0, n, PN));
-    MFX_TRY(launch_scale<T>(c, v0, n, xs, ldx, PN, nullptr, 0, vnorm, 1, nullptr));
+    auto start = [&](const Ctx<T>& g) -> int {
+      MFX_TRY(launch_sumsq<T>(g, v0, n, PN));
+      return launch_scale<T>(g, v0, n, xs, ldx, PN, nullptr, 0, vnorm, 1, nullptr);
+    };
+    MFX_TRY(c.for_groups(start));
   }
   // CSR operator, few slices: x_i = w / |w|, b_{i-1} = |w|, A x_i and a = x_i . A x_i in one launch (k_csr_step); w alternates
   // between the two scratch vectors because the un-normalised w of step i - 1 is the input of step i.
@@ -832,15 +868,19 @@ static int lanczos_forward_t(const mfx_operator* op, const T* v0, int64_t n, int
       MFX_TRY(apply_any(op, 0, xs + i * n, ldx, nullptr, 0, w, n, p, ws.opws, ws.opws_bytes, stream));
     }
     ScopedTimer t(2, stream);
-    if (!fused) MFX_TRY(launch_dots<T>(c, xs + i * n, ldx, n, 1, w, n, P + (m - 1) * prow));  // a = x_i . A x_i
-    UpdateArgs<T> a{};
-    a.rows = xs + (i == 0 ? 0 : (i - 1) * n); a.rows_ldb = ldx; a.row_stride = n; a.m = m;
-    a.partial_in = P; a.s1 = T(1);
-    if (i > 0) { a.extra = beta + (i - 1); a.extra_ldb = k; a.extra_stride = 1; a.s2 = T(1); }
-    a.hout = alpha + i; a.hout_ldb = k; a.hout_stride = 0; a.hout_from = m - 1;
-    a.x = w; a.ldx = n; a.y = w; a.ldy = n; a.partial_norm = PN;
-    MFX_TRY(launch_update<T>(c, a, false, true));
-    if (!fused || i + 1 == k) MFX_TRY(launch_scale<T>(c, w, n, xs + (i + 1) * n, ldx, PN, nullptr, 0, beta + i, k, nullptr));
+    auto three_term = [&](const Ctx<T>& g) -> int {
+      if (!fused) MFX_TRY(launch_dots<T>(g, xs + i * n, ldx, n, 1, w, n, P + (m - 1) * prow));  // a = x_i . A x_i
+      UpdateArgs<T> a{};
+      a.rows = xs + (i == 0 ? 0 : (i - 1) * n); a.rows_ldb = ldx; a.row_stride = n; a.m = m;
+      a.partial_in = P; a.s1 = T(1);
+      if (i > 0) { a.extra = beta + (i - 1); a.extra_ldb = k; a.extra_stride = 1; a.s2 = T(1); }
+      a.hout = alpha + i; a.hout_ldb = k; a.hout_stride = 0; a.hout_from = m - 1;
+      a.x = w; a.ldx = n; a.y = w; a.ldy = n; a.partial_norm = PN;
+      MFX_TRY(launch_update<T>(g, a, false, true));
+      if (!fused || i + 1 == k) MFX_TRY(launch_scale<T>(g, w, n, xs + (i + 1) * n, ldx, PN, nullptr, 0, beta + i, k, nullptr));
+      return MFX_OK;
+    };
+    MFX_TRY(c.for_groups(three_term));
   }
   return MFX_OK;
 }
@@ -854,6 +894,7 @@ static int lanczos_adjoint_t(const mfx_operator* op, int64_t n, int64_t k, int64
                              const mfx_comm* comm = nullptr, T* Lamfull = nullptr) {
   Ctx<T> c(n, k, p, pick_vec<T>(n, {xs, dxs, dv, Lam, ws.w}), stream);
   if (comm) c.shard(comm, static_cast<T*>(ws.stage));
+  c.set_group(probe_group(n, 3, p, sizeof(T), 1));  // a step's passes touch x_j, x_{j+1}, xi and lambda_j, lambda_{j+1}, A lambda
   T* P1 = static_cast<T*>(ws.p1);
   T* PN = static_cast<T*>(ws.pn);
   T* xi = static_cast<T*>(ws.w);
@@ -866,37 +907,56 @@ static int lanczos_adjoint_t(const mfx_operator* op, int64_t n, int64_t k, int64
   } else {
     MFX_TRY(zero_async(xi, sizeof(T) * p * n, stream));
   }
+  // the three dots of step j and lambda_j (lanczos.py:317-326), for one probe group
+  auto dots_lambda = [&](const Ctx<T>& g, int64_t j) -> int {
+    const T* xj = g.at(xs + j * n, ldx);
+    const T* xj1 = g.at(xs + (j + 1) * n, ldx);
+    const T* lam_plus = (j + 1 < k) ? g.at(Lam + (j + 1) * n, ldl) : nullptr;
+    MFX_VEC_SWITCH(c.vec, (k_lz_adj_dots<T, VEC><<<g.grid(), c.wg, 0, stream>>>(xj, xj1, ldx, g.at(xi, n), lam_plus, ldl, n,
+                                                                              g.at(c.producer(PN), (int64_t)3 * c.nblk), c.nblk)));
+    MFX_CHECK_LAUNCH();
+    MFX_TRY(g.finish(PN, 3, 3));
+    MFX_VEC_SWITCH(c.vec, (k_lz_adj_lambda<T, VEC><<<g.grid(), c.wg, 0, stream>>>(
+                              xj, xj1, ldx, g.at(xi, n), n, g.at(PN, (int64_t)3 * c.nblk_in), c.nblk_in, g.at(beta, k), g.at(dalpha, k),
+                              g.at(dbeta, k), (int)k, (int)j, g.at(Lam + j * n, ldl), ldl, g.at(munu, 2))));
+    MFX_CHECK_LAUNCH();
+    return MFX_OK;
+  };
+  {
+    ScopedTimer t(2, stream);
+    MFX_TRY(c.for_groups([&](const Ctx<T>& g) -> int { return dots_lambda(g, k - 1); }));
+  }
   for (int64_t j = k - 1; j >= 0; --j) {
     const T* xj = xs + j * n;
-    const T* xj1 = xs + (j + 1) * n;
-    const T* lam_plus = (j + 1 < k) ? Lam + (j + 1) * n : nullptr;
     T* lam_j = Lam + j * n;
-    {
-      ScopedTimer t(2, stream);
-      MFX_VEC_SWITCH(c.vec, (k_lz_adj_dots<T, VEC><<<c.grid(), c.wg, 0, stream>>>(xj, xj1, ldx, xi, lam_plus, ldl, n, c.producer(PN), c.nblk)));
-      MFX_CHECK_LAUNCH();
-      MFX_TRY(c.finish(PN, 3, 3));
-      MFX_VEC_SWITCH(c.vec, (k_lz_adj_lambda<T, VEC><<<c.grid(), c.wg, 0, stream>>>(
-                                xj, xj1, ldx, xi, n, PN, c.nblk_in, beta, dalpha, dbeta, (int)k, (int)j, lam_j, ldl, munu)));
-      MFX_CHECK_LAUNCH();
-    }
+    // What follows lambda_0 (A lambda_0, the last xi, its dot with x_0) produces only dv.  Without dv it is skipped, except the
+    // operator application where it does more than that: a callback operator accumulates its parameter gradient inside, and the
+    // row-sharded application gathers lambda_0 into Lambdafull for the parameter sweep.
+    const bool skip = j == 0 && !dv;
+    if (skip && op->kind != MFX_OP_CALLBACK && !comm) break;
     // A lambda (Q4: not A^T), parameter gradient of x_j^T A(theta) lambda (lanczos.py:328-329)
     if (comm) {
       MFX_TRY(apply_sharded<T>(op, comm, 0, lam_j, ldl, y, n, p, Lamfull + j * op->n, k * op->n, ws, stream));
     } else {
       MFX_TRY(apply_any(op, 2, lam_j, ldl, xj, ldx, y, n, p, ws.opws, ws.opws_bytes, stream));
     }
+    if (skip) break;
     ScopedTimer t(2, stream);
-    MFX_VEC_SWITCH(c.vec, (k_lz_adj_xi<T, VEC><<<c.grid(), c.wg, 0, stream>>>(
-                              dxs ? dxs + j * n : nullptr, ldx, y, lam_j, ldl, lam_plus, ldl, xj1, ldx, n, alpha, beta,
-                              (int)k, (int)j, munu, xi)));
-    MFX_CHECK_LAUNCH();
-  }
-  {
-    ScopedTimer t(2, stream);
-    MFX_TRY(launch_dots<T>(c, xs, ldx, n, 1, xi, n, P1));  // xi . x_0 (Q3: "lambda_1" is the final xi)
-    MFX_VEC_SWITCH(c.vec, (k_lz_adj_dvec<T, VEC><<<c.grid(), c.wg, 0, stream>>>(xs, ldx, xi, n, P1, c.kmax, c.nblk_in, vnorm, dv)));
-    MFX_CHECK_LAUNCH();
+    auto next_xi = [&](const Ctx<T>& g) -> int {  // xi of step j, then the dots and lambda of step j - 1 (or dv), per probe group
+      MFX_VEC_SWITCH(c.vec, (k_lz_adj_xi<T, VEC><<<g.grid(), c.wg, 0, stream>>>(
+                                dxs ? g.at(dxs + j * n, ldx) : nullptr, ldx, g.at(y, n), g.at(lam_j, ldl), ldl,
+                                (j + 1 < k) ? g.at(Lam + (j + 1) * n, ldl) : nullptr, ldl, g.at(xs + (j + 1) * n, ldx), ldx, n,
+                                g.at(alpha, k), g.at(beta, k), (int)k, (int)j, g.at(munu, 2), g.at(xi, n))));
+      MFX_CHECK_LAUNCH();
+      if (j > 0) return dots_lambda(g, j - 1);
+      MFX_TRY(launch_dots<T>(g, xs, ldx, n, 1, xi, n, P1));  // xi . x_0 (Q3: "lambda_1" is the final xi)
+      MFX_VEC_SWITCH(c.vec, (k_lz_adj_dvec<T, VEC><<<g.grid(), c.wg, 0, stream>>>(g.at(xs, ldx), ldx, g.at(xi, n), n,
+                                                                                g.at(P1, (int64_t)c.kmax * c.nblk_in), c.kmax, c.nblk_in,
+                                                                                g.at(vnorm, 1), g.at(dv, n))));
+      MFX_CHECK_LAUNCH();
+      return MFX_OK;
+    };
+    MFX_TRY(c.for_groups(next_xi));
   }
   if (op->kind != MFX_OP_CALLBACK && grads) {
     // d/dtheta sum_j x_j^T A(theta) lambda_j : L = xs (ld (k+1) n per probe), R = Lambda
@@ -913,6 +973,13 @@ static int lanczos_adjoint_t(const mfx_operator* op, int64_t n, int64_t k, int64
     }
   }
   return MFX_OK;
+}
+
+int64_t probe_group(int64_t n, int64_t rows, int64_t p, int64_t elem_size, int adjoint) {
+  static const long long forced = [] { const char* e = getenv("MFX_PROBE_GROUP"); return e ? atoll(e) : -1LL; }();
+  if (forced == 0) return p;
+  if (forced > 0) return forced < p ? forced : p;
+  return probe_group_rule(n, rows, p, elem_size, adjoint);
 }
 
 static int check_common(const mfx_operator* op, int64_t n, int64_t k, int64_t p) {
@@ -933,6 +1000,11 @@ static int check_common(const mfx_operator* op, int64_t n, int64_t k, int64_t p)
 using namespace mfx;
 
 extern "C" {
+
+int64_t mfx_probe_group(int64_t n, int64_t k, int64_t p, int64_t elem_size, int adjoint) {
+  if (n < 1 || k < 1 || p < 1 || elem_size < 1) return -1;
+  return probe_group_rule(n, k, p, elem_size, adjoint);
+}
 
 int64_t mfx_workspace_bytes(const mfx_operator* op, int64_t n, int64_t k, int64_t p) {
   if (!op) return -1;
@@ -1021,7 +1093,7 @@ int mfx_arnoldi_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p,
                         const void* r, const void* c, const void* dQ, const void* dH, const void* dr,
                         const void* dc, int reortho, void* dv, void* Lambda, const mfx_op_grads* grads, void* ws,
                         int64_t ws_bytes, void* stream) {
-  MFX_REQUIRE(Q && H && r && c && dH && dv && Lambda, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(Q && H && r && c && dH && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(reortho == MFX_REORTHO_NONE || reortho == MFX_REORTHO_FULL, MFX_ERR_INVALID, "bad reortho flag %d", reortho);
   MFX_TRY(check_grads_x(op, grads, false));
   MFX_DRIVER_PROLOGUE();
@@ -1080,7 +1152,7 @@ int mfx_arnoldi_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
                                 const void* Q, const void* Qfull, const void* H, const void* r, const void* c,
                                 const void* dQ, const void* dH, const void* dr, const void* dc, int reortho, void* dv,
                                 void* Lambda, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
-  MFX_REQUIRE(Q && Qfull && H && r && c && dH && dv && Lambda, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(Q && Qfull && H && r && c && dH && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(reortho == MFX_REORTHO_NONE || reortho == MFX_REORTHO_FULL, MFX_ERR_INVALID, "bad reortho flag %d", reortho);
   MFX_TRY(check_grads_x(op, grads, true));
   MFX_SHARDED_PROLOGUE();
@@ -1106,7 +1178,7 @@ int mfx_lanczos_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
                                 const void* alpha, const void* beta, const void* vnorm, const void* dxs, const void* dalpha,
                                 const void* dbeta, void* dv, void* Lambda, void* Lambdafull, const mfx_op_grads* grads, void* ws,
                                 int64_t ws_bytes, void* stream) {
-  MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && dv && Lambda && Lambdafull, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && Lambda && Lambdafull, MFX_ERR_INVALID, "null argument");
   MFX_TRY(check_grads_x(op, grads, true));
   MFX_SHARDED_PROLOGUE();
   if (op->dtype == MFX_F32)
@@ -1134,7 +1206,7 @@ int mfx_lanczos_forward(const mfx_operator* op, const void* v0, int64_t n, int64
 int mfx_lanczos_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p, const void* xs, const void* alpha,
                         const void* beta, const void* vnorm, const void* dxs, const void* dalpha, const void* dbeta,
                         void* dv, void* Lambda, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
-  MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && dv && Lambda, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_TRY(check_grads_x(op, grads, false));
   MFX_DRIVER_PROLOGUE();
   GraphKey key = driver_key(4, op, n, k, p, grads, ws, ws_bytes, stream);

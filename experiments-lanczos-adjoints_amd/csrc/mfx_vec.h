@@ -449,7 +449,10 @@ __global__ __launch_bounds__(256) void k_compact_partials(const T* __restrict__ 
 
 template <typename T>
 struct Ctx {
-  int64_t n, k, p;
+  int64_t n, k, p;  // p = probes of ONE launch: all of them, or the group a window() selects
+  int64_t pall;     // all probes of the call
+  int64_t b0 = 0;   // first probe of this launch: the launch helpers offset every per-probe pointer by it
+  int64_t group;    // probes per launch group (for_groups); pall = ungrouped
   int wg, nblk, kmax, vec;
   int ept = kEpt;  // elements per thread of the kernels launched through MFX_VEC_EPT_SWITCH
   hipStream_t stream;
@@ -457,7 +460,7 @@ struct Ctx {
   T* stage = nullptr;              // (p, kmax, nblk) producer scratch of the sharded mode
   int nblk_in;                     // slices the consumers sum over
   Ctx(int64_t n_, int64_t k_, int64_t p_, int vec_, hipStream_t s)
-      : n(n_), k(k_), p(p_), wg(pick_wg(n_, p_)), nblk((int)((n_ + (int64_t)wg * kEpt - 1) / ((int64_t)wg * kEpt))),
+      : n(n_), k(k_), p(p_), pall(p_), group(p_), wg(pick_wg(n_, p_)), nblk((int)((n_ + (int64_t)wg * kEpt - 1) / ((int64_t)wg * kEpt))),
         kmax((int)(k_ + 1)), vec(vec_), stream(s), nblk_in(nblk) {}
   // Finer slices (one 16-byte load per thread and row) when the 2048-element slicing gives fewer than 128 workgroups: the
   // vector kernels are bandwidth-bound PER CU (measured on config 3, n = 102400, one vector: 50 workgroups stream 1.4 TB/s).
@@ -477,6 +480,28 @@ struct Ctx {
     nblk_in = 1;
   }
   dim3 grid() const { return dim3(nblk, (unsigned)p); }
+  // Probe groups (mfx_internal.h: probe_group): the same kernels, the probe dimension of the grid cut to `cnt` probes from
+  // `first` on.  Geometry (workgroup size, slices, vector width) stays that of the whole call, and a probe's partial sums are
+  // produced and re-reduced by the same workgroups in the same order: results are bit-identical for every group size.
+  // Never in the row-sharded mode, whose all-reduces span all probes.
+  void set_group(int64_t g) { group = (comm || g < 1 || g > pall) ? pall : g; }
+  Ctx window(int64_t first, int64_t cnt) const {
+    Ctx w = *this;
+    w.b0 = first;
+    w.p = cnt;
+    return w;
+  }
+  // f(group context) for every probe group in turn; f returns an MFX_* code
+  template <typename F>
+  int for_groups(F&& f) const {
+    for (int64_t first = 0; first < pall; first += group) {
+      const int rc = f(window(first, pall - first < group ? pall - first : group));
+      if (rc != MFX_OK) return rc;
+    }
+    return MFX_OK;
+  }
+  template <typename P>
+  P* at(P* ptr, int64_t ld) const { return ptr ? ptr + b0 * ld : ptr; }  // a per-probe array of leading dimension ld
   // where a producer writes its (b, j, slice) partials that the caller wants in `dst`
   T* producer(T* dst) const { return comm ? stage : dst; }
   // sharded: dst[b][j] (j < m, row stride kmax_) = sum over the ranks and slices of the partials just produced in `stage`
@@ -505,7 +530,7 @@ static int launch_dots(const Ctx<T>& c, const T* rows, int64_t rows_ldb, int64_t
   const bool tiled = ncols > 1 && c.vec > 1 && c.ept == VecWidth<T>::value;  // CT vectors of EPT elements in registers beside the row buffers
   const int ctiles = tiled ? (ncols + kDotsColTile - 1) / kDotsColTile : ncols;
   // few slices (one vector, n ~ 1e5): split the rows over workgroups as well
-  const int64_t wgs = (int64_t)c.nblk * c.p * ctiles;
+  const int64_t wgs = (int64_t)c.nblk * c.pall * ctiles;  // (of the whole call: the row split does not depend on the probe group)
   const int64_t maxgroups = wgs < 256 ? 1024 / wgs : 1;
   int jchunk = (int)((m + maxgroups - 1) / maxgroups);
   const int jmin = c.ept <= 4 ? 16 : 8;  // one buffer of sweep_rows at least
@@ -514,13 +539,16 @@ static int launch_dots(const Ctx<T>& c, const T* rows, int64_t rows_ldb, int64_t
   const int ngroups = (m + jchunk - 1) / jchunk;
   const size_t sh = (size_t)4 * (tiled ? kDotsColTile : 1) * jchunk * sizeof(T);
   dim3 grid(c.nblk, (unsigned)c.p, (unsigned)(ctiles * ngroups));
+  rows = c.at(rows, rows_ldb);
+  x = c.at(x, ldx);
+  T* const part = c.at(c.producer(partial), (int64_t)c.kmax * c.nblk);
   if (tiled) {
     constexpr int VEC = VecWidth<T>::value;  // Ctx::fine: ept == VEC, 16-byte loads
-    k_dots<T, VEC, VEC, kDotsColTile><<<grid, c.wg, sh, c.stream>>>(rows, rows_ldb, row_stride, m, x, ldx, c.n, c.producer(partial),
+    k_dots<T, VEC, VEC, kDotsColTile><<<grid, c.wg, sh, c.stream>>>(rows, rows_ldb, row_stride, m, x, ldx, c.n, part,
                                                                    c.kmax, c.nblk, jchunk, ngroups, ncols, x_zstride, part_zstride);
   } else {
     MFX_VEC_EPT_SWITCH(c, (k_dots<T, VEC, EPT, 1><<<grid, c.wg, sh, c.stream>>>(
-                              rows, rows_ldb, row_stride, m, x, ldx, c.n, c.producer(partial), c.kmax, c.nblk, jchunk,
+                              rows, rows_ldb, row_stride, m, x, ldx, c.n, part, c.kmax, c.nblk, jchunk,
                               ngroups, ncols, x_zstride, part_zstride)));
   }
   MFX_CHECK_LAUNCH();
@@ -538,6 +566,15 @@ static int launch_update(const Ctx<T>& c, UpdateArgs<T> a, bool dots, bool norm)
   MFX_REQUIRE(!(c.comm && dots && norm), MFX_ERR_UNSUPPORTED, "sharded update: fused dots + norm share one staging buffer");
   if (dots) a.partial_out = c.producer(want_dots);
   if (norm) a.partial_norm = c.producer(want_norm);
+  a.rows = c.at(a.rows, a.rows_ldb);
+  a.partial_in = c.at(a.partial_in, (int64_t)a.kmax * a.nblk_in);
+  a.extra = c.at(a.extra, a.extra_ldb);
+  a.hout = c.at(a.hout, a.hout_ldb);
+  a.x = c.at(a.x, a.ldx);
+  a.y = c.at(a.y, a.ldy);
+  a.y2 = c.at(a.y2, a.ldy2);
+  a.partial_out = c.at(a.partial_out, (int64_t)a.kmax * a.nblk);
+  a.partial_norm = c.at(a.partial_norm, (int64_t)a.nblk);
   const size_t sh = (size_t)(a.m + (dots ? 4 * a.m : 0) + 4) * sizeof(T);
   MFX_REQUIRE(sh <= 64 * 1024, MFX_ERR_UNSUPPORTED, "Krylov depth %d too large for the update kernels' coefficient buffers (%zu B of LDS > 64 KiB)",
               a.m, sh);
@@ -558,7 +595,8 @@ static int launch_update(const Ctx<T>& c, UpdateArgs<T> a, bool dots, bool norm)
 
 template <typename T>
 static int launch_sumsq(const Ctx<T>& c, const T* x, int64_t ldx, T* partial_norm) {
-  MFX_VEC_EPT_SWITCH(c, (k_sumsq<T, VEC, EPT><<<c.grid(), c.wg, 0, c.stream>>>(x, ldx, c.n, c.producer(partial_norm), c.nblk)));
+  MFX_VEC_EPT_SWITCH(c, (k_sumsq<T, VEC, EPT><<<c.grid(), c.wg, 0, c.stream>>>(c.at(x, ldx), ldx, c.n, c.at(c.producer(partial_norm), (int64_t)c.nblk),
+                                                                            c.nblk)));
   MFX_CHECK_LAUNCH();
   return c.finish(partial_norm, 1, 1);
 }
@@ -567,8 +605,10 @@ template <typename T>
 static int launch_scale(const Ctx<T>& c, const T* x, int64_t ldx, T* y, int64_t ldy, const T* partial_norm,
                         const T* scale, int mode, T* len_out, int64_t len_ld, T* inv_out) {
   dim3 grid = y ? c.grid() : dim3(1, (unsigned)c.p);
-  MFX_VEC_EPT_SWITCH(c, (k_scale<T, VEC, EPT><<<grid, c.wg, 0, c.stream>>>(x, ldx, y, ldy, c.n, partial_norm, c.nblk_in,
-                                                                        scale, mode, len_out, len_ld, inv_out)));
+  MFX_VEC_EPT_SWITCH(c, (k_scale<T, VEC, EPT><<<grid, c.wg, 0, c.stream>>>(c.at(x, ldx), ldx, c.at(y, ldy), ldy, c.n,
+                                                                        c.at(partial_norm, (int64_t)c.nblk_in), c.nblk_in,
+                                                                        c.at(scale, 1), mode, c.at(len_out, len_ld), len_ld,
+                                                                        c.at(inv_out, 1))));
   MFX_CHECK_LAUNCH();
   return MFX_OK;
 }

@@ -115,6 +115,7 @@ _OPP, _GRP, _CMP = C.POINTER(Operator), C.POINTER(OpGrads), C.POINTER(Comm)
 SYMBOLS = {
     "mfx_last_error": (C.c_char_p, []),
     "mfx_version": (_I, []),
+    "mfx_probe_group": (_I64, [_I64, _I64, _I64, _I64, _I]),
     "mfx_workspace_bytes": (_I64, [_OPP, _I64, _I64, _I64]),
     "mfx_op_apply": (_I, [_OPP, _P, _I64, _P, _I64, _I64, _I, _P, _I64, _P]),
     "mfx_op_vjp_params": (_I, [_OPP, _P, _I64, _P, _I64, _I64, _GRP, _P, _I64, _P]),
@@ -302,6 +303,15 @@ def scratch(need: int, device) -> torch.Tensor:
 
 def workspace_pcg(desc: Operator, n: int, p: int, rank: int, device) -> torch.Tensor:
     return scratch(int(get().mfx_pcg_workspace_bytes(C.byref(desc), n, p, rank)), device)
+
+
+def probe_group(n: int, k: int, p: int, elem_size: int, adjoint: bool) -> int:
+    """Probes per launch group of the Krylov vector kernels for an (n, k, p) problem (``mfx_probe_group``: the rule itself,
+    without the MFX_PROBE_GROUP override)."""
+    g = int(get().mfx_probe_group(n, k, p, elem_size, int(adjoint)))
+    if g < 1:
+        raise ValueError(f"mfx_probe_group({n}, {k}, {p}, {elem_size}, {adjoint}) = {g}")
+    return g
 
 
 def timing_enable(flag: bool):

@@ -191,7 +191,9 @@ class _ArnoldiFn(torch.autograd.Function):
         dr = None if dr is None else dr.contiguous()
         dc = None if dc is None else dc.contiguous()
         dH = torch.zeros_like(H) if dH is None else dH.contiguous()
-        dv = torch.empty((p, n), dtype=dt, device=dev)
+        # probes are constants in SLQ / GP training: without a cotangent to return, the driver skips the last operator application
+        # and the vector kernels behind it, which produce nothing else (dv == NULL, include/mfx.h)
+        dv = torch.empty((p, n), dtype=dt, device=dev) if ctx.needs_input_grad[5] else None
         Lam = torch.empty((p, k, n), dtype=dt, device=dev)
         keep = None
         if isinstance(op, CallbackOp):
@@ -272,7 +274,7 @@ class _ArnoldiShardedFn(torch.autograd.Function):
         dr = None if dr is None else dr.contiguous()
         dc = None if dc is None else dc.contiguous()
         dH = torch.zeros_like(H) if dH is None else dH.contiguous()
-        dv = torch.empty((p, nrows), dtype=dt, device=dev)
+        dv = torch.empty((p, nrows), dtype=dt, device=dev) if ctx.needs_input_grad[5] else None  # see _ArnoldiFn.backward
         Lam = torch.empty((p, k, nrows), dtype=dt, device=dev)
         desc = op.descriptor(cparams, dt, n)
         gstruct, grads = op.new_grads(*cparams)

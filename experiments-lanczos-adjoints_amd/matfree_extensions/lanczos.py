@@ -148,7 +148,8 @@ class _LanczosFn(torch.autograd.Function):
         dxs = None if dxs is None else dxs.contiguous()
         dalpha = torch.zeros_like(alpha) if dalpha is None else dalpha.contiguous()
         dbeta = torch.zeros_like(beta) if dbeta is None else dbeta.contiguous()
-        dv = torch.empty((p, n), dtype=dt, device=dev)
+        # no cotangent wanted for the start vector: the driver skips what only produces it (dv == NULL, include/mfx.h)
+        dv = torch.empty((p, n), dtype=dt, device=dev) if ctx.needs_input_grad[3] else None
         Lam = torch.empty((p, k, n), dtype=dt, device=dev)
         keep = None
         if isinstance(op, CallbackOp):
@@ -225,7 +226,7 @@ class _LanczosShardedFn(torch.autograd.Function):
         dxs = None if dxs is None else dxs.contiguous()
         dalpha = torch.zeros_like(alpha) if dalpha is None else dalpha.contiguous()
         dbeta = torch.zeros_like(beta) if dbeta is None else dbeta.contiguous()
-        dv = torch.empty((p, nrows), dtype=dt, device=dev)
+        dv = torch.empty((p, nrows), dtype=dt, device=dev) if ctx.needs_input_grad[3] else None  # see _LanczosFn.backward
         Lam = torch.empty((p, k, nrows), dtype=dt, device=dev)
         Lamfull = torch.empty((p, k, n), dtype=dt, device=dev)
         desc = op.descriptor(cparams, dt, n)

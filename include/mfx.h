@@ -148,6 +148,17 @@ typedef struct mfx_op_grads {
 const char* mfx_last_error(void);
 int mfx_version(void);
 
+/* Probe groups of the Krylov vector kernels.  Between two operator applications the drivers below run their vector kernels
+ * (dots, updates, combine) group by group -- the same kernels on g of the p probes at a time, every pass of a group before the
+ * next group -- so that the later passes over a group's basis rows can be served by the Infinity Cache instead of HBM.  Results
+ * are bit-identical for every g (a probe's sums are formed by the same workgroups in the same order).  This function is the rule:
+ * the largest power of two g whose rows of one pass, g * k * n * elem_size bytes (twice that for adjoint != 0, which sweeps the
+ * adjoint states beside the basis), fit a fixed budget; p when all probes fit -- then the launches are exactly the ungrouped
+ * ones (every small problem).  1 <= g <= p always; -1 on a non-positive argument.  The row-sharded drivers do not group (each of
+ * their vector kernels ends in an all-reduce over all probes).  The environment variable MFX_PROBE_GROUP=<g>, read once per
+ * process, overrides the rule inside the drivers (0 = all probes in one launch); this function ignores it. */
+int64_t mfx_probe_group(int64_t n, int64_t k, int64_t p, int64_t elem_size, int adjoint);
+
 /* Workspace (bytes) needed by the drivers below for an (n, k, p) problem on this operator. */
 int64_t mfx_workspace_bytes(const mfx_operator* op, int64_t n, int64_t k, int64_t p);
 
@@ -189,7 +200,11 @@ int mfx_arnoldi_forward_complex(const mfx_operator* op, const void* v0, int64_t 
  * dr (p, n) or NULL, dc (p) or NULL.  Outputs dv (p, n); parameter gradients accumulated into
  * `grads` (native operators: one deferred sweep; CALLBACK: inside the callback, per step).
  * reortho = MFX_REORTHO_FULL re-projects lambda every step (arnoldi.py:200-204).
- * Lambda (p, k, n) is caller-provided scratch that holds the adjoint states on return. */
+ * Lambda (p, k, n) is caller-provided scratch that holds the adjoint states on return.
+ * dv == NULL: the cotangent of the start vector is not wanted (probes are constants in SLQ and in GP training).  The driver then
+ * skips what produces only dv -- the last of the k operator applications with its dots, its combine step and the final scaling --
+ * and leaves Lambda and `grads` bit for bit what they are with dv.  A CALLBACK operator is still applied k times (it accumulates
+ * its parameter gradient inside the application); only the vector kernels behind the last one are skipped. */
 int mfx_arnoldi_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p, const void* Q,
                         const void* H, const void* r, const void* c, const void* dQ,
                         const void* dH, const void* dr, const void* dc, int reortho, void* dv,
@@ -204,7 +219,9 @@ int mfx_lanczos_forward(const mfx_operator* op, const void* v0, int64_t n, int64
 
 /* lanczos._adjoint (lanczos.py:288-335).  dxs (p, k+1, n) or NULL, dalpha (p, k), dbeta (p, k).
  * Outputs dv (p, n); Lambda (p, k, n) scratch (adjoint states).  Applies A (not A^T) as the
- * reference does (quirk Q4, lanczos.py:328). */
+ * reference does (quirk Q4, lanczos.py:328).
+ * dv == NULL as in mfx_arnoldi_adjoint: A lambda_0, the last xi and its dot with x_0 are skipped (a CALLBACK operator is still
+ * applied to lambda_0); Lambda and `grads` are unchanged. */
 int mfx_lanczos_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p, const void* xs,
                         const void* alpha, const void* beta, const void* vnorm, const void* dxs,
                         const void* dalpha, const void* dbeta, void* dv, void* Lambda,
@@ -309,7 +326,8 @@ int mfx_arnoldi_forward_sharded(const mfx_operator* op, const mfx_comm* comm, co
                                 int64_t ws_bytes, void* stream);
 
 /* mfx_arnoldi_adjoint on row shards.  Q, dQ, Lambda: (p, k, nrows); r, dr, dv: (p, nrows); Qfull (p, k, n) from the
- * forward pass; H, dH, c, dc replicated.  grads: partial sums over this rank's rows (see above). */
+ * forward pass; H, dH, c, dc replicated.  grads: partial sums over this rank's rows (see above).  dv == NULL as in
+ * mfx_arnoldi_adjoint (the last all-gather + operator application and what follows it are skipped). */
 int mfx_arnoldi_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, int64_t n, int64_t k, int64_t p,
                                 const void* Q, const void* Qfull, const void* H, const void* r, const void* c,
                                 const void* dQ, const void* dH, const void* dr, const void* dc, int reortho, void* dv,
@@ -320,7 +338,8 @@ int mfx_arnoldi_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
  * vnorm and their cotangents are replicated.  Lambdafull (p, k, n) receives the gathered adjoint states -- the operator input
  * of every adjoint step and the right factor of the parameter-gradient sweep, whose result (`grads`) is this rank's PARTIAL sum
  * over its rows: the caller adds the ranks up.  Collectives per step: one all-gather of the iterate, the dots as small
- * all-reduces.  Workspace: mfx_sharded_workspace_bytes. */
+ * all-reduces.  Workspace: mfx_sharded_workspace_bytes.  dv == NULL: the last xi and its dot with x_0 are skipped; lambda_0 is
+ * still gathered (and the operator applied to it), because Lambdafull feeds the parameter sweep. */
 int mfx_lanczos_forward_sharded(const mfx_operator* op, const mfx_comm* comm, const void* v0, int64_t n, int64_t k,
                                 int64_t p, void* xs, void* alpha, void* beta, void* vnorm, void* ws, int64_t ws_bytes,
                                 void* stream);
