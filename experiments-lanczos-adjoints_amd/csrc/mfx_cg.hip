@@ -57,6 +57,11 @@ struct CgArgs {
   int nblk_in;   // slices the consumers sum over (= nblk; 1 in the row-sharded mode, where the partials arrive summed)
   T* qrow;       // re-orthogonalising variant: row i of Q = r_old / sqrt(r_old . z_old)  (cg.py:200), or null
   int64_t ldq;   // batch stride of Q
+  // mBCG (mfx_mbcg_solve), or null: block 0 of a column records the scalars it holds anyway, entry log_step of its row
+  T* log_rz;      // (p, ldlog): (r.z)_j, written by k_cg_dir (j = 0: the start; j = it + 1: after iteration it)
+  T* log_pap;     // (p, ldlog): (p.Ap)_j, written by k_cg_xr of iteration j
+  int64_t ldlog;
+  int log_step;
 };
 
 template <typename T, int VEC>
@@ -71,6 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_xr(CgArgs<T> a) {
     const T pap = reduce_partials_group<T, 64>(a.part_pap + (int64_t)b * a.kmax * a.nblk_in, a.nblk_in, tid);
     if (tid == 0) {
       alpha_sh = safe_div(a.rz_cur[b], pap);
+      if (a.log_pap && blk == 0) a.log_pap[(int64_t)b * a.ldlog + a.log_step] = pap;
       const T rzv = a.rz_cur[b];
       smn[0] = sqrt(rzv > T(0) ? rzv : T(0));  // _safe_sqrt (cg.py:244-246)
     }
@@ -124,7 +130,10 @@ __global__ __launch_bounds__(kBlock) void k_cg_dir(CgArgs<T> a) {
     const T rz_new = reduce_partials_group<T, 64>(a.part_rz + (int64_t)b * a.nblk_in, a.nblk_in, tid);
     if (tid == 0) {
       beta_sh = a.first ? T(0) : safe_div(rz_new, a.rz_cur[b]);
-      if (blk == 0) a.rz_next[b] = rz_new;
+      if (blk == 0) {
+        a.rz_next[b] = rz_new;
+        if (a.log_rz) a.log_rz[(int64_t)b * a.ldlog + a.log_step] = rz_new;
+      }
     }
   }
   __syncthreads();
@@ -185,6 +194,90 @@ template <typename T>
 __global__ void k_fill_i64(int64_t* dst, int64_t p, int64_t v) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b < p) dst[b] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mBCG: the Lanczos tridiagonal of M^-1/2 A M^-1/2 started at M^-1/2 b from the recorded CG scalars.  With
+//   alpha_j = (r.z)_j / (p.Ap)_j, beta_j = (r.z)_{j+1} / (r.z)_j:
+//   tdiag[j] = 1 / alpha_j + beta_{j-1} / alpha_{j-1},  toff[j] = sqrt(beta_j) / alpha_j
+// Step j is live when j < num_steps, (r.z)_j > eps^2 and (p.Ap)_j > eps^2 (the threshold of safe_div: below it the loop
+// itself stops dividing) and every earlier step is live; depth = the number of live steps m.  Entries from m on (toff: from
+// m - 1 on) are the identity block (1, 0), which e1^T log(T) e1 does not see.  One workgroup per right-hand side.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_mbcg_finish(const T* __restrict__ log_rz, const T* __restrict__ log_pap,
+                                                     int64_t ldlog, const int64_t* __restrict__ nsteps, int maxiter,
+                                                     T* __restrict__ tdiag, T* __restrict__ toff, T* __restrict__ rz0,
+                                                     int64_t* __restrict__ depth) {
+  __shared__ int m_sh;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const T* rz = log_rz + b * ldlog;
+  const T* pap = log_pap + b * ldlog;
+  const T eps2 = dtype_eps<T>() * dtype_eps<T>();
+  const int64_t ns64 = nsteps[b];
+  const int ns = ns64 < (int64_t)maxiter ? (int)ns64 : maxiter;
+  if (tid == 0) m_sh = ns;
+  __syncthreads();
+  for (int j = tid; j < ns; j += (int)blockDim.x)
+    if (!(rz[j] > eps2 && pap[j] > eps2)) atomicMin(&m_sh, j);  // NaN is not live
+  __syncthreads();
+  const int m = m_sh;
+  if (tid == 0) {
+    depth[b] = m;
+    rz0[b] = rz[0];
+  }
+  for (int j = tid; j < maxiter; j += (int)blockDim.x) {
+    T dj = T(1), ej = T(0);
+    if (j < m) {
+      const T aj = rz[j] / pap[j];
+      dj = T(1) / aj;
+      if (j > 0) dj += (rz[j] / rz[j - 1]) / (rz[j - 1] / pap[j - 1]);
+      if (j < m - 1) ej = sqrt(rz[j + 1] / rz[j]) / aj;
+    }
+    tdiag[b * maxiter + j] = dj;
+    toff[b * maxiter + j] = ej;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// probes with covariance s I + L L^T:  out[b][i] = sqrt(s) eps(b, i) + sum_c Lt[c][i] eps(b, n + c),  eps = the +-1 of
+// mfx_rademacher for (seed, first_probe + b).  kSampleProbes probes per workgroup share every load of L^T; their rank signs sit
+// in LDS; nothing of size (p, n + rank) is stored.
+// ------------------------------------------------------------------------------------------------
+constexpr int kSampleProbes = 8;
+template <typename T>
+__global__ __launch_bounds__(256) void k_precond_sample(uint64_t seed, int64_t first_probe, int64_t p, int64_t n, int rank,
+                                                        const T* __restrict__ lt, const T* __restrict__ shift,
+                                                        T* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* sgn = reinterpret_cast<T*>(smem_raw);  // [kSampleProbes][rank]
+  const int tid = threadIdx.x;
+  const int64_t b0 = (int64_t)blockIdx.y * kSampleProbes;
+  const int nb = p - b0 < kSampleProbes ? (int)(p - b0) : kSampleProbes;
+  uint64_t key[kSampleProbes];
+#pragma unroll
+  for (int q = 0; q < kSampleProbes; ++q) key[q] = rademacher_key(seed, first_probe + b0 + (q < nb ? q : 0));
+  for (int idx = tid; idx < kSampleProbes * rank; idx += (int)blockDim.x) {
+    const int q = idx / rank, c = idx - q * rank;
+    sgn[idx] = rademacher_sign<T>(rademacher_key(seed, first_probe + b0 + (q < nb ? q : 0)), n + c);
+  }
+  __syncthreads();
+  const T root = shift ? sqrt(shift[0]) : T(1);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + tid; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    T acc[kSampleProbes];
+#pragma unroll
+    for (int q = 0; q < kSampleProbes; ++q) acc[q] = root * rademacher_sign<T>(key[q], i);
+#pragma unroll 4
+    for (int c = 0; c < rank; ++c) {
+      const T l = lt[(int64_t)c * n + i];
+#pragma unroll
+      for (int q = 0; q < kSampleProbes; ++q) acc[q] += l * sgn[q * rank + c];
+    }
+#pragma unroll
+    for (int q = 0; q < kSampleProbes; ++q)
+      if (q < nb) out[(b0 + q) * n + i] = acc[q];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -333,10 +426,18 @@ static int64_t cg_carve(const mfx_operator* op, int64_t n, int64_t p, int64_t ra
 // ------------------------------------------------------------------------------------------------
 // PCG driver
 // ------------------------------------------------------------------------------------------------
+// what mfx_mbcg_solve takes out of the loop beside x, r and num_steps (pcg_t: mb == NULL is the plain solve)
+template <typename T>
+struct MbcgRecord {
+  T* w0;                 // (p, n) or null: the first preconditioned residual M^-1 b (b itself without a preconditioner)
+  T *log_rz, *log_pap;   // (p, maxiter + 1) each: CgArgs::log_rz / log_pap
+};
+
 template <typename T>
 static int pcg_t(const mfx_operator* op, const T* b, int64_t ldb, int64_t n, int64_t p, const Precond* pc,
                  int64_t maxiter, int64_t miniter, double atol, double rtol, int adaptive, T* x, T* r,
-                 int64_t* num_steps, T* Q, const CgWs& ws, hipStream_t stream, const mfx_comm* comm = nullptr) {
+                 int64_t* num_steps, T* Q, const CgWs& ws, hipStream_t stream, const mfx_comm* comm = nullptr,
+                 const MbcgRecord<T>* mb = nullptr) {
   // comm != NULL: row-sharded -- n = this rank's rows of every vector (and columns of L^T), op->n = the system size; the
   // operator input is gathered, every inner product (p.Ap, r.z, the error sum, L^T v) is summed over the ranks, so all ranks
   // take the same steps and stop together
@@ -363,6 +464,9 @@ static int pcg_t(const mfx_operator* op, const T* b, int64_t ldb, int64_t n, int
   a.x = x; a.r = r; a.pv = pv; a.z = z; a.Ap = Ap; a.n = n;
   a.part_pap = (T*)ws.part_a; a.part_rz = (T*)ws.part_rz; a.part_err = adaptive ? (T*)ws.part_err : nullptr;
   a.active = nullptr; a.atol = (T)atol; a.rtol = (T)rtol; a.kmax = c.kmax; a.nblk = c.nblk; a.nblk_in = c.nblk_in; a.has_z = pc ? 1 : 0;
+  if (mb) {
+    a.log_rz = mb->log_rz; a.log_pap = mb->log_pap; a.ldlog = maxiter + 1;
+  }
   if (comm) {  // producers write per-slice partials into their staging buffers; the summed values land where the consumers read
     a.part_rz = stage_rz;
     if (adaptive) a.part_err = stage_err;
@@ -376,6 +480,8 @@ static int pcg_t(const mfx_operator* op, const T* b, int64_t ldb, int64_t n, int
     } else {
       MFX_TRY(launch_sumsq<T>(c, r, n, part_rz));
     }
+    if (mb && mb->w0)
+      MFX_CHECK_HIP(hipMemcpyAsync(mb->w0, pc ? z : r, sizeof(T) * p * n, hipMemcpyDeviceToDevice, stream));
     CgArgs<T> d = a;  // k_cg_dir only READS the r.z partials: always the summed ones
     d.part_rz = part_rz;
     d.first = 1; d.rz_cur = rz; d.rz_next = rz;
@@ -413,6 +519,7 @@ static int pcg_t(const mfx_operator* op, const T* b, int64_t ldb, int64_t n, int
     MFX_TRY(launch_dots<T>(c, Ap, n, 0, 1, pv, n, (T*)ws.part_a));
     a.rz_cur = rz + (it & 1) * p;
     a.rz_next = rz + ((it + 1) & 1) * p;
+    a.log_step = (int)it;
     if (Q) {
       a.qrow = Q + it * n;
       a.ldq = maxiter * n;
@@ -443,11 +550,27 @@ static int pcg_t(const mfx_operator* op, const T* b, int64_t ldb, int64_t n, int
     }
     CgArgs<T> d = a;
     d.part_rz = part_rz;
+    d.log_step = (int)it + 1;
     MFX_VEC_SWITCH(c.vec, (k_cg_dir<T, VEC><<<c.grid(), c.wg, 0, stream>>>(d)));
     MFX_CHECK_LAUNCH();
   }
   if (num_steps)
     MFX_CHECK_HIP(hipMemcpyAsync(num_steps, nsteps, sizeof(int64_t) * p, hipMemcpyDeviceToDevice, stream));
+  return MFX_OK;
+}
+
+// the PCG loop with its scalars recorded, then ONE small kernel that turns the record into tdiag / toff / rz0 / depth
+template <typename T>
+static int mbcg_t(const mfx_operator* op, const T* b, int64_t ldb, int64_t n, int64_t p, const Precond* pc, int64_t maxiter,
+                  int64_t miniter, double atol, double rtol, int adaptive, T* x, T* r, int64_t* num_steps, T* w0, T* tdiag,
+                  T* toff, T* rz0, int64_t* depth, const CgWs& ws, void* logs, hipStream_t stream) {
+  MbcgRecord<T> mb{w0, (T*)logs, (T*)logs + p * (maxiter + 1)};
+  MFX_TRY(pcg_t<T>(op, b, ldb, n, p, pc, maxiter, miniter, atol, rtol, adaptive, x, r, num_steps, nullptr, ws, stream, nullptr,
+                   &mb));
+  ScopedTimer t(2, stream);
+  k_mbcg_finish<T><<<(unsigned)p, 256, 0, stream>>>(mb.log_rz, mb.log_pap, maxiter + 1, (const int64_t*)ws.nsteps, (int)maxiter,
+                                                   tdiag, toff, rz0, depth);
+  MFX_CHECK_LAUNCH();
   return MFX_OK;
 }
 
@@ -659,6 +782,70 @@ int mfx_pcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n,
                         (float*)x, (float*)r, (int64_t*)num_steps, nullptr, w, s);
   return pcg_t<double>(op, (const double*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
                        (double*)x, (double*)r, (int64_t*)num_steps, nullptr, w, s);
+}
+
+static int64_t mbcg_log_bytes(const mfx_operator* op, int64_t p, int64_t maxiter) {
+  return align_up(2 * p * (maxiter + 1) * (int64_t)dtype_size(op->dtype), 256);
+}
+
+int64_t mfx_mbcg_workspace_bytes(const mfx_operator* op, int64_t n, int64_t p, int64_t rank, int64_t maxiter) {
+  if (!op || n <= 0 || p <= 0 || rank < 0 || maxiter < 1) return -1;
+  return cg_carve(op, n, p, rank, nullptr, 0, nullptr) + mbcg_log_bytes(op, p, maxiter) + 256;
+}
+
+int mfx_mbcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n, int64_t p, const void* precond_lt,
+                   int64_t rank, const void* precond_minv, const void* precond_shift, int64_t maxiter, int64_t miniter,
+                   double atol, double rtol, int adaptive, void* x, void* r, void* num_steps, void* w0, void* tdiag,
+                   void* toff, void* rz0, void* depth, void* ws, int64_t ws_bytes, void* stream) {
+  MFX_REQUIRE(op && b && x && r, MFX_ERR_INVALID, "mfx_mbcg_solve: null argument");
+  MFX_REQUIRE(tdiag && toff && rz0 && depth, MFX_ERR_INVALID, "mfx_mbcg_solve: tdiag, toff, rz0 and depth are required");
+  MFX_REQUIRE(op->n == n && n >= 1 && p >= 1 && ldb >= n, MFX_ERR_INVALID, "mfx_mbcg_solve: bad sizes n=%lld p=%lld ldb=%lld",
+              (long long)n, (long long)p, (long long)ldb);
+  MFX_REQUIRE(maxiter >= 1 && miniter >= 0, MFX_ERR_INVALID, "mfx_mbcg_solve: maxiter %lld < 1 or negative miniter",
+              (long long)maxiter);
+  MFX_REQUIRE(maxiter < ((int64_t)1 << 30), MFX_ERR_UNSUPPORTED, "mfx_mbcg_solve: maxiter %lld too large", (long long)maxiter);
+  MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
+  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
+  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "mfx_mbcg_solve: no row block (nrows > 0): mBCG is not row-sharded");
+  MFX_CHECK_KERNEL_FN(op);
+  Precond pc{precond_lt, precond_minv, precond_shift, rank};
+  if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
+  CgWs w;
+  const int64_t base = ws ? cg_carve(op, n, p, precond_lt ? rank : 0, ws, ws_bytes, &w) : 0;
+  MFX_REQUIRE(ws && base + mbcg_log_bytes(op, p, maxiter) <= ws_bytes, MFX_ERR_WORKSPACE,
+              "mfx_mbcg_solve: workspace too small (mfx_mbcg_workspace_bytes)");
+  void* logs = static_cast<char*>(ws) + base;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PrepScope prep_scope;
+  if (op->dtype == MFX_F32)
+    return mbcg_t<float>(op, (const float*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
+                         (float*)x, (float*)r, (int64_t*)num_steps, (float*)w0, (float*)tdiag, (float*)toff, (float*)rz0,
+                         (int64_t*)depth, w, logs, s);
+  return mbcg_t<double>(op, (const double*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
+                        (double*)x, (double*)r, (int64_t*)num_steps, (double*)w0, (double*)tdiag, (double*)toff, (double*)rz0,
+                        (int64_t*)depth, w, logs, s);
+}
+
+int mfx_precond_sample(int dtype, int64_t n, int64_t rank, const void* lt, const void* shift, uint64_t seed,
+                       int64_t first_probe, int64_t p, void* out, void* stream) {
+  MFX_REQUIRE(out && n >= 1 && p >= 1 && rank >= 0, MFX_ERR_INVALID, "mfx_precond_sample: bad arguments");
+  MFX_REQUIRE(dtype == MFX_F32 || dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
+  MFX_REQUIRE(rank == 0 || (lt && shift), MFX_ERR_INVALID, "mfx_precond_sample: rank > 0 needs lt and shift");
+  MFX_REQUIRE(rank <= 1024, MFX_ERR_UNSUPPORTED, "preconditioner rank %lld > 1024", (long long)rank);
+  MFX_REQUIRE(p <= (int64_t)65535 * kSampleProbes, MFX_ERR_UNSUPPORTED, "too many probes per call");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int64_t gx = (n + 255) / 256;
+  if (gx > 2048) gx = 2048;
+  const dim3 grid((unsigned)gx, (unsigned)((p + kSampleProbes - 1) / kSampleProbes));
+  const size_t sh = (size_t)kSampleProbes * rank * dtype_size(dtype);
+  if (dtype == MFX_F32)
+    k_precond_sample<float><<<grid, 256, sh, s>>>(seed, first_probe, p, n, (int)rank, (const float*)lt, (const float*)shift,
+                                                  (float*)out);
+  else
+    k_precond_sample<double><<<grid, 256, sh, s>>>(seed, first_probe, p, n, (int)rank, (const double*)lt,
+                                                   (const double*)shift, (double*)out);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
 }
 
 static int64_t pcg_shard_rows(const mfx_comm* cm, int64_t n) {

@@ -270,6 +270,22 @@ template <typename T>
 struct VecWidth {
   static constexpr int value = 16 / sizeof(T);
 };
+
+// ---- counter-based +-1 probes (mfx_rademacher, mfx_precond_sample) -----------------------------
+// element j of probe b depends only on (seed, b, j): one key per probe, one splitmix64 step per element
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint64_t rademacher_key(uint64_t seed, int64_t probe) {
+  return splitmix64(seed ^ ((uint64_t)probe * 0xD1342543DE82EF95ull));
+}
+template <typename T>
+__device__ __forceinline__ T rademacher_sign(uint64_t key, int64_t j) {
+  return (splitmix64(key + (uint64_t)j) >> 63) ? T(1) : T(-1);
+}
 #endif
 
 }  // namespace mfx

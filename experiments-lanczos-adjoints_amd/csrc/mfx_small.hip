@@ -152,21 +152,12 @@ __global__ __launch_bounds__(64) void k_quadform_bwd(const T* __restrict__ evals
   }
 }
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 template <typename T>
 __global__ void k_rademacher(uint64_t seed, int64_t first_probe, int64_t n, T* __restrict__ out) {
   const int64_t b = blockIdx.y;
-  const uint64_t key = splitmix64(seed ^ ((uint64_t)(first_probe + b) * 0xD1342543DE82EF95ull));
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t bits = splitmix64(key + (uint64_t)i);
-    out[b * n + i] = (bits >> 63) ? T(1) : T(-1);
-  }
+  const uint64_t key = rademacher_key(seed, first_probe + b);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[b * n + i] = rademacher_sign<T>(key, i);
 }
 
 constexpr int kSmallLdsDepth = 120;   // up to here the k x k work matrices of the two kernels above live in LDS

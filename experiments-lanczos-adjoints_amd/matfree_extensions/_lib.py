@@ -160,6 +160,13 @@ SYMBOLS = {
     ),
     "mfx_pcg_solve_reortho": (_I, [_OPP, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _P]),
     "mfx_precond_apply": (_I, [_I, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "mfx_mbcg_workspace_bytes": (_I64, [_OPP, _I64, _I64, _I64, _I64]),
+    "mfx_mbcg_solve": (
+        _I,
+        [_OPP, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _I64, C.c_double, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+         _I64, _P],
+    ),
+    "mfx_precond_sample": (_I, [_I, _I64, _I64, _P, _P, C.c_uint64, _I64, _I64, _P, _P]),
     "mfx_partial_cholesky": (_I, [_OPP, _I64, _I, _I, _P, _P, _P, _P, _I64, _P]),
     "mfx_gram_cross_workspace_bytes": (_I64, [_OPP, _I64]),
     "mfx_gram_cross_apply": (_I, [_OPP, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),

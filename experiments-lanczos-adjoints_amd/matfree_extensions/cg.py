@@ -15,7 +15,15 @@ here -- and the loop runs in ``mfx_pcg_solve_sharded`` (not for the re-orthogona
 
 Differentiation is the rule of ``jax.lax.custom_linear_solve(..., symmetric=True)`` (cg.py:23-25): the cotangent of the
 right-hand side is another solve with the same solver, the cotangent of the operator's parameters is the parameter sweep
-with (-lambda, x); nothing flows through the preconditioner or the info dict.  ``cg_fixed_step_reortho`` /
+with (-lambda, x); nothing flows through the preconditioner or the info dict.
+
+    mbcg_fixed_step(num_matvecs)(A, b, P)        mbcg_adaptive(atol=, rtol=, maxiter=, miniter=)(A, b, P)
+        -> (x, info)   info = {"residual_abs", "num_steps", "tridiag": (diag, offdiag), "rz0", "depth", "w0"}
+
+are the same solves (``x``, the residual and the step counts are ``pcg_*``'s bit for bit, ``x`` differentiable in the same way)
+through ``mfx_mbcg_solve``, which also keeps the CG coefficients: per right-hand side the Lanczos tridiagonal of the preconditioned
+system, padded with an identity block beyond ``depth`` (include/mfx.h).  ``util.gp_util.krylov_logdet_mbcg`` / ``logpdf_mbcg`` turn
+them into the log-determinant and the GP log-likelihood.  Not row-sharded.  ``cg_fixed_step_reortho`` /
 ``pcg_fixed_step_reortho`` (cg.py:140-219; "needs more work" according to the reference's own test) are reproduced as they are.
 """
 
@@ -89,8 +97,49 @@ def pcg_adaptive(*, atol: float, rtol, maxiter: int, miniter: int = 0):
     return pcg
 
 
+def mbcg_fixed_step(num_matvecs: int, /):
+    """pcg_fixed_step that keeps its coefficients (modified batched CG): see the module docstring."""
+    cfg = {"maxiter": int(num_matvecs), "miniter": 0, "atol": 1.0, "rtol": 0.0, "adaptive": False, "mbcg": True}
+
+    def mbcg(A, b, P):
+        return _mbcg(A, b, P, cfg)
+
+    mbcg.cfg = cfg
+    return mbcg
+
+
+def mbcg_adaptive(*, atol: float, rtol, maxiter: int, miniter: int = 0):
+    """pcg_adaptive that keeps its coefficients (modified batched CG): see the module docstring."""
+    cfg = {"maxiter": int(maxiter), "miniter": int(miniter), "atol": float(atol), "rtol": float(rtol), "adaptive": True,
+           "mbcg": True}
+
+    def mbcg(A, b, P):
+        return _mbcg(A, b, P, cfg)
+
+    mbcg.cfg = cfg
+    return mbcg
+
+
+def _mbcg(A, b, P, cfg):
+    x, r, steps, diag, off, rz0, depth, w0 = _solve(A, b, P, cfg)
+    return x, {"residual_abs": r, "num_steps": steps, "tridiag": (diag, off), "rz0": rz0, "depth": depth, "w0": w0}
+
+
+def _check_mbcg(op, P, cfg):
+    if cfg["maxiter"] < 1:
+        raise ValueError("mBCG needs at least one iteration (num_matvecs / maxiter >= 1)")
+    if isinstance(op, RowShardedOp):
+        raise NotImplementedError("mBCG is not row-sharded in the MI355X build (mfx_mbcg_solve has no sharded form); shard the "
+                                  "probes instead of the rows")
+    if P is not None and not isinstance(P, BoundPreconditioner):
+        raise TypeError("P must be None or low_rank.Preconditioner.bind(s): the PCG loop runs inside libmfx and "
+                        "cannot call back into an arbitrary Python preconditioner")
+
+
 def _solve(A, b, P, cfg):
     op, bound = as_operator(A)
+    if cfg.get("mbcg", False):
+        _check_mbcg(op, P, cfg)
     if isinstance(op, RowShardedOp) and cfg.get("reortho", False):
         raise NotImplementedError("the re-orthogonalising PCG variant is not row-sharded in the MI355X build")
     params = tuple(bound) if bound is not None else ()
@@ -100,10 +149,10 @@ def _solve(A, b, P, cfg):
     batched = b.dim() == 2
     B = b if batched else b[None]
     cparams = op.constrain(*params)
-    x, r, steps = _PcgFn.apply(op, cfg, P, B, *cparams)  # steps: int64 (p,), or the basis Q (p, m, n) when re-orthogonalising
+    out = _PcgFn.apply(op, cfg, P, B, *cparams)  # (x, r, steps[, mBCG extras]); steps: int64 (p,), or the basis Q (p, m, n) when re-orthogonalising
     if not batched:
-        return x[0], r[0], steps[0]
-    return x, r, steps
+        return tuple(t[0] for t in out)
+    return out
 
 
 def _run_sharded(sop, cfg, P, B, cparams):
@@ -183,6 +232,8 @@ def _run(op, cfg, P, B, cparams):
             raise keep[1][0]
         _lib.check(rc)
         return x, r, Q
+    if cfg.get("mbcg", False):
+        return _run_mbcg(lib, desc, cfg, B, (rank, lt, minv, shift), x, r, keep, reg if keep is not None else None)
     steps = torch.empty((p,), dtype=torch.int64, device=dev)
     with _lib.busy(ws):
         rc = lib.mfx_pcg_solve(C.byref(desc), _lib.ptr(B), n, n, p, _lib.ptr(lt), rank, _lib.ptr(minv), _lib.ptr(shift),
@@ -194,20 +245,47 @@ def _run(op, cfg, P, B, cparams):
     return x, r, steps
 
 
+def _run_mbcg(lib, desc, cfg, B, precond, x, r, keep, reg):
+    """One mfx_mbcg_solve call -> (x, r, steps, tdiag, toff, rz0, depth, w0); the padded tridiagonals are (p, maxiter) each."""
+    p, n = B.shape
+    dt, dev = B.dtype, B.device
+    rank, lt, minv, shift = precond
+    m = cfg["maxiter"]
+    ws = _lib.scratch(int(lib.mfx_mbcg_workspace_bytes(C.byref(desc), n, p, rank, m)), dev)
+    if reg is not None:
+        reg.add_bytes(ws, dt)
+    steps = torch.empty((p,), dtype=torch.int64, device=dev)
+    depth = torch.empty((p,), dtype=torch.int64, device=dev)
+    tdiag = torch.empty((p, m), dtype=dt, device=dev)
+    toff = torch.empty((p, m), dtype=dt, device=dev)
+    rz0 = torch.empty((p,), dtype=dt, device=dev)
+    w0 = torch.empty_like(B)
+    with _lib.busy(ws):
+        rc = lib.mfx_mbcg_solve(C.byref(desc), _lib.ptr(B), n, n, p, _lib.ptr(lt), rank, _lib.ptr(minv), _lib.ptr(shift), m,
+                                cfg["miniter"], cfg["atol"], cfg["rtol"], int(cfg["adaptive"]), _lib.ptr(x), _lib.ptr(r),
+                                _lib.ptr(steps), _lib.ptr(w0), _lib.ptr(tdiag), _lib.ptr(toff), _lib.ptr(rz0), _lib.ptr(depth),
+                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    if keep is not None and keep[1]:
+        raise keep[1][0]
+    _lib.check(rc)
+    return x, r, steps, tdiag, toff, rz0, depth, w0
+
+
 class _PcgFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, op, cfg, P, B, *cparams):
         tensors = [q for q in cparams if torch.is_tensor(q)]
         _lib.require_device(B, *tensors)
-        x, r, steps = _run(op, cfg, P, B, cparams)
-        ctx.op, ctx.cfg, ctx.P = op, cfg, P
+        x, *rest = _run(op, cfg, P, B, cparams)
+        ctx.op, ctx.P = op, P
+        ctx.cfg = {k: v for k, v in cfg.items() if k != "mbcg"}  # the transpose solve needs no coefficients
         ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
         ctx.save_for_backward(x, *tensors)
-        ctx.mark_non_differentiable(r, steps)
-        return x, r, steps
+        ctx.mark_non_differentiable(*rest)
+        return (x, *rest)
 
     @staticmethod
-    def backward(ctx, dx, _dr, _dsteps):
+    def backward(ctx, dx, *_unused):
         x, *tensors = ctx.saved_tensors
         it = iter(tensors)
         cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)

@@ -116,6 +116,29 @@ class Preconditioner:
         minv = torch.cholesky_inverse(torch.linalg.cholesky(cap))
         return minv.to(self.lt.dtype).contiguous(), s.contiguous()
 
+    def logdet(self, s):
+        """log det(s I + L L^T) = (n - rank) log s + log det(s I_r + L^T L) (the matrix determinant lemma), from the fp64 Gram matrix
+        that ``minv`` caches -> fp64 scalar on the device of L.  Not differentiable (``_NoGrad`` convention)."""
+        if self._gram is None:
+            self._gram = (self.lt @ self.lt.t()).double()
+        s = s.detach() if torch.is_tensor(s) else torch.tensor(float(s), dtype=torch.float64)  # (a Python float is not rounded to fp32)
+        s = s.to(self.lt.device).double().reshape(())
+        cap = self._gram + s * torch.eye(self.rank, dtype=torch.float64, device=self.lt.device)
+        return (self.n - self.rank) * torch.log(s) + 2.0 * torch.log(torch.diagonal(torch.linalg.cholesky(cap))).sum()
+
+    def sample(self, seed, num, s, first_probe=0):
+        """``num`` probes z (num, n) with E[z z^T] = s I + L L^T exactly: z = sqrt(s) e_1 + L e_2 with (e_1, e_2) the +-1 probe of
+        length n + rank that ``mfx_rademacher`` draws for (seed, first_probe + b) -- one fused kernel (``mfx_precond_sample``).
+        Shards with different ``first_probe`` tile one probe matrix."""
+        _lib.require_device(self.lt)
+        dt, dev = self.lt.dtype, self.lt.device
+        sdev = torch.as_tensor(s, dtype=dt, device=dev).detach().reshape(1).contiguous()
+        out = torch.empty((int(num), self.n), dtype=dt, device=dev)
+        _lib.check(_lib.get().mfx_precond_sample(_lib.dtype_code(dt), self.n, self.rank, _lib.ptr(self.lt), _lib.ptr(sdev),
+                                                 int(seed) & ((1 << 64) - 1), int(first_probe), int(num), _lib.ptr(out),
+                                                 _lib.stream_ptr(dev)))
+        return out
+
     def _apply(self, v, s):
         _lib.require_device(v)
         V = (v if v.dim() == 2 else v[None]).detach().contiguous()
@@ -149,6 +172,12 @@ class BoundPreconditioner:
 
     def __call__(self, v):
         return self.pre(v, self.s)
+
+    def logdet(self):
+        return self.pre.logdet(self.s)
+
+    def sample(self, seed, num, first_probe=0):
+        return self.pre.sample(seed, num, self.s, first_probe=first_probe)
 
 
 def preconditioner(cholesky, /):

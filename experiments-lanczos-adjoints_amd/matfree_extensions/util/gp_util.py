@@ -11,10 +11,11 @@ from __future__ import annotations
 
 import torch
 
+import ctypes as C
 import math
 
-from .. import hutchinson, lanczos, low_rank
-from ..operators import RbfGramOp, softplus
+from .. import _lib, cg, hutchinson, lanczos, low_rank
+from ..operators import CallbackOp, RbfGramOp, as_operator, softplus
 
 
 def constraint_greater_than(minval, /):
@@ -331,6 +332,168 @@ def logpdf_krylov_p(solve_p, logdet):
         info = {"logdet": info_logdet, "solve": info_solve}
         (n,) = mean.shape
         return -logdet_ - 0.5 * mahalanobis - n / 2 * math.log(2 * math.pi), info
+
+    return logpdf
+
+
+# ------------------------------------------------------------------------------------------------
+# modified batched CG (mBCG): log-determinant and log-likelihood from ONE preconditioned solve  
+# ------------------------------------------------------------------------------------------------
+def _mbcg_config(solve_mbcg):
+    cfg = getattr(solve_mbcg, "cfg", None)
+    if not (isinstance(cfg, dict) and cfg.get("mbcg", False)):
+        raise TypeError("solve_mbcg must come from cg.mbcg_fixed_step / cg.mbcg_adaptive (the solver that keeps its coefficients)")
+    return cfg
+
+
+def _mbcg_probes(op, cparams, key, P, num_probes):
+    """(num_probes, n) probes with covariance M: an explicit tensor as it is (the parity interface of ``hutchinson``), else
+    ``P.sample`` (M = s I + L L^T), else plain +-1 (M = I); ``key`` an int seed or (seed, first_probe)."""
+    if torch.is_tensor(key):
+        if key.dim() != 2 or key.shape[0] != num_probes:
+            raise ValueError(f"explicit probes {tuple(key.shape)} must be ({num_probes}, n)")
+        return key.detach()
+    seed, first = key if isinstance(key, tuple) else (key, 0)
+    if P is not None:
+        return P.sample(seed, num_probes, first_probe=first)
+    if isinstance(op, CallbackOp):
+        raise TypeError("a callable operator has no size: pass explicit probes (num_probes, n) as the key")
+    ref = next(q for q in cparams if torch.is_tensor(q))
+    like = torch.empty(op.size(*cparams), dtype=ref.dtype, device=ref.device)
+    return hutchinson.sampler_rademacher(like, num=num_probes)((seed, first))
+
+
+def _mbcg_quadrature(tdiag, toff, rz0, kmax=None):
+    """rz0_b e1^T log(T_b) e1 per right-hand side, in fp64, for the padded tridiagonals of ``mfx_mbcg_solve`` (the identity block
+    beyond a column's depth has log 1 = 0 and no weight on e1).  ``kmax``: only the leading kmax x kmax block can be live."""
+    p, k = tdiag.shape
+    if kmax is not None and kmax < k:
+        k = max(int(kmax), 1)
+        tdiag, toff = tdiag[:, :k], toff[:, :k]
+    dt, dev = tdiag.dtype, tdiag.device
+    # beyond depth 120 the eigensolver accumulates its rotations in the fp64 output itself (include/mfx.h): fp32 problems are cast
+    et = torch.float64 if k > 120 else dt
+    diag_e, off_e = tdiag.to(et).contiguous(), toff.to(et).contiguous()
+    evals = torch.empty((p, k), dtype=et, device=dev)
+    evecs = torch.empty((p, k, k), dtype=et, device=dev)
+    _lib.check(_lib.get().mfx_tridiag_eigh(_lib.ptr(diag_e), _lib.ptr(off_e) if k > 1 else None, k, p, k, _lib.dtype_code(et),
+                                           _lib.ptr(evals), _lib.ptr(evecs), _lib.stream_ptr(dev)))
+    weights = evecs[:, 0, :].double() ** 2
+    return rz0.double() * (weights * torch.log(evals.double())).sum(-1)
+
+
+def _mbcg_kmax(cfg, steps):
+    # the adaptive loop has synchronised with the host every iteration anyway: trim the eigen-problem to the steps taken
+    return int(steps.max()) if cfg["adaptive"] else None
+
+
+def krylov_logdet_mbcg(solve_mbcg, /, *, num_probes: int):
+    """logdet(A, key, P=None) -> (value, info): the log-determinant estimate of modified batched CG (the estimator of GPyTorch
+    that the reference's optim_logml_gpytorch_adaptive.py trains with).  One ``solve_mbcg`` (cg.mbcg_fixed_step / cg.mbcg_adaptive)
+    on ``num_probes`` probes z_b with covariance M (the preconditioner ``P = pre.bind(s)``, M = s I + L L^T; M = I for None):
+
+        value = logdet M + (1 / p) sum_b rz0_b e1^T log(T_b) e1,
+
+    T_b the Lanczos tridiagonal of M^-1/2 A M^-1/2 started at M^-1/2 z_b that the CG coefficients form, rz0_b = z_b^T M^-1 z_b.
+    ``key``: int seed, (seed, first_probe), or the probes themselves.  The value carries no gradient: ``logpdf_mbcg`` owns it."""
+    cfg = _mbcg_config(solve_mbcg)
+    num_probes = int(num_probes)
+    if num_probes < 1:
+        raise ValueError(f"num_probes must be >= 1, got {num_probes}")
+
+    def logdet(A, /, key, P=None):
+        op, bound = as_operator(A)
+        cg._check_mbcg(op, P, cfg)
+        with torch.no_grad():
+            cparams = op.constrain(*(tuple(bound) if bound is not None else ()))
+            z = _mbcg_probes(op, cparams, key, P, num_probes)
+            _x, info = solve_mbcg(A, z, P)
+            quad = _mbcg_quadrature(*info["tridiag"], info["rz0"], _mbcg_kmax(cfg, info["num_steps"]))
+            value = quad.mean()
+            if P is not None:
+                value = value + P.logdet()
+            std = quad.std(unbiased=False)
+        return value.to(z.dtype), {"std_abs": std, "std_rel": std / value.abs(), "solve": info}
+
+    return logdet
+
+
+class _MbcgLogpdfFn(torch.autograd.Function):
+    """value = -1/2 r^T A^-1 r - 1/2 logdet A - n/2 log 2 pi from ONE mfx_mbcg_solve on [r ; z_1 .. z_p]."""
+
+    @staticmethod
+    def forward(ctx, op, cfg, P, z, y, mean, *cparams):
+        tensors = [q for q in cparams if torch.is_tensor(q)]
+        _lib.require_device(y, z, *tensors)
+        resid = (y - mean).to(z.dtype)
+        n, p = resid.shape[0], z.shape[0]
+        B = torch.cat([resid[None], z])
+        x, r, steps, tdiag, toff, rz0, depth, w0 = cg._run(op, cfg, P, B, cparams)
+        quad = _mbcg_quadrature(tdiag[1:], toff[1:], rz0[1:], _mbcg_kmax(cfg, steps[1:]))
+        logdet = quad.mean()
+        if P is not None:
+            logdet = logdet + P.logdet()
+        value = -0.5 * (resid.double() @ x[0].double()) - 0.5 * logdet - n / 2 * math.log(2 * math.pi)
+        ctx.op, ctx.p = op, p
+        ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
+        ctx.save_for_backward(x, w0, *tensors)
+        out = (r, steps, depth, logdet.to(z.dtype))
+        ctx.mark_non_differentiable(*out)
+        return (value.to(z.dtype), *out)
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        x, w0, *tensors = ctx.saved_tensors
+        it = iter(tensors)
+        cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)
+        op, p = ctx.op, ctx.p
+        if isinstance(op, CallbackOp):
+            raise NotImplementedError("logpdf_mbcg differentiates native operators only (the gradient is ONE mfx_op_vjp_params sweep, "
+                                      "which a Python callable does not have)")
+        n = x.shape[1]
+        alpha = x[:1]
+        # d/dtheta [1/2 alpha^T A alpha - 1/(2p) sum_b x_b^T A w_b]:  tr(A^-1 dA) ~ mean_b z_b^T M^-1 dA A^-1 z_b for E[z z^T] = M
+        L = torch.cat([0.5 * g * alpha, (-0.5 / p) * g * x[1:]]).contiguous()
+        R = torch.cat([alpha, w0[1:]]).contiguous()
+        desc = op.descriptor(cparams, x.dtype, n)
+        gstruct, grads = op.new_grads(*cparams)
+        ws = _lib.workspace(desc, n, 1, p + 1, x.device)
+        _lib.check(_lib.get().mfx_op_vjp_params(C.byref(desc), _lib.ptr(L), n, _lib.ptr(R), n, p + 1, C.byref(gstruct),
+                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+        galpha = g * alpha[0]  # d value / d y = -alpha, d value / d mean = +alpha  (r = y - mean)
+        return (None, None, None, None, -galpha, galpha, *grads)
+
+
+def logpdf_mbcg(solve_mbcg, /, *, num_probes: int):
+    """logpdf(y, key, *, mean, cov_matvec, P=None) -> (value, info): the Gaussian log-density by modified batched CG, usable under
+    both ``likelihood_pdf`` and ``likelihood_pdf_p`` (where ``logpdf_krylov[_p]`` runs an SLQ pass beside a separate solve).
+
+    ONE ``mfx_mbcg_solve`` on the num_probes + 1 right-hand sides [y - mean ; z_1 .. z_p], z_b probes with the preconditioner's
+    covariance M (``P.sample``; plain +-1 without P):
+        value = -1/2 r^T alpha - 1/2 logdet - n/2 log 2 pi,   r = y - mean,  alpha = A^-1 r,  logdet as ``krylov_logdet_mbcg``.
+    Backward, with x_b = A^-1 z_b and w_b = M^-1 z_b from the same solve: ONE parameter sweep (``mfx_op_vjp_params``, the input
+    gradient included when X.requires_grad) of  1/2 alpha^T dA alpha - 1/(2p) sum_b x_b^T dA w_b;  -alpha to y, +alpha to the mean.
+
+    The gradient of the log-determinant term is the TRACE ESTIMATOR tr(A^-1 dA) ~ mean_b x_b^T dA w_b (unbiased for any fixed M when
+    the solves have converged) -- it is NOT the derivative of the forward quadrature, so value and gradient are two estimates from
+    the same probes, not a function and its derivative (a finite-difference check of the value does not reproduce it).  Nothing flows
+    through the preconditioner (``low_rank._NoGrad`` convention).  Native operators only: a callable operator raises
+    NotImplementedError in backward.  ``key``: int seed, (seed, first_probe) or explicit probes (num_probes, n)."""
+    cfg = _mbcg_config(solve_mbcg)
+    num_probes = int(num_probes)
+    if num_probes < 1:
+        raise ValueError(f"num_probes must be >= 1, got {num_probes}")
+
+    def logpdf(y, key, *, mean, cov_matvec, P=None):
+        op, bound = as_operator(cov_matvec)
+        cg._check_mbcg(op, P, cfg)
+        cparams = op.constrain(*(tuple(bound) if bound is not None else ()))
+        with torch.no_grad():
+            z = _mbcg_probes(op, cparams, key, P, num_probes)
+        value, r, steps, depth, logdet = _MbcgLogpdfFn.apply(op, cfg, P, z, y, mean, *cparams)
+        solve = {"residual_abs": r[0], "num_steps": steps[0]}
+        return value, {"logdet": {"value": logdet, "depth": depth[1:], "num_steps": steps[1:], "residual_abs": r[1:]},
+                       "solve": solve}
 
     return logpdf
 

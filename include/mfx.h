@@ -391,6 +391,45 @@ int mfx_precond_apply(int dtype, int64_t n, int64_t rank, const void* lt, const 
                       const void* shift, const void* v, int64_t ldv, void* z, int64_t ldz, int64_t p,
                       void* ws, int64_t ws_bytes, void* stream);
 
+/* Modified batched CG (mBCG; Gardner et al. 2018, the estimator behind GPyTorch's marginal likelihood that
+ * optim_logml_gpytorch_adaptive.py trains with): mfx_pcg_solve that keeps the scalars of its own iteration, so that ONE
+ * preconditioned solve of [y - m, z_1 .. z_p] yields the Mahalanobis term (first column) and, from the probe columns, the Lanczos
+ * tridiagonals T_b of M^-1/2 A M^-1/2 started at M^-1/2 b, M = s I + L L^T the preconditioner (M = I without one):
+ *   b^T M^-1/2 log(M^-1/2 A M^-1/2) M^-1/2 b  ~  rz0_b e1^T log(T_b) e1,   logdet A = logdet M + E_z[that] for E[z z^T] = M.
+ * Arguments up to num_steps, the iteration and the outputs x, r, num_steps are mfx_pcg_solve's bit for bit (the same kernels in the
+ * same order; the two scalars are recorded by the thread that already holds them, no launch is added per iteration).  Then, with
+ * alpha_j = (r.z)_j / (p.Ap)_j and beta_j = (r.z)_{j+1} / (r.z)_j:
+ *   w0    (p, n) or NULL: M^-1 b, the first preconditioned residual (a copy of b without a preconditioner);
+ *   rz0   (p): r_0 . z_0 = b^T M^-1 b;
+ *   depth (p) int64: the number m_b of live steps.  Step j is live when j < num_steps[b], (r.z)_j > eps^2 and (p.Ap)_j > eps^2 (eps =
+ *         machine epsilon of the dtype: the threshold below which the loop's own divisions are switched off, cg.py:222-241) and every
+ *         earlier step is live;
+ *   tdiag, toff (p, maxiter) in the operator's dtype:  tdiag[j] = 1 / alpha_j + (j > 0 ? beta_{j-1} / alpha_{j-1} : 0) for j < m_b,
+ *         toff[j] = sqrt(beta_j) / alpha_j for j < m_b - 1; every other entry is exactly tdiag = 1, toff = 0 -- an identity block
+ *         that decouples (log 1 = 0, no weight on e1), so e1^T log(T) e1 of the padded maxiter x maxiter matrix is that of the live
+ *         block, and 0 for depth 0.  mfx_tridiag_eigh takes (tdiag, toff, ldbeta = maxiter) as they are.
+ * One small kernel after the loop builds tdiag / toff / rz0 / depth.  The gradient of the log-determinant estimate is the trace
+ * estimator tr(A^-1 dA) ~ mean_b x_b^T dA w0_b (x_b = A^-1 z_b): one mfx_op_vjp_params sweep over the solves.
+ * Refused before any launch, with mfx_pcg_solve's codes: NULL tdiag, toff, rz0 or depth, maxiter < 1 (MFX_ERR_INVALID); a row
+ * block, nrows > 0 (MFX_ERR_UNSUPPORTED: there is no sharded form); a short workspace (MFX_ERR_WORKSPACE).
+ * Workspace: mfx_mbcg_workspace_bytes (mfx_pcg_workspace_bytes' vectors plus 2 p (maxiter + 1) scalars; -1 on a bad argument). */
+int64_t mfx_mbcg_workspace_bytes(const mfx_operator* op, int64_t n, int64_t p, int64_t rank, int64_t maxiter);
+int mfx_mbcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n, int64_t p,
+                   const void* precond_lt, int64_t rank, const void* precond_minv,
+                   const void* precond_shift, int64_t maxiter, int64_t miniter, double atol, double rtol,
+                   int adaptive, void* x, void* r, void* num_steps, void* w0, void* tdiag, void* toff,
+                   void* rz0, void* depth, void* ws, int64_t ws_bytes, void* stream);
+
+/* Probes with the preconditioner's covariance, for mfx_mbcg_solve:  out (p, n),
+ *   out[b][i] = sqrt(s) eps(b, i) + sum_{c < rank} Lt[c][i] eps(b, n + c),
+ * eps(b, j) = the element mfx_rademacher produces for (seed, first_probe + b, j) in a probe of length n + rank, so E[z z^T] =
+ * s I + L L^T exactly and probe shards tile one global probe matrix.  lt (rank, n) row-major and the device scalar shift = s as in
+ * mfx_precond_apply.  rank = 0 with shift = NULL: plain +-1 probes, bit for bit mfx_rademacher's (rank = 0 with a shift: scaled by
+ * sqrt(s)).  One fused kernel generated from the counters: no (p, n + rank) buffer, no workspace.
+ * MFX_ERR_INVALID: NULL out, n < 1, p < 1, rank < 0, rank > 0 without lt or shift, unknown dtype; MFX_ERR_UNSUPPORTED: rank > 1024. */
+int mfx_precond_sample(int dtype, int64_t n, int64_t rank, const void* lt, const void* shift, uint64_t seed,
+                       int64_t first_probe, int64_t p, void* out, void* stream);
+
 /* Partial Cholesky factor of a dense or kernel-Gram operator, element access instead of the reference's
  * lazy_kernel(i, j) callable (low_rank.py:63-120 without pivoting, :123-228 with pivoting).  Output Lt (rank, n)
  * = the reference's factor transposed, already in the original row order (low_rank.py:227-228); pivots int64
