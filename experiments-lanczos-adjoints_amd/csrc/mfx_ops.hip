@@ -209,12 +209,89 @@ __global__ __launch_bounds__(256) void k_rbf_apply(const T* __restrict__ xs, con
   }
 }
 
-// Parameter-gradient sweep (generic VALU path): workgroup = 256 rows i, walks all j in tiles of 16,
-// S_ij = sum_bt L[bt][i] R[bt][j] accumulated in registers, then W = S o K and the per-parameter
-// reductions.  Per-workgroup partials (double) -> k_rbf_grad_final (deterministic).
+// tiles of the gradient sweeps: columns per tile, batch entries staged at a time
 constexpr int kGradTJ = 16;
 constexpr int kGradBC = 32;
 
+// Weight sources of the cross sweeps (k_rbf_cross_grad[_wide]'s Src, further down): tile() gives S of one owner row i against
+// the columns j0 .. j0 + TJ (columns >= je as 0), called by every thread of the workgroup at the top of a column tile.  rj is the
+// caller's LDS staging tile; only the factored source uses it.
+//
+// Factored, S_ij = sum_b L_b[i] R_b[j] with L (batch, owners), R (batch, columns): the R slices of kGradBC batch entries at a
+// time through rj, S accumulated in registers.  Waves without a live row (wave_live false) only stage.
+template <typename T>
+struct FactoredSrc {
+  const T* L;
+  int64_t ldl;
+  const T* R;
+  int64_t ldr, batch;
+  static constexpr int kDotsTag = 1;
+  template <int TJ>
+  __device__ __forceinline__ void tile(bool live, bool wave_live, int64_t i, int64_t j0, int64_t je, T (*rj)[TJ], T (&S)[TJ]) const {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int jj = 0; jj < TJ; ++jj) S[jj] = T(0);
+    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
+      __syncthreads();
+      for (int t = tid; t < kGradBC * TJ; t += 256) {
+        const int q = t / TJ, jj = t % TJ;
+        rj[q][jj] = (bt0 + q < batch && j0 + jj < je) ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
+      }
+      __syncthreads();
+      if (!wave_live) continue;
+      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
+      for (int q = 0; q < qmax; ++q) {
+        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
+#pragma unroll
+        for (int jj = 0; jj < TJ; ++jj) S[jj] += l * rj[q][jj];
+      }
+    }
+  }
+};
+
+// Dense, S (m, n) with leading dimension lds given as it is (the predictive variance's S_aj = -2 vbar_a W_aj is diagonal in any
+// batch, so the factored form would need batch = m and an m-long inner loop per entry).  TRANS = false, owner = a row of S: the
+// thread's own TJ consecutive entries, no other thread reads them, so they go straight to registers as 16-byte vector loads (vec:
+// S and lds keep every row's tile 16-byte aligned; the tile is whole) -- an LDS round trip would only add a write, a barrier and a
+// read.  Otherwise, and for the tail tile, scalar loads.  TRANS = true, owner = a column of S: entry (j, i), consecutive owners in
+// consecutive lanes, coalesced.  No barrier: the loads are in flight while the caller stages the column points.
+template <typename T, bool TRANS>
+struct DenseSrc {
+  const T* S;
+  int64_t lds;
+  int vec;
+  static constexpr int kDotsTag = 2;
+  template <int TJ>
+  __device__ __forceinline__ void tile(bool live, bool, int64_t i, int64_t j0, int64_t je, T (*)[TJ], T (&s)[TJ]) const {
+#pragma unroll
+    for (int jj = 0; jj < TJ; ++jj) s[jj] = T(0);
+    if (!live) return;
+    if (TRANS) {
+#pragma unroll
+      for (int jj = 0; jj < TJ; ++jj)
+        if (j0 + jj < je) s[jj] = S[(j0 + jj) * lds + i];
+    } else {
+      const T* row = S + i * lds + j0;
+      if (vec && j0 + TJ <= je) {
+        constexpr int V = 16 / (int)sizeof(T);
+#pragma unroll
+        for (int u = 0; u < TJ / V; ++u) {
+          const Pack<T, V> p = load_pack<T, V>(row + u * V);
+#pragma unroll
+          for (int e = 0; e < V; ++e) s[u * V + e] = p.v[e];
+        }
+      } else {
+#pragma unroll
+        for (int jj = 0; jj < TJ; ++jj)
+          if (j0 + jj < je) s[jj] = row[jj];
+      }
+    }
+  }
+};
+
+// Parameter-gradient sweep (generic VALU path): workgroup = 256 rows i, walks all j in tiles of 16,
+// S_ij = sum_bt L[bt][i] R[bt][j] accumulated in registers, then W = S o K and the per-parameter
+// reductions.  Per-workgroup partials (double) -> k_rbf_grad_final (deterministic).
 template <typename T, int DPAD>
 __global__ __launch_bounds__(256) void k_rbf_grad(const T* __restrict__ xs, const T* __restrict__ sq, int64_t n,
                                                   int ard, int kind, const T* __restrict__ L, int64_t ldl,
@@ -310,7 +387,8 @@ constexpr int kWideGJ = 16;   // columns per tile, parameter sweep
 constexpr int kWideGC = 32;   // ARD dimensions a workgroup of the sweep accumulates (blockIdx.y selects them)
 
 // dot[jj] += <x_i, x_j> over all chunks of the padded d axis; TJ columns j0 .. j0 + TJ.  TAG only separates instantiations: the
-// cross sweep takes its own (sharing k_rbf_grad_wide's <double, 16> reordered two registers of that kernel's code)
+// cross sweep takes its own per weight source, Src::kDotsTag (sharing k_rbf_grad_wide's <double, 16> reordered two registers of
+// that kernel's code)
 template <typename T, int TJ, int TAG = 0>
 __device__ __forceinline__ void wide_dots(const T* __restrict__ xs, int64_t n, int dpad, const T* __restrict__ xrow, int64_t ic,
                                           int64_t j0, T (*xiT)[256], T (*xjT)[TJ], T (&dot)[TJ]) {
@@ -692,17 +770,16 @@ __global__ __launch_bounds__(256) void k_rbf_grad_final(const double* __restrict
 // workgroup's l / s sums go to partial (splits x blocks, DPAD + 2) in k_rbf_grad_final's layout (noise slot 0).  No atomics
 // anywhere: bitwise reproducible.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int DPAD, bool THETA, bool GX>
+template <typename T, int DPAD, bool THETA, bool GX, typename Src>
 __global__ __launch_bounds__(256) void k_rbf_cross_grad(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
                                                         const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
-                                                        int64_t chunk, int d, int ard, int kind, const T* __restrict__ L,
-                                                        int64_t ldl, const T* __restrict__ R, int64_t ldr, int64_t batch,
+                                                        int64_t chunk, int d, int ard, int kind, const Src src,
                                                         const T* __restrict__ ls, const T* __restrict__ outputscale,
                                                         T* __restrict__ go, double* __restrict__ gpart,
                                                         double* __restrict__ partial) {
   __shared__ __attribute__((aligned(16))) T xj[kGradTJ][DPAD];
   __shared__ T sqj[kGradTJ];
-  __shared__ T rj[kGradBC][kGradTJ];
+  __shared__ T rj[kGradBC][kGradTJ];  // (the factored source's staging; unused, and not allocated, with a dense source)
   __shared__ double red[4][DPAD + 2];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int64_t i = (int64_t)blockIdx.x * 256 + tid;
@@ -723,23 +800,7 @@ __global__ __launch_bounds__(256) void k_rbf_cross_grad(const T* __restrict__ xo
   for (int c = 0; c < DPAD; ++c) gx[c] = 0.0;
   for (int64_t j0 = jb; j0 < je; j0 += kGradTJ) {
     T S[kGradTJ];
-#pragma unroll
-    for (int jj = 0; jj < kGradTJ; ++jj) S[jj] = T(0);
-    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
-      __syncthreads();
-      for (int t = tid; t < kGradBC * kGradTJ; t += 256) {
-        const int q = t / kGradTJ, jj = t % kGradTJ;
-        rj[q][jj] = (bt0 + q < batch && j0 + jj < je) ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
-      }
-      __syncthreads();
-      if (!wave_live) continue;
-      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
-      for (int q = 0; q < qmax; ++q) {
-        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
-#pragma unroll
-        for (int jj = 0; jj < kGradTJ; ++jj) S[jj] += l * rj[q][jj];
-      }
-    }
+    src.template tile<kGradTJ>(live, wave_live, i, j0, je, rj, S);
     __syncthreads();
     for (int t = tid; t < kGradTJ * DPAD; t += 256) {
       const int64_t gi = j0 * DPAD + t;
@@ -803,20 +864,19 @@ __global__ __launch_bounds__(256) void k_rbf_cross_grad(const T* __restrict__ xo
 // the cross sweep for wide inputs (d > 32): as k_rbf_cross_grad with the distances of wide_dots; blockIdx.y selects kWideGC of
 // the row's d sums (ARD lengthscale and input gradient; a scalar lengthscale without input gradient has one selection, as in
 // k_rbf_grad_wide), blockIdx.z is the column split
-template <typename T, bool THETA, bool GX>
+template <typename T, bool THETA, bool GX, typename Src>
 __global__ __launch_bounds__(256) void k_rbf_cross_grad_wide(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
                                                              const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
-                                                             int64_t chunk, int dpad, int d, int ard, int kind,
-                                                             const T* __restrict__ L, int64_t ldl, const T* __restrict__ R,
-                                                             int64_t ldr, int64_t batch, const T* __restrict__ ls,
-                                                             const T* __restrict__ outputscale, T* __restrict__ go,
-                                                             double* __restrict__ gpart, double* __restrict__ partial) {
+                                                             int64_t chunk, int dpad, int d, int ard, int kind, const Src src,
+                                                             const T* __restrict__ ls, const T* __restrict__ outputscale,
+                                                             T* __restrict__ go, double* __restrict__ gpart,
+                                                             double* __restrict__ partial) {
   constexpr int CH = Wide<T>::CH;
   __shared__ __attribute__((aligned(16))) T xiT[CH][256];
   __shared__ __attribute__((aligned(16))) T xjT[CH][kWideGJ];
   __shared__ __attribute__((aligned(16))) T xjg[kWideGJ][kWideGC];
   __shared__ T sqj[kWideGJ];
-  __shared__ T rj[kGradBC][kWideGJ];
+  __shared__ T rj[kGradBC][kWideGJ];  // (as in k_rbf_cross_grad)
   __shared__ double red[4][kWideGC + 2];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int gc = (int)blockIdx.y;  // dimensions gc * 32 .. gc * 32 + 31
@@ -839,23 +899,7 @@ __global__ __launch_bounds__(256) void k_rbf_cross_grad_wide(const T* __restrict
   for (int c = 0; c < kWideGC; ++c) gx[c] = 0.0;
   for (int64_t j0 = jb; j0 < je; j0 += kWideGJ) {
     T S[kWideGJ];
-#pragma unroll
-    for (int jj = 0; jj < kWideGJ; ++jj) S[jj] = T(0);
-    for (int64_t bt0 = 0; bt0 < batch; bt0 += kGradBC) {
-      __syncthreads();
-      for (int t = tid; t < kGradBC * kWideGJ; t += 256) {
-        const int q = t / kWideGJ, jj = t % kWideGJ;
-        rj[q][jj] = (bt0 + q < batch && j0 + jj < je) ? R[(bt0 + q) * ldr + j0 + jj] : T(0);
-      }
-      __syncthreads();
-      if (!wave_live) continue;
-      const int qmax = (int)((batch - bt0) < kGradBC ? (batch - bt0) : kGradBC);
-      for (int q = 0; q < qmax; ++q) {
-        const T l = live ? L[(bt0 + q) * ldl + i] : T(0);
-#pragma unroll
-        for (int jj = 0; jj < kWideGJ; ++jj) S[jj] += l * rj[q][jj];
-      }
-    }
+    src.template tile<kWideGJ>(live, wave_live, i, j0, je, rj, S);
     __syncthreads();
     if (tid < kWideGJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
     if (sel)
@@ -864,7 +908,7 @@ __global__ __launch_bounds__(256) void k_rbf_cross_grad_wide(const T* __restrict
         xjg[jj][c] = (j0 + jj < je) ? xc[(j0 + jj) * dpad + gc * kWideGC + c] : T(0);
       }
     T dot[kWideGJ];
-    wide_dots<T, kWideGJ, 1>(xc, je, dpad, xo, ic, j0, xiT, xjT, dot);  // (its barriers publish sqj / xjg too)
+    wide_dots<T, kWideGJ, Src::kDotsTag>(xc, je, dpad, xo, ic, j0, xiT, xjT, dot);  // (its barriers publish sqj / xjg too)
     if (!wave_live) continue;
 #pragma unroll
     for (int jj = 0; jj < kWideGJ; ++jj) {
@@ -936,244 +980,6 @@ __global__ __launch_bounds__(256) void k_rbf_cross_gx_final(const double* __rest
   double acc = 0.0;
   for (int64_t q = 0; q < nsplit; ++q) acc += gpart[(q * mo + o) * dpad + c];
   go[e] += (T)(-(double)outputscale[0] / (double)ls[ard ? c : 0] * acc);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Cross-covariance sweep with a DENSE weight matrix: the gradient of G = sum_aj S_aj K(Xn_a, X_j) for S (m, n), leading dimension
-// lds, given as it is (the predictive variance's S_aj = -2 vbar_a W_aj is diagonal in any batch, so the factored form of
-// k_rbf_cross_grad would need batch = m and an m-long inner loop per entry).  Formulas, kernel_eval weights, the dist <= 0 rule,
-// the column split, the fp64 partials and their fixed-order finals are those of k_rbf_cross_grad / k_rbf_cross_grad_wide; only
-// the S tile is read instead of formed.  TRANS = false: the owners are the rows of S (Xn, X̄n); TRANS = true: the owners are its
-// columns (X, X̄).
-// ------------------------------------------------------------------------------------------------
-
-// S of one owner row against the tile's columns j0 .. j0 + TJ (columns >= je read as 0).  Owner = a row of S: the thread's own TJ
-// consecutive entries, no other thread reads them, so they go straight to registers as 16-byte vector loads (vec: S and lds keep
-// every row's tile 16-byte aligned; the tile is whole) -- an LDS round trip would only add a write, a barrier and a read.  Otherwise,
-// and for the tail tile, scalar loads.  Owner = a column of S: entry (j, i), consecutive owners in consecutive lanes, coalesced.
-template <typename T, bool TRANS, int TJ>
-__device__ __forceinline__ void dense_tile(const T* __restrict__ S, int64_t lds, bool live, int64_t i, int64_t j0, int64_t je,
-                                           int vec, T (&s)[TJ]) {
-#pragma unroll
-  for (int jj = 0; jj < TJ; ++jj) s[jj] = T(0);
-  if (!live) return;
-  if (TRANS) {
-#pragma unroll
-    for (int jj = 0; jj < TJ; ++jj)
-      if (j0 + jj < je) s[jj] = S[(j0 + jj) * lds + i];
-  } else {
-    const T* row = S + i * lds + j0;
-    if (vec && j0 + TJ <= je) {
-      constexpr int V = 16 / (int)sizeof(T);
-#pragma unroll
-      for (int u = 0; u < TJ / V; ++u) {
-        const Pack<T, V> p = load_pack<T, V>(row + u * V);
-#pragma unroll
-        for (int e = 0; e < V; ++e) s[u * V + e] = p.v[e];
-      }
-    } else {
-#pragma unroll
-      for (int jj = 0; jj < TJ; ++jj)
-        if (j0 + jj < je) s[jj] = row[jj];
-    }
-  }
-}
-
-// d <= 32: k_rbf_cross_grad with the S tile of dense_tile (loaded before the tile's barriers, so that its latency hides behind the
-// staging of the column points)
-template <typename T, int DPAD, bool THETA, bool GX, bool TRANS>
-__global__ __launch_bounds__(256) void k_rbf_cross_grad_dense(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
-                                                              const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
-                                                              int64_t chunk, int d, int ard, int kind, const T* __restrict__ S,
-                                                              int64_t lds, int vec, const T* __restrict__ ls,
-                                                              const T* __restrict__ outputscale, T* __restrict__ go,
-                                                              double* __restrict__ gpart, double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) T xj[kGradTJ][DPAD];
-  __shared__ T sqj[kGradTJ];
-  __shared__ double red[4][DPAD + 2];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-  const bool live = i < mo;
-  const bool wave_live = (int64_t)blockIdx.x * 256 + wid * 64 < mo;
-  const int64_t ic = live ? i : mo - 1;
-  const int64_t jb = (int64_t)blockIdx.y * chunk;
-  const int64_t je = jb + chunk < nc ? jb + chunk : nc;
-  T xi[DPAD];
-#pragma unroll
-  for (int c = 0; c < DPAD; ++c) xi[c] = xo[ic * DPAD + c];
-  const T sqi = sqo[ic];
-  double gt[DPAD + 2];  // THETA: [0..DPAD) lengthscale dims (scalar: [0]), [DPAD] outputscale, [DPAD + 1] noise (stays 0)
-  double gx[DPAD];
-#pragma unroll
-  for (int c = 0; c < DPAD + 2; ++c) gt[c] = 0.0;
-#pragma unroll
-  for (int c = 0; c < DPAD; ++c) gx[c] = 0.0;
-  for (int64_t j0 = jb; j0 < je; j0 += kGradTJ) {
-    T Sv[kGradTJ];
-    dense_tile<T, TRANS, kGradTJ>(S, lds, live, i, j0, je, vec, Sv);
-    __syncthreads();
-    for (int t = tid; t < kGradTJ * DPAD; t += 256) {
-      const int64_t gi = j0 * DPAD + t;
-      (&xj[0][0])[t] = gi < je * DPAD ? xc[gi] : T(0);
-    }
-    if (tid < kGradTJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
-    __syncthreads();
-    if (!wave_live) continue;
-#pragma unroll
-    for (int jj = 0; jj < kGradTJ; ++jj) {
-      if (j0 + jj >= je) continue;
-      T dot = T(0);
-#pragma unroll
-      for (int c = 0; c < DPAD; ++c) dot += xi[c] * xj[jj][c];
-      const T raw = sqi + sqj[jj] - T(2) * dot;
-      const T dist = raw > T(0) ? raw : T(0);
-      T kv, wl;
-      kernel_eval<T>(kind, dist, kv, wl);
-      if (THETA) gt[DPAD] += (double)(Sv[jj] * kv);
-      if (!(raw > T(0))) continue;  // clamped: no l or input gradient
-      const T w = Sv[jj] * wl;
-      if (THETA) {
-        if (ard) {
-#pragma unroll
-          for (int c = 0; c < DPAD; ++c) {
-            const T df = xi[c] - xj[jj][c];
-            gt[c] += (double)(w * df * df);
-          }
-        } else {
-          gt[0] += (double)(w * dist);
-        }
-      }
-      if (GX) {
-#pragma unroll
-        for (int c = 0; c < DPAD; ++c) gx[c] += (double)(w * (xi[c] - xj[jj][c]));
-      }
-    }
-  }
-  if (THETA) {
-#pragma unroll
-    for (int c = 0; c < DPAD + 2; ++c) {
-      const double v = wave_sum(live ? gt[c] : 0.0);
-      if (lane == 0) red[wid][c] = v;
-    }
-    __syncthreads();
-    if (tid < DPAD + 2)
-      partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (DPAD + 2) + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-  }
-  if (!GX || !live) return;
-  if (go) {
-    const double s = (double)outputscale[0];
-#pragma unroll
-    for (int c = 0; c < DPAD; ++c)
-      if (c < d) go[i * d + c] += (T)(-s / (double)ls[ard ? c : 0] * gx[c]);
-  } else if (gpart) {
-#pragma unroll
-    for (int c = 0; c < DPAD; ++c) gpart[((int64_t)blockIdx.y * mo + i) * DPAD + c] = gx[c];
-  }
-}
-
-// d > 32: k_rbf_cross_grad_wide with the S tile of dense_tile (blockIdx.y selects 32 dimensions, blockIdx.z is the column split)
-template <typename T, bool THETA, bool GX, bool TRANS>
-__global__ __launch_bounds__(256) void k_rbf_cross_grad_dense_wide(const T* __restrict__ xo, const T* __restrict__ sqo, int64_t mo,
-                                                                   const T* __restrict__ xc, const T* __restrict__ sqc, int64_t nc,
-                                                                   int64_t chunk, int dpad, int d, int ard, int kind,
-                                                                   const T* __restrict__ S, int64_t lds, int vec,
-                                                                   const T* __restrict__ ls, const T* __restrict__ outputscale,
-                                                                   T* __restrict__ go, double* __restrict__ gpart,
-                                                                   double* __restrict__ partial) {
-  constexpr int CH = Wide<T>::CH;
-  __shared__ __attribute__((aligned(16))) T xiT[CH][256];
-  __shared__ __attribute__((aligned(16))) T xjT[CH][kWideGJ];
-  __shared__ __attribute__((aligned(16))) T xjg[kWideGJ][kWideGC];
-  __shared__ T sqj[kWideGJ];
-  __shared__ double red[4][kWideGC + 2];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int gc = (int)blockIdx.y;  // dimensions gc * 32 .. gc * 32 + 31
-  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-  const bool live = i < mo;
-  const bool wave_live = (int64_t)blockIdx.x * 256 + wid * 64 < mo;
-  const int64_t ic = live ? i : mo - 1;
-  const int64_t jb = (int64_t)blockIdx.z * chunk;
-  const int64_t je = jb + chunk < nc ? jb + chunk : nc;
-  const bool sel = ard || GX;
-  const T sqi = sqo[ic];
-  T xig[kWideGC];
-#pragma unroll
-  for (int c = 0; c < kWideGC; ++c) xig[c] = sel ? xo[ic * dpad + gc * kWideGC + c] : T(0);
-  double gt[kWideGC + 2];
-  double gx[kWideGC];
-#pragma unroll
-  for (int c = 0; c < kWideGC + 2; ++c) gt[c] = 0.0;
-#pragma unroll
-  for (int c = 0; c < kWideGC; ++c) gx[c] = 0.0;
-  for (int64_t j0 = jb; j0 < je; j0 += kWideGJ) {
-    T Sv[kWideGJ];
-    dense_tile<T, TRANS, kWideGJ>(S, lds, live, i, j0, je, vec, Sv);
-    __syncthreads();
-    if (tid < kWideGJ) sqj[tid] = (j0 + tid < je) ? sqc[j0 + tid] : T(0);
-    if (sel)
-      for (int t = tid; t < kWideGJ * kWideGC; t += 256) {
-        const int jj = t / kWideGC, c = t % kWideGC;
-        xjg[jj][c] = (j0 + jj < je) ? xc[(j0 + jj) * dpad + gc * kWideGC + c] : T(0);
-      }
-    T dot[kWideGJ];
-    wide_dots<T, kWideGJ, 2>(xc, je, dpad, xo, ic, j0, xiT, xjT, dot);  // (its barriers publish sqj / xjg too)
-    if (!wave_live) continue;
-#pragma unroll
-    for (int jj = 0; jj < kWideGJ; ++jj) {
-      if (j0 + jj >= je) continue;
-      const T raw = sqi + sqj[jj] - T(2) * dot[jj];
-      const T dist = raw > T(0) ? raw : T(0);
-      T kv, wl;
-      kernel_eval<T>(kind, dist, kv, wl);
-      if (THETA && gc == 0) gt[kWideGC] += (double)(Sv[jj] * kv);
-      if (!(raw > T(0))) continue;
-      const T w = Sv[jj] * wl;
-      if (THETA) {
-        if (ard) {
-#pragma unroll
-          for (int c = 0; c < kWideGC; ++c) {
-            const T df = xig[c] - xjg[jj][c];
-            gt[c] += (double)(w * df * df);
-          }
-        } else if (gc == 0) {
-          gt[0] += (double)(w * dist);
-        }
-      }
-      if (GX) {
-#pragma unroll
-        for (int c = 0; c < kWideGC; ++c) gx[c] += (double)(w * (xig[c] - xjg[jj][c]));
-      }
-    }
-  }
-  if (THETA) {
-#pragma unroll
-    for (int c = 0; c < kWideGC + 2; ++c) {
-      const double v = wave_sum(live ? gt[c] : 0.0);
-      if (lane == 0) red[wid][c] = v;
-    }
-    __syncthreads();
-    double* out = partial + ((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * (dpad + 2);
-    if (ard) {
-      if (tid < kWideGC) out[gc * kWideGC + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-    } else if (gc == 0) {
-      if (tid == 0) out[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-      for (int c = 1 + tid; c < dpad; c += 256) out[c] = 0.0;
-    }
-    if (gc == 0 && tid >= kWideGC && tid < kWideGC + 2)
-      out[dpad + tid - kWideGC] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-  }
-  if (!GX || !live) return;
-  if (go) {
-    const double s = (double)outputscale[0];
-#pragma unroll
-    for (int c = 0; c < kWideGC; ++c) {
-      const int col = gc * kWideGC + c;
-      if (col < d) go[i * d + col] += (T)(-s / (double)ls[ard ? col : 0] * gx[c]);
-    }
-  } else if (gpart) {
-#pragma unroll
-    for (int c = 0; c < kWideGC; ++c) gpart[((int64_t)blockIdx.z * mo + i) * dpad + gc * kWideGC + c] = gx[c];
-  }
 }
 
 constexpr int kRbfMaxD = 1024;  // wide inputs (d > 32): padded to a multiple of 32, k_rbf_apply_wide / k_rbf_grad_wide
@@ -1600,17 +1406,17 @@ int64_t rbf_cross_vjp_ws_bytes(const mfx_operator* op, int64_t m) {
   return rbf_carve(op, nullptr, 0, nullptr) + cross_vjp_extra(op, m, nullptr, nullptr);
 }
 
-// one sweep with owner rows (xo, sqo, mo) against the columns (xc, sqc, nc); S = L^T R with L (batch, mo), R (batch, nc).
-// The l / s sums and the owner gradient share one sweep where both sets of fp64 sums fit the registers (d <= 16); at padded
-// d = 32 and for wide inputs the shared form spills (34 registers at DPAD 32 in fp32), so there they are two sweeps.
-template <typename T>
+// one sweep with owner rows (xo, sqo, mo) against the columns (xc, sqc, nc); src gives S (owners x columns): FactoredSrc with
+// L (batch, mo), R (batch, nc), or DenseSrc.  The l / s sums and the owner gradient share one sweep where both sets of fp64 sums
+// fit the registers (d <= 16); at padded d = 32 and for wide inputs the shared form spills (34 registers at DPAD 32 in fp32), so
+// there they are two sweeps.
+template <typename T, typename Src>
 static int cross_sweep(const mfx_operator* op, int dpad, const T* xo, const T* sqo, int64_t mo, const T* xc, const T* sqc, int64_t nc,
-                       const T* L, int64_t ldl, const T* R, int64_t ldr, int64_t batch, bool theta, T* go, double* gpart,
-                       double* partial, int64_t* nblocks, hipStream_t stream) {
+                       const Src& src, bool theta, T* go, double* gpart, double* partial, int64_t* nblocks, hipStream_t stream) {
   const bool shared = dpad < 32;
   if (theta && go && !shared) {
-    MFX_TRY(cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, L, ldl, R, ldr, batch, true, nullptr, gpart, partial, nblocks, stream));
-    return cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, L, ldl, R, ldr, batch, false, go, gpart, partial, nblocks, stream);
+    MFX_TRY(cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, src, true, nullptr, gpart, partial, nblocks, stream));
+    return cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, src, false, go, gpart, partial, nblocks, stream);
   }
   const int64_t sel = dpad > 32 && (op->ard || go) ? dpad / kWideGC : 1;
   const CrossPlan pl = cross_plan(mo, nc, sel);
@@ -1620,9 +1426,9 @@ static int cross_sweep(const mfx_operator* op, int dpad, const T* xo, const T* s
   const T *ls = (const T*)op->lengthscale, *s = (const T*)op->outputscale;
   if (dpad <= 32) {
     const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
-#define MFX_CROSS_GRAD(D, TH, GX)                                                                                               \
-  k_rbf_cross_grad<T, D, TH, GX><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, op->d, op->ard, op->kernel_fn, L, ldl, \
-                                                           R, ldr, batch, ls, s, gdirect, gp, partial)
+#define MFX_CROSS_GRAD(D, TH, GX)                                                                                                \
+  k_rbf_cross_grad<T, D, TH, GX, Src><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, op->d, op->ard, op->kernel_fn, \
+                                                                src, ls, s, gdirect, gp, partial)
 #define MFX_CROSS_GRAD_D(D)                      \
   if (!go) {                                     \
     MFX_CROSS_GRAD(D, true, false);              \
@@ -1642,9 +1448,9 @@ static int cross_sweep(const mfx_operator* op, int dpad, const T* xo, const T* s
 #undef MFX_CROSS_GRAD
   } else {
     const dim3 grid((unsigned)pl.gx, (unsigned)sel, (unsigned)pl.gy);
-#define MFX_CROSS_GRAD_W(TH, GX)                                                                                          \
-  k_rbf_cross_grad_wide<T, TH, GX><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, dpad, op->d, op->ard,    \
-                                                             op->kernel_fn, L, ldl, R, ldr, batch, ls, s, gdirect, gp, partial)
+#define MFX_CROSS_GRAD_W(TH, GX)                                                                                               \
+  k_rbf_cross_grad_wide<T, TH, GX, Src><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, dpad, op->d, op->ard,    \
+                                                                  op->kernel_fn, src, ls, s, gdirect, gp, partial)
     if (!go) {
       MFX_CROSS_GRAD_W(true, false);
     } else {
@@ -1660,12 +1466,13 @@ static int cross_sweep(const mfx_operator* op, int dpad, const T* xo, const T* s
   return MFX_OK;
 }
 
-// grads->lengthscale / outputscale += d/dtheta sum_b L_b^T K(X_new, X) R_b, grads->x += d/dX, gxnew += d/dX_new (each if non-null).
-// Owner X_new carries its own gradient and the l / s partials; owner X runs only for grads->x (and then carries the partials
-// when X_new's gradient is not asked for, so that a (theta, X) request is two sweeps, not three).
-template <typename T>
-static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const T* L, int64_t ldl, const T* R, int64_t ldr,
-                         int64_t batch, const mfx_op_grads* grads, T* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
+// grads->lengthscale / outputscale += d/dtheta sum_aj S_aj K(X_new_a, X_j), grads->x += d/dX, gxnew += d/dX_new (each if non-null);
+// by_new gives S with owner X_new, by_x the same S with owner X (what: the prefix of the workspace message).  Owner X_new carries
+// its own gradient and the l / s partials; owner X runs only for grads->x (and then carries the partials when X_new's gradient is
+// not asked for, so that a (theta, X) request is two sweeps, not three).
+template <typename T, typename SrcNew, typename SrcX>
+static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const SrcNew& by_new, const SrcX& by_x, const char* what,
+                         const mfx_op_grads* grads, T* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
   const int dpad = rbf_dpad(op->d);
   RbfWs w;
   const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
@@ -1676,7 +1483,7 @@ static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const
   T* sqr = (T*)cv.take(m * sizeof(T));
   double* partial = (double*)cv.take(tb);
   double* gpart = (double*)cv.take(gb);
-  MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "cross-covariance VJP workspace too small");
+  MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "%scross-covariance VJP workspace too small", what);
   const bool theta = grads->lengthscale || grads->outputscale;
   T* gx = (T*)grads->x;
   if (!theta && !gx && !gxnew) return MFX_OK;
@@ -1687,10 +1494,8 @@ static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const
   const T *xs = (const T*)w.xs, *sq = (const T*)w.sq;
   int64_t nblocks = 0;
   if (gxnew || (theta && !gx))
-    MFX_TRY(cross_sweep<T>(op, dpad, xr, sqr, m, xs, sq, op->n, L, ldl, R, ldr, batch, theta, gxnew, gpart, partial, &nblocks, stream));
-  if (gx)
-    MFX_TRY(cross_sweep<T>(op, dpad, xs, sq, op->n, xr, sqr, m, R, ldr, L, ldl, batch, theta && !gxnew, gx, gpart, partial, &nblocks,
-                           stream));
+    MFX_TRY(cross_sweep<T>(op, dpad, xr, sqr, m, xs, sq, op->n, by_new, theta, gxnew, gpart, partial, &nblocks, stream));
+  if (gx) MFX_TRY(cross_sweep<T>(op, dpad, xs, sq, op->n, xr, sqr, m, by_x, theta && !gxnew, gx, gpart, partial, &nblocks, stream));
   if (theta) {
     k_rbf_grad_final<T><<<dpad + 2, 256, 0, stream>>>(partial, nblocks, dpad, op->d, op->ard, (const T*)op->lengthscale,
                                                       (const T*)op->outputscale, (T*)grads->lengthscale, (T*)grads->outputscale,
@@ -1698,6 +1503,15 @@ static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const
     MFX_CHECK_LAUNCH();
   }
   return MFX_OK;
+}
+
+// S = sum_b L_b^T R_b, L (batch, m), R (batch, n): owner X swaps the two factors
+template <typename T>
+static int cross_vjp_factored(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl, const void* R,
+                              int64_t ldr, int64_t batch, const mfx_op_grads* grads, void* gxnew, void* ws, int64_t ws_bytes,
+                              hipStream_t stream) {
+  const FactoredSrc<T> by_new{(const T*)L, ldl, (const T*)R, ldr, batch}, by_x{(const T*)R, ldr, (const T*)L, ldl, batch};
+  return rbf_cross_vjp<T>(op, (const T*)xnew, m, by_new, by_x, "", grads, (T*)gxnew, ws, ws_bytes, stream);
 }
 
 int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void* L, int64_t ldl, const void* R, int64_t ldr,
@@ -1706,126 +1520,19 @@ int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void
   MFX_REQUIRE(!grads->dense_a && !grads->val, MFX_ERR_INVALID,
               "the cross-covariance VJP fills the kernel-Gram fields only (dense_a / val must be NULL)");
   ScopedTimer t(1, stream);
-  if (op->dtype == MFX_F32)
-    return rbf_cross_vjp<float>(op, (const float*)xnew, m, (const float*)L, ldl, (const float*)R, ldr, batch, grads, (float*)gxnew,
-                                ws, ws_bytes, stream);
-  return rbf_cross_vjp<double>(op, (const double*)xnew, m, (const double*)L, ldl, (const double*)R, ldr, batch, grads,
-                               (double*)gxnew, ws, ws_bytes, stream);
+  if (op->dtype == MFX_F32) return cross_vjp_factored<float>(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, stream);
+  return cross_vjp_factored<double>(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, stream);
 }
 
-// cross_sweep with a dense S (m, n), lds: owner = its rows (trans = false: xo = X_new) or its columns (trans = true: xo = X).  The
-// same plan, the same split of the theta and owner sums into two launches at DPAD 32 and for wide inputs.
+// S (m, n) dense, leading dimension lds: owner X_new reads its rows, owner X its columns.  The row form's 16-byte loads: every
+// tile starts at a multiple of 16 columns, so an aligned S and lds keep each tile aligned.
 template <typename T>
-static int cross_sweep_dense(const mfx_operator* op, int dpad, const T* xo, const T* sqo, int64_t mo, const T* xc, const T* sqc,
-                             int64_t nc, const T* S, int64_t lds, bool trans, bool theta, T* go, double* gpart, double* partial,
-                             int64_t* nblocks, hipStream_t stream) {
-  const bool shared = dpad < 32;
-  if (theta && go && !shared) {
-    MFX_TRY(cross_sweep_dense<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, S, lds, trans, true, nullptr, gpart, partial, nblocks, stream));
-    return cross_sweep_dense<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, S, lds, trans, false, go, gpart, partial, nblocks, stream);
-  }
-  const int64_t sel = dpad > 32 && (op->ard || go) ? dpad / kWideGC : 1;
-  const CrossPlan pl = cross_plan(mo, nc, sel);
-  T* gdirect = pl.gy == 1 ? go : nullptr;
-  double* gp = go && pl.gy > 1 ? gpart : nullptr;
-  if (theta) *nblocks = pl.gx * pl.gy;
-  // the row form's 16-byte loads: every tile starts at a multiple of 16 columns, so an aligned S and lds keep each tile aligned
-  const int vec = !trans && (uintptr_t)S % 16 == 0 && (lds * (int64_t)sizeof(T)) % 16 == 0;
-  const T *ls = (const T*)op->lengthscale, *s = (const T*)op->outputscale;
-  if (dpad <= 32) {
-    const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
-#define MFX_DENSE_GRAD(D, TH, GX, TR)                                                                                           \
-  k_rbf_cross_grad_dense<T, D, TH, GX, TR><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, op->d, op->ard,          \
-                                                                     op->kernel_fn, S, lds, vec, ls, s, gdirect, gp, partial)
-#define MFX_DENSE_GRAD_T(D, TH, GX)  \
-  if (trans) {                       \
-    MFX_DENSE_GRAD(D, TH, GX, true); \
-  } else {                           \
-    MFX_DENSE_GRAD(D, TH, GX, false); \
-  }
-#define MFX_DENSE_GRAD_D(D)                                  \
-  if (!go) {                                                 \
-    MFX_DENSE_GRAD_T(D, true, false);                        \
-  } else if (!theta) {                                       \
-    MFX_DENSE_GRAD_T(D, false, true);                        \
-  } else {                                                   \
-    if constexpr (D < 32) { MFX_DENSE_GRAD_T(D, true, true); } \
-  }
-    switch (dpad) {
-      case 4: MFX_DENSE_GRAD_D(4); break;
-      case 8: MFX_DENSE_GRAD_D(8); break;
-      case 12: MFX_DENSE_GRAD_D(12); break;
-      case 16: MFX_DENSE_GRAD_D(16); break;
-      default: MFX_DENSE_GRAD_D(32); break;
-    }
-#undef MFX_DENSE_GRAD_D
-#undef MFX_DENSE_GRAD_T
-#undef MFX_DENSE_GRAD
-  } else {
-    const dim3 grid((unsigned)pl.gx, (unsigned)sel, (unsigned)pl.gy);
-#define MFX_DENSE_GRAD_W(TH, GX, TR)                                                                                          \
-  k_rbf_cross_grad_dense_wide<T, TH, GX, TR><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, dpad, op->d, op->ard, \
-                                                                       op->kernel_fn, S, lds, vec, ls, s, gdirect, gp, partial)
-    if (!go) {
-      if (trans) {
-        MFX_DENSE_GRAD_W(true, false, true);
-      } else {
-        MFX_DENSE_GRAD_W(true, false, false);
-      }
-    } else {
-      if (trans) {
-        MFX_DENSE_GRAD_W(false, true, true);
-      } else {
-        MFX_DENSE_GRAD_W(false, true, false);
-      }
-    }
-#undef MFX_DENSE_GRAD_W
-  }
-  MFX_CHECK_LAUNCH();
-  if (gp) {
-    k_rbf_cross_gx_final<T><<<(unsigned)((mo * op->d + 255) / 256), 256, 0, stream>>>(gp, pl.gy, mo, dpad, op->d, op->ard, ls, s, go);
-    MFX_CHECK_LAUNCH();
-  }
-  return MFX_OK;
-}
-
-// grads->lengthscale / outputscale += d/dtheta sum_aj S_aj K(X_new_a, X_j), grads->x += d/dX, gxnew += d/dX_new (each if non-null),
-// with rbf_cross_vjp's workspace and its order of sweeps: owner X_new for gxnew (and theta), owner X for grads->x
-template <typename T>
-static int rbf_cross_vjp_dense(const mfx_operator* op, const T* xnew, int64_t m, const T* S, int64_t lds, const mfx_op_grads* grads,
-                               T* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  const int dpad = rbf_dpad(op->d);
-  RbfWs w;
-  const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
-  int64_t tb = 0, gb = 0;
-  cross_vjp_extra(op, m, &tb, &gb);
-  Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
-  T* xr = (T*)cv.take(m * dpad * sizeof(T));
-  T* sqr = (T*)cv.take(m * sizeof(T));
-  double* partial = (double*)cv.take(tb);
-  double* gpart = (double*)cv.take(gb);
-  MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "dense cross-covariance VJP workspace too small");
-  const bool theta = grads->lengthscale || grads->outputscale;
-  T* gx = (T*)grads->x;
-  if (!theta && !gx && !gxnew) return MFX_OK;
-  MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
-  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
-                                                                xr, sqr);
-  MFX_CHECK_LAUNCH();
-  const T *xs = (const T*)w.xs, *sq = (const T*)w.sq;
-  int64_t nblocks = 0;
-  if (gxnew || (theta && !gx))
-    MFX_TRY(cross_sweep_dense<T>(op, dpad, xr, sqr, m, xs, sq, op->n, S, lds, false, theta, gxnew, gpart, partial, &nblocks, stream));
-  if (gx)
-    MFX_TRY(cross_sweep_dense<T>(op, dpad, xs, sq, op->n, xr, sqr, m, S, lds, true, theta && !gxnew, gx, gpart, partial, &nblocks,
-                                 stream));
-  if (theta) {
-    k_rbf_grad_final<T><<<dpad + 2, 256, 0, stream>>>(partial, nblocks, dpad, op->d, op->ard, (const T*)op->lengthscale,
-                                                      (const T*)op->outputscale, (T*)grads->lengthscale, (T*)grads->outputscale,
-                                                      nullptr, nullptr);
-    MFX_CHECK_LAUNCH();
-  }
-  return MFX_OK;
+static int cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds, const mfx_op_grads* grads,
+                           void* gxnew, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  const int vec = (uintptr_t)S % 16 == 0 && (lds * (int64_t)sizeof(T)) % 16 == 0;
+  const DenseSrc<T, false> by_new{(const T*)S, lds, vec};
+  const DenseSrc<T, true> by_x{(const T*)S, lds, 0};
+  return rbf_cross_vjp<T>(op, (const T*)xnew, m, by_new, by_x, "dense ", grads, (T*)gxnew, ws, ws_bytes, stream);
 }
 
 int op_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, const void* S, int64_t lds, const mfx_op_grads* grads,
@@ -1834,9 +1541,8 @@ int op_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, cons
   MFX_REQUIRE(!grads->dense_a && !grads->val, MFX_ERR_INVALID,
               "the cross-covariance VJP fills the kernel-Gram fields only (dense_a / val must be NULL)");
   ScopedTimer t(1, stream);
-  if (op->dtype == MFX_F32)
-    return rbf_cross_vjp_dense<float>(op, (const float*)xnew, m, (const float*)S, lds, grads, (float*)gxnew, ws, ws_bytes, stream);
-  return rbf_cross_vjp_dense<double>(op, (const double*)xnew, m, (const double*)S, lds, grads, (double*)gxnew, ws, ws_bytes, stream);
+  if (op->dtype == MFX_F32) return cross_vjp_dense<float>(op, xnew, m, S, lds, grads, gxnew, ws, ws_bytes, stream);
+  return cross_vjp_dense<double>(op, xnew, m, S, lds, grads, gxnew, ws, ws_bytes, stream);
 }
 
 // ================================================================================================

@@ -208,6 +208,38 @@ def test_dense_sweep_equals_factored_sweep_with_diagonal_L(dtype, kind, ard, d, 
         check(a, f.double(), SWEEP_TOL[dtype], name)
 
 
+@pytest.mark.parametrize("d", [3, 20, 40])  # one launch (DPAD 4), two launches (DPAD 32), wide with selections
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_dense_sweep_is_bitwise_the_factored_sweep_with_rank_one_weights(dtype, d):
+    """batch = 1: the factored sweep forms S_aj = L[a] * R[j], one rounded product; the dense call gets the same products
+    materialised by torch in the operator's dtype.  Both entry points are one kernel body with two weight sources, so on equal
+    numbers they give equal bits: xs, lengthscale, outputscale and X gradients, torch.equal.  m = 70: a partly dead workgroup with
+    dead waves; n = 300: three column splits and a 12-column tail tile; ARD, Matern-3/2, a test point on a training point."""
+    m, n = 70, 300
+    g = torch.Generator(device=DEV).manual_seed(m + n + d)
+    X = torch.randn(n, d, device=DEV, generator=g, dtype=dtype)
+    xs = torch.randn(m, d, device=DEV, generator=g, dtype=dtype)
+    xs[0] = X[5]
+    L = torch.randn(1, m, device=DEV, generator=g, dtype=dtype)
+    R = torch.randn(1, n, device=DEV, generator=g, dtype=dtype)
+    S = (L.T * R).contiguous()
+    op = RbfGramOp(X, kernel="matern32")
+    cparams = op.constrain(*(r.detach() for r in raw_params(d, True, dtype)))
+    desc = op.descriptor(cparams, dtype, n)
+    dense = _sweep(desc, xs, S, n, dtype, cparams[0], cparams[1])
+    lib, stream = _lib.get(), _lib.stream_ptr(DEV)
+    out = [torch.zeros_like(t) for t in dense]
+    st = _lib.OpGrads()
+    st.lengthscale, st.outputscale, st.x = out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr()
+    ws = _lib.scratch(int(lib.mfx_gram_cross_vjp_workspace_bytes(C.byref(desc), m, 1)), DEV)
+    _lib.check(lib.mfx_gram_cross_vjp(C.byref(desc), _lib.ptr(xs), m, _lib.ptr(L), m, _lib.ptr(R), n, 1, C.byref(st), _lib.ptr(out[0]),
+                                      _lib.ptr(ws), ws.numel(), stream))
+    torch.cuda.synchronize()
+    for name, a, f in zip(("xs", "lengthscale", "outputscale", "X"), dense, out):
+        assert float(a.abs().max()) > 0, name
+        assert torch.equal(a, f), (name, float((a - f).abs().max()))
+
+
 def test_chunk_size_does_not_change_the_result():
     X0, xs0, vbar = _problem(3, 70, 300, seed=9)
     raw = raw_params(3, True)

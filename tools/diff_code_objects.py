@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 code objects of two builds of libmfx.so function by function (no GPU needed).
+
+  python tools/diff_code_objects.py OLD/libmfx.so NEW/libmfx.so
+
+Instructions are compared as llvm-objdump prints them, without addresses and encodings.  The dense cross sweeps of the old
+naming (k_rbf_cross_grad_dense[_wide]<.., TRANS>) are matched with the weight-source instantiations that replaced them
+(k_rbf_cross_grad[_wide]<.., DenseSrc<T, TRANS>> / <.., FactoredSrc<T>>).  For every function that differs, the register, LDS,
+scratch and spill figures of both builds are printed.  Exit status 1 if anything differs or is unmatched."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+LLVM = "/opt/rocm/lib/llvm/bin/"
+KEYS = ("vgpr_count", "agpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count")
+
+
+def canonical(name):
+    """demangled name without the parameter list, cross sweeps in the weight-source naming"""
+    name = re.sub(r"^void ", "", name)
+    while "> >" in name:
+        name = name.replace("> >", ">>")
+    name = name[: name.index(">(") + 1] if ">(" in name else name.split("(")[0]
+    name = re.sub(r"\.kd$", "", name)
+    m = re.match(r"mfx::k_rbf_cross_grad(_dense)?(_wide)?<(float|double), (.*)>$", name)
+    if m and "Src<" not in name:
+        dense, wide, t, rest = m.groups()
+        args = rest.split(", ")
+        src = f"mfx::DenseSrc<{t}, {args.pop()}>" if dense else f"mfx::FactoredSrc<{t}>"
+        name = f"mfx::k_rbf_cross_grad{wide or ''}<{t}, {', '.join(args)}, {src}>"
+    return name
+
+
+def load(so):
+    """{canonical name: (instruction text, {metadata key: value})}"""
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        copy = shutil.copy(so, os.path.join(tmp, "libmfx.so" if so.endswith(".so") else "device-gfx950.co"))
+        if so.endswith(".so"):  # (anything else: a device-only code object, `hipcc --cuda-device-only -c`)
+            subprocess.run([LLVM + "llvm-objdump", "--offloading", copy], cwd=tmp, check=True, capture_output=True)
+        for f in sorted(os.listdir(tmp)):
+            if "gfx950" not in f:
+                continue
+            path = os.path.join(tmp, f)
+            notes = subprocess.run([LLVM + "llvm-readelf", "--notes", path], check=True, capture_output=True, text=True).stdout
+            meta = {}
+            for block in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+                block = ".agpr_count:" + block
+                sym = re.search(r"\.name:\s+(\S+)", block)
+                if sym:
+                    meta[sym.group(1)] = {k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1)) for k in KEYS}
+            dis = subprocess.run([LLVM + "llvm-objdump", "-d", "--no-show-raw-insn", path], check=True, capture_output=True, text=True).stdout
+            syms = re.findall(r"^[0-9a-f]+ <(\S+)>:$", dis, flags=re.M)
+            names = subprocess.run(["c++filt"], input="\n".join(syms), check=True, capture_output=True, text=True).stdout.split("\n")
+            pretty = dict(zip(syms, names))
+            for sym, body in re.findall(r"^[0-9a-f]+ <(\S+)>:\n(.*?)(?=^[0-9a-f]+ <\S+>:$|\Z)", dis, flags=re.M | re.S):
+                text = "\n".join(re.sub(r"\s*//.*$", "", line).strip() for line in body.split("\n") if line.strip())
+                out[canonical(pretty[sym])] = (text, meta.get(sym, {}))
+    return out
+
+
+def main():
+    old, new = load(sys.argv[1]), load(sys.argv[2])
+    same = [n for n in old if n in new and old[n][0] == new[n][0]]
+    differ = [n for n in old if n in new and old[n][0] != new[n][0]]
+    cross = lambda names: sum("k_rbf_cross_grad" in n and "gx_final" not in n for n in names)  # noqa: E731
+    print(f"functions: old {len(old)}, new {len(new)}; identical {len(same)} (cross family {cross(same)}), "
+          f"differing {len(differ)} (cross family {cross(differ)})")
+    for n in sorted(set(old) - set(new)):
+        print("only in old:", n)
+    for n in sorted(set(new) - set(old)):
+        print("only in new:", n)
+    for n in sorted(differ):
+        print("differs:", n)
+        for k in KEYS:
+            print(f"    {k}: {old[n][1].get(k)} -> {new[n][1].get(k)}")
+        print(f"    instructions: {old[n][0].count(chr(10)) + 1} -> {new[n][0].count(chr(10)) + 1}")
+    return 1 if differ or set(old) ^ set(new) else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
