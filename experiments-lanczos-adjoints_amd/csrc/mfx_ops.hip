@@ -1617,6 +1617,16 @@ int op_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, int64_
 int op_apply_cb(const mfx_operator* op, int mode, const void* x, int64_t ldx, const void* aux, int64_t ldaux, void* y,
                 int64_t ldy, int64_t p, hipStream_t stream) {
   MFX_REQUIRE(op->callback, MFX_ERR_INVALID, "callback operator without function pointer");
+  // A callback may call back into the library (a Python matvec around a native Gram operator).  Those are calls of their own, on a
+  // workspace of the callee's whose contents the driver in progress knows nothing about: they must not inherit its PrepScope, or
+  // the second nested application would skip k_rbf_prep and read whatever the caller left in its workspace since the first.
+  // The price: every native Gram application inside a callback runs its own k_rbf_prep (one more launch per nested matvec).
+  struct PrepSuspend {
+    const int depth = t_prep_depth;
+    const PrepKey done = t_prep_done;
+    PrepSuspend() { t_prep_depth = 0; t_prep_done = PrepKey{}; }
+    ~PrepSuspend() { t_prep_depth = depth; t_prep_done = done; }
+  } suspend;
   const int rc = op->callback(op->ctx, mode, x, ldx, aux, ldaux, y, ldy, p, op->n, stream);
   MFX_REQUIRE(rc == 0, MFX_ERR_CALLBACK, "operator callback failed with code %d", rc);
   return MFX_OK;
