@@ -85,6 +85,19 @@ constexpr int kSlice = kBlock * kEpt;  // 2048 elements of one vector per workgr
 
 inline int64_t num_slices(int64_t n) { return (n + kSlice - 1) / kSlice; }
 
+// ---- the small dense (k x k) kernels: mfx_small.hip (eigensolver, quadrature VJP) and mfx_funm.hip (f(T) e1 and its VJP) ----------
+constexpr int kSmallLdsDepth = 120;   // up to here the k x k work matrices of those kernels live in LDS
+constexpr int kSmallMaxDepth = 2048;  // a few vectors of k doubles (d, e; lam, f, f', u0, w) still do
+// dynamic LDS beyond the 64 KiB a kernel gets by default
+template <typename F>
+static int allow_big_lds(F fn, size_t bytes) {
+  if (bytes > 64 * 1024) {
+    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)bytes));
+  }
+  return MFX_OK;
+}
+
 // ---- probe groups of the Krylov vector passes ---------------------------
 // The consecutive vector kernels between two operator applications (dots -> update -> update; dots -> combine -> update)
 // each sweep the same basis rows.  Launched for all probes at once, every pass streams the whole basis from HBM as soon as

@@ -160,18 +160,6 @@ __global__ void k_rademacher(uint64_t seed, int64_t first_probe, int64_t n, T* _
     out[b * n + i] = rademacher_sign<T>(key, i);
 }
 
-constexpr int kSmallLdsDepth = 120;   // up to here the k x k work matrices of the two kernels above live in LDS
-constexpr int kSmallMaxDepth = 2048;  // d, e (or lam, f, f', u0) still do: 4 k doubles
-
-template <typename F>
-static int allow_big_lds(F fn, size_t bytes) {
-  if (bytes > 64 * 1024) {
-    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)bytes));
-  }
-  return MFX_OK;
-}
-
 }  // namespace mfx
 
 using namespace mfx;

@@ -147,6 +147,11 @@ SYMBOLS = {
     ),
     "mfx_tridiag_eigh": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "mfx_slq_quadform_bwd": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I, _P, _P, _I64, _P]),
+    "mfx_funm_coeffs": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _P, _P]),
+    "mfx_funm_coeffs_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
+    "mfx_basis_combine": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P]),
+    "mfx_basis_combine_workspace_bytes": (_I64, [_I64, _I64, _I64, _I]),
+    "mfx_basis_combine_bwd": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P, _I64, _P]),
     "mfx_rademacher": (_I, [C.c_uint64, _I64, _I64, _I64, _I, _P, _P]),
     "mfx_pcg_workspace_bytes": (_I64, [_OPP, _I64, _I64, _I64]),
     "mfx_pcg_sharded_workspace_bytes": (_I64, [_OPP, _CMP, _I64, _I64, _I64]),

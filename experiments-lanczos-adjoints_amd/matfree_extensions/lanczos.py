@@ -8,6 +8,11 @@ Same functional surface as the reference's ``matfree_extensions/lanczos.py``:
         -> quadform(v0, *params) -> scalar
     integrand_spd_custom_vjp_reuse(matfun, order, matvec, /, *, reortho="full")
 
+and, beyond the reference, the vector-valued form on the same path:
+
+    funm_spd(matfun, krylov_depth, matvec, /, *, reortho="full", custom_vjp=True)
+        -> apply(v, *params) -> f(A) v  (``mfx_funm_coeffs`` / ``mfx_basis_combine`` and their VJPs)
+
 ``reortho="full"`` runs through the Arnoldi kernels exactly as the reference does (lanczos.py:152-169);
 ``reortho="none"`` is the three-term recurrence with its own adjoint (lanczos.py:172-335).  The k x k
 eigen-problem and its VJP (lanczos.py:48-59) run on the device too (``mfx_tridiag_eigh`` /
@@ -369,6 +374,121 @@ def integrand_spd(matfun, krylov_depth, matvec, /, *, reortho: str = "full",
 
     quadform.batched = True
     return quadform
+
+
+# ------------------------------------------------------------------------------------------------
+# vector-valued matrix functions  f(A) v ~ |v| Q f(T) e1  (no counterpart in the reference)
+# ------------------------------------------------------------------------------------------------
+def _tridiag_eigh(diag, off):
+    """``mfx_tridiag_eigh`` of the (p, k) / (p, k - 1) tridiagonal, detached: evals (p, k), evecs (p, k, k) in the input dtype."""
+    _lib.require_device(diag, off)
+    lib = _lib.get()
+    diag, off = diag.detach().contiguous(), off.detach().contiguous()
+    p, k = diag.shape
+    dt, dev = diag.dtype, diag.device
+    et = torch.float64 if k > 120 else dt  # as _QuadformFn: beyond depth 120 the eigensolver wants fp64 buffers
+    diag_e, off_e = diag.to(et), off.to(et)
+    evals = torch.empty((p, k), dtype=et, device=dev)
+    evecs = torch.empty((p, k, k), dtype=et, device=dev)
+    _lib.check(lib.mfx_tridiag_eigh(_lib.ptr(diag_e), _lib.ptr(off_e) if k > 1 else None, max(k - 1, 1), p, k,
+                                    _lib.dtype_code(et), _lib.ptr(evals), _lib.ptr(evecs), _lib.stream_ptr(dev)))
+    return evals.to(dt), evecs.to(dt)
+
+
+class _FunmFn(torch.autograd.Function):
+    """y = sum_j c_j q_j with c = scale U (fvals o U[0])  (``mfx_funm_coeffs``, ``mfx_basis_combine``) and its VJP w.r.t. the basis, the
+    tridiagonal, the scale and ``fvals`` (``mfx_basis_combine_bwd``, ``mfx_funm_coeffs_bwd``).  ``evals`` / ``evecs`` are the detached
+    eigen-problem of (diag, off) and ``dfvals`` = f'(evals): the dependence of the eigen-problem on the tridiagonal is what the
+    divided-difference VJP accounts for.  ``fvals`` is an input of its own so that gradients reach whatever ``matfun`` closes over."""
+
+    @staticmethod
+    def forward(ctx, Q, diag, off, scale, evals, evecs, fvals, dfvals):
+        _lib.require_device(Q, diag, off, scale, evals, evecs, fvals, dfvals)
+        lib = _lib.get()
+        Q = Q.contiguous()
+        p, k, n = Q.shape
+        dt, dev = Q.dtype, Q.device
+        code = _lib.dtype_code(dt)
+        scale, evals, evecs = scale.contiguous(), evals.contiguous(), evecs.contiguous()
+        fvals, dfvals = fvals.to(dt).contiguous(), dfvals.to(dt).contiguous()
+        coeffs = torch.empty((p, k), dtype=dt, device=dev)
+        y = torch.empty((p, n), dtype=dt, device=dev)
+        _lib.check(lib.mfx_funm_coeffs(_lib.ptr(evals), _lib.ptr(evecs), _lib.ptr(fvals), _lib.ptr(scale), p, k, code,
+                                       _lib.ptr(coeffs), _lib.stream_ptr(dev)))
+        _lib.check(lib.mfx_basis_combine(_lib.ptr(Q), _lib.ptr(coeffs), n, k, p, code, _lib.ptr(y), _lib.stream_ptr(dev)))
+        ctx.save_for_backward(Q, coeffs, scale, evals, evecs, fvals, dfvals)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        Q, coeffs, scale, evals, evecs, fvals, dfvals = ctx.saved_tensors
+        lib = _lib.get()
+        p, k, n = Q.shape
+        dt, dev = Q.dtype, Q.device
+        code = _lib.dtype_code(dt)
+        dy = dy.contiguous()
+        need_q = ctx.needs_input_grad[0]
+        need_c = any(ctx.needs_input_grad[i] for i in (1, 2, 3, 6))
+        if not (need_q or need_c):
+            return (None,) * 8
+        dQ = torch.empty((p, k, n), dtype=dt, device=dev) if need_q else None
+        dcoeffs = torch.empty((p, k), dtype=dt, device=dev) if need_c else None
+        ws = _lib.scratch(int(lib.mfx_basis_combine_workspace_bytes(n, k, p, code)), dev)
+        _lib.check(lib.mfx_basis_combine_bwd(_lib.ptr(Q), _lib.ptr(coeffs), _lib.ptr(dy), n, k, p, code, _lib.ptr(dQ),
+                                             _lib.ptr(dcoeffs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        dalpha = dbeta = dscale = dfv = None
+        if need_c:
+            dalpha = torch.empty((p, k), dtype=dt, device=dev)
+            dbeta = torch.empty((p, max(k - 1, 1)), dtype=dt, device=dev)
+            dscale = torch.empty((p,), dtype=dt, device=dev)
+            _lib.check(lib.mfx_funm_coeffs_bwd(_lib.ptr(evals), _lib.ptr(evecs), _lib.ptr(fvals), _lib.ptr(dfvals), _lib.ptr(dcoeffs),
+                                               _lib.ptr(scale), p, k, code, _lib.ptr(dalpha), _lib.ptr(dbeta), max(k - 1, 1),
+                                               _lib.ptr(dscale), _lib.stream_ptr(dev)))
+            dbeta = dbeta[:, : k - 1]
+            if ctx.needs_input_grad[6]:  # d fvals[b][a] = scale (U^T dc)_a u0_a: (p, k, k) plumbing, only when matfun's closure wants it
+                dfv = scale[:, None] * torch.einsum("pja,pj->pa", evecs, dcoeffs) * evecs[:, 0, :]
+        return dQ, dalpha, dbeta, dscale, None, None, dfv, None
+
+
+def _funm_apply(matfun, Q, diag, off, scale):
+    """scale Q^T f(T) e1 for the (p, k, n) basis and (p, k) / (p, k - 1) tridiagonal of ``tridiag``: eigen-problem on the device, f and f' by
+    torch on the (p, k) eigenvalues, coefficients and combination by libmfx."""
+    evals, evecs = _tridiag_eigh(diag, off)
+    with torch.enable_grad():
+        lam = evals.detach().requires_grad_(True)
+        (dfx,) = torch.autograd.grad(matfun(lam).sum(), lam, allow_unused=True)
+    if dfx is None:
+        dfx = torch.zeros_like(evals)
+    # A second evaluation on the (p, k) eigenvalues, deliberately: on the DETACHED eigenvalues the values are attached only to what
+    # matfun closes over (expm_lanczos: dt).  The values of the evaluation above hang on `lam` as well, so with them _FunmFn would see an
+    # input that always requires grad, and every backward would form the fvals cotangent and push it into that throwaway leaf.
+    fx = matfun(evals)
+    return _FunmFn.apply(Q, diag, off, scale, evals, evecs, fx, dfx)
+
+
+def funm_spd(matfun, krylov_depth, matvec, /, *, reortho: str = "full", custom_vjp: bool = True):
+    """f(A) v ~ |v| Q f(T) e1 for a symmetric operator: ``apply(v, *params) -> f(A) v`` with v (n,) or (p, n).
+
+    ``matfun`` is any torch callable on the (p, k) eigenvalues of the tridiagonal.  Differentiable w.r.t. v, the parameters, the inputs of
+    a kernel-Gram operator and whatever ``matfun`` closes over: the VJP of f(T) e1 is in divided-difference form (stable for close Ritz
+    values, as ``integrand_spd``'s), and the adjoint drivers of ``tridiag`` turn the basis / tridiagonal cotangents into the rest.
+    A row-sharded operator is refused: there is no sharded combination."""
+
+    def apply(v, *parameters):
+        op, _ = as_operator(matvec)
+        if isinstance(op, RowShardedOp):
+            raise NotImplementedError("funm_spd on a row-sharded operator: there is no sharded basis combination")
+        batched = v.dim() == 2
+        V = v if batched else v[None]
+        algorithm = tridiag(matvec, krylov_depth, custom_vjp=custom_vjp, reortho=reortho)  # refusals before any work
+        scale = torch.linalg.vector_norm(V, dim=-1)
+        V = V / scale[:, None]
+        (basis, (diag, off_diag)), _remainder = algorithm(V, *parameters)
+        out = _funm_apply(matfun, basis, diag, off_diag, scale)
+        return out if batched else out[0]
+
+    apply.batched = True
+    return apply
 
 
 def integrand_spd_custom_vjp_reuse(matfun, order, matvec, /, *, reortho: str = "full"):

@@ -133,6 +133,20 @@ def gram_operator(inputs, *, noise_minval=0.0, precision="f16x3", kernel="rbf"):
     return RbfGramOp(inputs, noise_minval=noise_minval, precision=precision, kernel=kernel)
 
 
+def gram_funm(matfun, krylov_depth, *, precision="f16x3", kernel="rbf", reortho="full", noise_minval=0.0):
+    """``apply(inputs, V, raw_lengthscale=, raw_outputscale=, raw_noise=) -> f(K(X, X) + noise I) V`` for V (n,) or (p, n), by
+    ``lanczos.funm_spd`` on the native Gram operator (the constrain / ``gram_operator`` plumbing of the likelihoods).  With z ~ N(0, I),
+    ``matfun=torch.sqrt`` gives prior draws from N(0, K + sigma^2 I) and ``matfun=torch.rsqrt`` whitens residuals.  Differentiable w.r.t.
+    the raw parameters, V and the inputs.  No counterpart in the reference."""
+
+    def apply(inputs, V, *, raw_lengthscale, raw_outputscale, raw_noise):
+        op = gram_operator(inputs, noise_minval=noise_minval, precision=precision, kernel=kernel)
+        funm = lanczos.funm_spd(matfun, krylov_depth, op.bind(raw_lengthscale, raw_outputscale, raw_noise), reortho=reortho)
+        return funm(V)
+
+    return apply
+
+
 def krylov_logdet_slq(krylov_depth, /, *, sample, num_batches: int, checkpoint: bool = False):
     """util/gp_util.py:552-576: logdet(A, key) -> (value, info) by stochastic Lanczos quadrature.
 

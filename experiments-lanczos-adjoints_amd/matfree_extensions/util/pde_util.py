@@ -38,6 +38,19 @@ def expm_arnoldi(krylov_depth, *, max_squarings: int = 32, reortho="full", custo
     return expm
 
 
+def expm_lanczos(krylov_depth, *, reortho="full", custom_vjp=True):
+    """exp(dt A) y0 ~ |y0| Q exp(dt T) e1 for a SYMMETRIC operator, with expm_arnoldi's call signature.  The k x k exponential is the
+    eigen-decomposition of the tridiagonal on the device and the combination over the basis is one native pass (``lanczos.funm_spd``);
+    the backward is the divided-difference VJP, not autograd through ``eigh`` / ``matrix_exp``.  ``dt`` may be a tensor that requires
+    grad.  No counterpart in the reference; expm_arnoldi is unchanged."""
+
+    def expm(matvec, dt, y0_flat, *p):
+        apply = lanczos.funm_spd(lambda lam: torch.exp(dt * lam), krylov_depth, matvec, reortho=reortho, custom_vjp=custom_vjp)
+        return apply(y0_flat, *p), {"num_matvecs": krylov_depth}
+
+    return expm
+
+
 def expm_pade():
     """Dense baseline of expm_arnoldi (util/pde_util.py:271-280): materialise A through the matvec (the reference takes its Jacobian; the
     matvec is linear, so n applications to the identity are the same matrix) and apply torch.linalg.matrix_exp(dt A) to y0.  Small n only."""

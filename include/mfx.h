@@ -245,6 +245,46 @@ int mfx_slq_quadform_bwd(const void* evals, const void* evecs, const void* fvals
                          const void* dfvals, const void* gout, int64_t p, int64_t k, int dtype,
                          void* dalpha, void* dbeta, int64_t lddbeta, void* stream);
 
+/* ---- matrix-function--vector products on the Lanczos path:  f(A) v ~ |v| Q f(T) e1   ----------------
+ * The thin layer between the tridiagonalisation and the user: the coefficient vector c = scale f(T) e1 from the eigen-problem
+ * mfx_tridiag_eigh solved, the combination y = sum_j c_j q_j over the (p, k, n) basis, and the VJP of both.  No counterpart in
+ * the reference (its vector-valued forms are jnp compositions, util/pde_util.py:257-268, :335-356).  All asynchronous, no atomics,
+ * bit-reproducible from run to run; fp32 and fp64; every refusal below happens before any launch.
+ *
+ * coeffs[b][j] = scale[b] sum_a evecs[b][j][a] fvals[b][a] evecs[b][0][a]   (p, k);  fvals = f(evals) (p, k), scale (p).
+ * fp64 arithmetic inside, one workgroup per vector, k <= 2048 (MFX_ERR_UNSUPPORTED beyond).  `evals` is not read (the caller
+ * evaluated f); it is part of the signature so that forward and backward take the same eigen-problem.
+ * MFX_ERR_INVALID: a null pointer, p < 1, k < 1; MFX_ERR_UNSUPPORTED: unknown dtype, k > 2048, p > 2^31 - 1. */
+int mfx_funm_coeffs(const void* evals, const void* evecs, const void* fvals, const void* scale, int64_t p, int64_t k, int dtype,
+                    void* coeffs, void* stream);
+
+/* VJP of mfx_funm_coeffs w.r.t. the tridiagonal and the scale (Daleckii-Krein).  With U = evecs[b], w = U^T dcoeffs[b],
+ * u0 = U[0][:], M_ac = F_ac w_a u0_c (F the divided differences of f at the eigenvalues, F_aa = f'(lam_a) = dfvals) and
+ * G = U M U^T:   dalpha[b][i] = scale G_ii,   dbeta[b][i] = scale (G_{i,i+1} + G_{i+1,i})  (leading dimension lddbeta >= k - 1),
+ * dscale[b] = <coeffs[b] / scale[b], dcoeffs[b]>  (dscale may be NULL).  M is not symmetric, unlike mfx_slq_quadform_bwd's.
+ * Two Ritz values count as equal, and the mean of f' replaces the divided difference, exactly as in mfx_slq_quadform_bwd:
+ * |lam_a - lam_c| <= (1e-6 in fp32, 1e-13 in fp64) max|lam|.  k <= 120: M in LDS; k <= 2048: evaluated where it is used.
+ * MFX_ERR_INVALID: a null pointer other than dscale (dbeta may be NULL when k == 1), p < 1, k < 1, lddbeta < k - 1;
+ * MFX_ERR_UNSUPPORTED: unknown dtype, k > 2048, p > 2^31 - 1. */
+int mfx_funm_coeffs_bwd(const void* evals, const void* evecs, const void* fvals, const void* dfvals, const void* dcoeffs,
+                        const void* scale, int64_t p, int64_t k, int dtype, void* dalpha, void* dbeta, int64_t lddbeta, void* dscale,
+                        void* stream);
+
+/* y[b][:] = sum_j coeffs[b][j] Q[b][j][:]   -- Q (p, k, n) contiguous, coeffs (p, k), y (p, n).  One pass over the basis on the
+ * vector geometry of the Krylov drivers (grid = (slices, p), 16-byte loads when n and the pointers allow, double-buffered rows).
+ * MFX_ERR_INVALID: a null pointer, n, k or p < 1; MFX_ERR_UNSUPPORTED: unknown dtype, k > 2048, p > 65535. */
+int mfx_basis_combine(const void* Q, const void* coeffs, int64_t n, int64_t k, int64_t p, int dtype, void* y, void* stream);
+
+/* VJP of mfx_basis_combine:  dQ[b][j][:] = coeffs[b][j] dy[b][:]  (p, k, n)  and  dcoeffs[b][j] = <Q[b][j], dy[b]>  (p, k): per-slice
+ * partial sums in `ws`, re-reduced in fp64 in a fixed order.  dQ == NULL or dcoeffs == NULL skips that half (Q is not read without
+ * dcoeffs, coeffs not without dQ; the other output is bit-identical to the full call's).  The workspace is needed for dcoeffs only:
+ * mfx_basis_combine_workspace_bytes(n, k, p, dtype) bytes (-1 for arguments the call would refuse), MFX_ERR_WORKSPACE when short.
+ * MFX_ERR_INVALID: null dy, both outputs NULL, a null input of a half that is asked for, n, k or p < 1; MFX_ERR_UNSUPPORTED as in
+ * mfx_basis_combine. */
+int64_t mfx_basis_combine_workspace_bytes(int64_t n, int64_t k, int64_t p, int dtype);
+int mfx_basis_combine_bwd(const void* Q, const void* coeffs, const void* dy, int64_t n, int64_t k, int64_t p, int dtype, void* dQ,
+                          void* dcoeffs, void* ws, int64_t ws_bytes, void* stream);
+
 /* +-1 probes (matfree.hutchinson.sampler_rademacher call sites: util/gp_util.py:557,
  * optim_logml_adjoints_adaptive.py:109).  Counter-based: element (b, i) depends only on
  * (seed, first_probe + b, i), so probe shards on different GPUs form one global probe matrix. */
