@@ -1582,12 +1582,15 @@ static int op_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int
       return MFX_OK;
     }
     case MFX_OP_CSR: {
-      MFX_REQUIRE(op->crow && op->col && op->val, MFX_ERR_INVALID, "CSR operator without structure");
+      // an operator with no stored values (nnz == 0) is the zero matrix: only the row pointers exist, and the kernel, which
+      // finds every row empty, reads nothing else
+      const bool stored = op->nnz > 0;
+      MFX_REQUIRE(op->crow && (!stored || (op->col && op->val)), MFX_ERR_INVALID, "CSR operator without structure");
       const dim3 grid((unsigned)((nrow + 31) / 32), (unsigned)p);
       if (!transpose) {
         k_csr_apply<T><<<grid, 256, 0, stream>>>(op->crow, op->col, nullptr, (const T*)op->val, nrow, x, ldx, y, ldy, row0);
       } else {
-        MFX_REQUIRE(op->t_crow && op->t_col && op->t_perm, MFX_ERR_INVALID,
+        MFX_REQUIRE(op->t_crow && (!stored || (op->t_col && op->t_perm)), MFX_ERR_INVALID,
                     "CSR transpose structure required for the Arnoldi adjoint");
         k_csr_apply<T><<<grid, 256, 0, stream>>>(op->t_crow, op->t_col, op->t_perm, (const T*)op->val, nrow, x, ldx, y, ldy, row0);
       }
@@ -1648,7 +1651,7 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
       MFX_CHECK_LAUNCH();
       return MFX_OK;
     case MFX_OP_CSR:
-      if (!grads->val) return MFX_OK;
+      if (!grads->val || op->nnz == 0) return MFX_OK;  // no stored values: nothing to accumulate (and a zero-sized grid is a launch error)
       MFX_REQUIRE(op->row && op->col, MFX_ERR_INVALID, "CSR gradient needs the COO row index");
       k_csr_grad<T><<<(unsigned)((op->nnz + 255) / 256), 256, 0, stream>>>(op->row, op->col, op->nnz, L, ldl, R, ldr,
                                                                          batch, (T*)grads->val, row0, nrow);
