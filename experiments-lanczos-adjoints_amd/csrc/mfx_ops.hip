@@ -4,6 +4,8 @@
 //
 // The RBF kernels in this file are the generic VALU path (any dtype, any number of probes); the
 // fp32 MFMA path for wide probe batches lives in mfx_rbf_mfma.hip and is selected in rbf_apply().
+#include <type_traits>
+
 #include "mfx_internal.h"
 #include "mfx_kernel_fn.h"
 
@@ -985,6 +987,49 @@ __global__ __launch_bounds__(256) void k_rbf_cross_gx_final(const double* __rest
 constexpr int kRbfMaxD = 1024;  // wide inputs (d > 32): padded to a multiple of 32, k_rbf_apply_wide / k_rbf_grad_wide
 static int rbf_dpad(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 12 ? 12 : d <= 16 ? 16 : d <= kRbfMaxD ? (d + 31) / 32 * 32 : -1; }
 
+// The launch layer of the VALU kernel-Gram kernels.  Every launch site goes through with_dpad; the matvec sites also through one
+// of the two vectors-per-workgroup choosers.  A compile-time value arrives as a std::integral_constant argument of a generic lambda.
+template <int V>
+using Const = std::integral_constant<int, V>;
+
+// rbf_dpad's value as a compile-time constant: narrow(Const<DPAD>) for the register kernels (a point in DPAD registers), wide() for
+// d > 32 (the padded dimension stays a run-time argument of the *_wide kernels)
+template <typename Narrow, typename WideFn>
+static void with_dpad(int dpad, Narrow&& narrow, WideFn&& wide) {
+  switch (dpad) {
+    case 4: narrow(Const<4>{}); break;
+    case 8: narrow(Const<8>{}); break;
+    case 12: narrow(Const<12>{}); break;
+    case 16: narrow(Const<16>{}); break;
+    case 32: narrow(Const<32>{}); break;
+    default: wide(); break;
+  }
+}
+
+// vectors per workgroup (PB) of k_rbf_apply: launch(Const<PB>)
+template <typename Launch>
+static void with_apply_pb(int64_t p, Launch&& launch) {
+  if (p == 1) launch(Const<1>{});
+  else if (p == 2) launch(Const<2>{});
+  else if (p <= 4) launch(Const<4>{});
+  else launch(Const<8>{});
+}
+
+// ... and of k_rbf_apply_wide
+template <typename T, typename Launch>
+static void with_apply_wide_pb(int64_t p, Launch&& launch) {
+  if (p == 1) launch(Const<1>{});
+  else if (p <= 4 || sizeof(T) == 8) launch(Const<4>{});  // (8 fp64 vectors next to the 32 fp64 dot products of a tile would spill)
+  else if constexpr (sizeof(T) == 4) launch(Const<8>{});
+}
+
+// A prepared point set (k_rbf_prep's output): x (m, dpad) = the points over the lengthscale, zero padded; sq (m) = their squared norms
+template <typename T>
+struct Points {
+  const T *x, *sq;
+  int64_t m;
+};
+
 struct RbfWs {
   void *xs, *sq;
   double* partial;
@@ -1061,58 +1106,60 @@ static int rbf_prep(const mfx_operator* op, const RbfWs& w, int dpad, hipStream_
   return MFX_OK;
 }
 
-template <typename T, int DPAD>
-static int rbf_apply_d(const mfx_operator* op, const RbfWs& w, const T* x, int64_t ldx, T* y, int64_t ldy, int64_t p,
-                       hipStream_t stream, const T* xrow = nullptr, const T* sqrow = nullptr, int64_t m = 0) {
-  int64_t row0 = -1;  // cross-covariance rows (another point set)
-  if (!xrow) {        // rows row0 .. row0 + m of the square Gram operator
-    row0 = op_row0(op);
-    m = op_nrows(op);
-    xrow = (const T*)w.xs + row0 * DPAD;
-    sqrow = (const T*)w.sq + row0;
-  }
-  const unsigned gx = (unsigned)((m + 255) / 256);
-#define MFX_RBF_LAUNCH(PB)                                                                           \
-  k_rbf_apply<T, DPAD, PB><<<dim3(gx, (unsigned)((p + PB - 1) / PB)), 256, 0, stream>>>(               \
-      (const T*)w.xs, (const T*)w.sq, op->n, (const T*)op->outputscale, (const T*)op->noise, x, ldx, y, ldy, p, \
-      op->kernel_fn, xrow, sqrow, m, row0)
-  if (p == 1) {
-    MFX_RBF_LAUNCH(1);
-  } else if (p == 2) {
-    MFX_RBF_LAUNCH(2);
-  } else if (p <= 4) {
-    MFX_RBF_LAUNCH(4);
-  } else {
-    MFX_RBF_LAUNCH(8);
-  }
-#undef MFX_RBF_LAUNCH
+// the operator's own prepared X (rbf_prep's output in the carved workspace)
+template <typename T>
+static Points<T> own_points(const mfx_operator* op, const RbfWs& w) {
+  return {(const T*)w.xs, (const T*)w.sq, op->n};
+}
+
+// Another point set (X_new of the cross-covariance, the two sets of a Gram block) is prepared in the caller's workspace:
+// points_carve takes its x (m, dpad) and sq (m), es bytes per element, from cv; points_ws_bytes is the size of that; points_prep
+// fills it.  On every call: the PrepScope cache of rbf_prep is for the operator's own X alone.
+struct PointsWs {
+  void *x, *sq;
+};
+static PointsWs points_carve(Carver& cv, const mfx_operator* op, int64_t m, size_t es) {
+  const int dpad = rbf_dpad(op->d) > 0 ? rbf_dpad(op->d) : 1;  // (a size query answers for a d that the entry points refuse)
+  PointsWs w;
+  w.x = cv.take(m * dpad * es);
+  w.sq = cv.take(m * es);
+  return w;
+}
+static int64_t points_ws_bytes(const mfx_operator* op, int64_t m) {
+  Carver cv(nullptr, 0);
+  points_carve(cv, op, m, dtype_size(op->dtype));
+  return cv.off;
+}
+template <typename T>
+static int points_prep(const mfx_operator* op, const T* raw, int64_t m, const PointsWs& w, hipStream_t stream, Points<T>* out) {
+  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(raw, m, op->d, rbf_dpad(op->d), (const T*)op->lengthscale, op->ard,
+                                                                (T*)w.x, (T*)w.sq);
   MFX_CHECK_LAUNCH();
+  *out = {(const T*)w.x, (const T*)w.sq, m};
   return MFX_OK;
 }
 
+// y (p, rows.m) = s K(rows, cols) x with x (p, cols.m): the VALU matvec of every entry point.  row0 >= 0: rows are the points
+// row0 .. row0 + rows.m of cols -- the square Gram operator or a row block of it, noise on the diagonal; row0 = -1: two different
+// point sets (K(X_new, X) v, K(X, X_new) u), noise not read.
 template <typename T>
-static int rbf_apply_wide(const mfx_operator* op, const RbfWs& w, int dpad, const T* x, int64_t ldx, T* y, int64_t ldy, int64_t p,
-                          hipStream_t stream, const T* xrow = nullptr, const T* sqrow = nullptr, int64_t m = 0) {
-  int64_t row0 = -1;
-  if (!xrow) {
-    row0 = op_row0(op);
-    m = op_nrows(op);
-    xrow = (const T*)w.xs + row0 * dpad;
-    sqrow = (const T*)w.sq + row0;
-  }
-  const unsigned gx = (unsigned)((m + 255) / 256);
-#define MFX_RBF_LAUNCH(PB)                                                                                 \
-  k_rbf_apply_wide<T, PB><<<dim3(gx, (unsigned)((p + PB - 1) / PB)), 256, 0, stream>>>(                     \
-      (const T*)w.xs, (const T*)w.sq, op->n, dpad, (const T*)op->outputscale, (const T*)op->noise, x, ldx, y, ldy, p, \
-      op->kernel_fn, xrow, sqrow, m, row0)
-  if (p == 1) {
-    MFX_RBF_LAUNCH(1);
-  } else if (p <= 4 || sizeof(T) == 8) {  // (8 fp64 vectors next to the 32 fp64 dot products of a tile would spill)
-    MFX_RBF_LAUNCH(4);
-  } else {
-    if constexpr (sizeof(T) == 4) MFX_RBF_LAUNCH(8);
-  }
-#undef MFX_RBF_LAUNCH
+static int rbf_apply_valu(int dpad, const Points<T>& rows, const Points<T>& cols, const T* outputscale, const T* noise, int64_t row0,
+                          int kind, const T* x, int64_t ldx, T* y, int64_t ldy, int64_t p, hipStream_t stream) {
+  auto grid = [&](int pb) { return dim3((unsigned)((rows.m + 255) / 256), (unsigned)((p + pb - 1) / pb)); };
+  with_dpad(
+      dpad,
+      [&](auto dc) {
+        with_apply_pb(p, [&](auto pb) {
+          k_rbf_apply<T, decltype(dc)::value, decltype(pb)::value><<<grid(pb), 256, 0, stream>>>(
+              cols.x, cols.sq, cols.m, outputscale, noise, x, ldx, y, ldy, p, kind, rows.x, rows.sq, rows.m, row0);
+        });
+      },
+      [&] {
+        with_apply_wide_pb<T>(p, [&](auto pb) {
+          k_rbf_apply_wide<T, decltype(pb)::value><<<grid(pb), 256, 0, stream>>>(
+              cols.x, cols.sq, cols.m, dpad, outputscale, noise, x, ldx, y, ldy, p, kind, rows.x, rows.sq, rows.m, row0);
+        });
+      });
   MFX_CHECK_LAUNCH();
   return MFX_OK;
 }
@@ -1140,14 +1187,11 @@ static int rbf_apply(const mfx_operator* op, const T* x, int64_t ldx, T* y, int6
     if (rbf_mfma_exact_wide_supported(op, p))
       return rbf_mfma_apply(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, stream);
   }
-  switch (dpad) {
-    case 4: return rbf_apply_d<T, 4>(op, w, x, ldx, y, ldy, p, stream);
-    case 8: return rbf_apply_d<T, 8>(op, w, x, ldx, y, ldy, p, stream);
-    case 12: return rbf_apply_d<T, 12>(op, w, x, ldx, y, ldy, p, stream);
-    case 16: return rbf_apply_d<T, 16>(op, w, x, ldx, y, ldy, p, stream);
-    case 32: return rbf_apply_d<T, 32>(op, w, x, ldx, y, ldy, p, stream);
-    default: return rbf_apply_wide<T>(op, w, dpad, x, ldx, y, ldy, p, stream);
-  }
+  const Points<T> X = own_points<T>(op, w);
+  const int64_t row0 = op_row0(op);
+  const Points<T> rows{X.x + row0 * dpad, X.sq + row0, op_nrows(op)};  // the operator's row block: a view into its own points
+  return rbf_apply_valu<T>(dpad, rows, X, (const T*)op->outputscale, (const T*)op->noise, row0, op->kernel_fn, x, ldx, y, ldy, p,
+                           stream);
 }
 
 // y (p, m) = K(X_new, X) v: the cross-covariance matvec of the posterior mean (util/gp_util.py:299-305), no noise term
@@ -1159,28 +1203,16 @@ static int rbf_cross_apply(const mfx_operator* op, const T* xnew, int64_t m, con
   RbfWs w;
   const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
   Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
-  T* xr = (T*)cv.take(m * dpad * sizeof(T));
-  T* sqr = (T*)cv.take(m * sizeof(T));
+  const PointsWs nw = points_carve(cv, op, m, sizeof(T));
   MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "cross-Gram workspace too small");
   MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
-  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
-                                                                xr, sqr);
-  MFX_CHECK_LAUNCH();
-  switch (dpad) {
-    case 4: return rbf_apply_d<T, 4>(op, w, v, ldv, y, ldy, p, stream, xr, sqr, m);
-    case 8: return rbf_apply_d<T, 8>(op, w, v, ldv, y, ldy, p, stream, xr, sqr, m);
-    case 12: return rbf_apply_d<T, 12>(op, w, v, ldv, y, ldy, p, stream, xr, sqr, m);
-    case 16: return rbf_apply_d<T, 16>(op, w, v, ldv, y, ldy, p, stream, xr, sqr, m);
-    case 32: return rbf_apply_d<T, 32>(op, w, v, ldv, y, ldy, p, stream, xr, sqr, m);
-    default: return rbf_apply_wide<T>(op, w, dpad, v, ldv, y, ldy, p, stream, xr, sqr, m);
-  }
+  Points<T> Xnew;
+  MFX_TRY(points_prep<T>(op, xnew, m, nw, stream, &Xnew));
+  return rbf_apply_valu<T>(dpad, Xnew, own_points<T>(op, w), (const T*)op->outputscale, (const T*)op->noise, -1, op->kernel_fn, v,
+                           ldv, y, ldy, p, stream);
 }
 
-int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m) {
-  const int dpad = rbf_dpad(op->d);
-  return rbf_carve(op, nullptr, 0, nullptr) + align_up(m * (dpad > 0 ? dpad : 1) * dtype_size(op->dtype), 256) +
-         align_up(m * dtype_size(op->dtype), 256);
-}
+int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m) { return rbf_carve(op, nullptr, 0, nullptr) + points_ws_bytes(op, m); }
 
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream) {
@@ -1220,21 +1252,16 @@ static int rbf_grad(const mfx_operator* op, const T* L, int64_t ldl, const T* R,
     }
   }
   if (!done) {
-#define MFX_RBF_GRAD(D)                                                                                    \
-  k_rbf_grad<T, D><<<(unsigned)nblocks, 256, 0, stream>>>((const T*)w.xs, (const T*)w.sq, op->n, op->ard, op->kernel_fn, L, ldl, R, \
-                                                           ldr, batch, w.partial, row0, nrow)
-    switch (dpad) {
-      case 4: MFX_RBF_GRAD(4); break;
-      case 8: MFX_RBF_GRAD(8); break;
-      case 12: MFX_RBF_GRAD(12); break;
-      case 16: MFX_RBF_GRAD(16); break;
-      case 32: MFX_RBF_GRAD(32); break;
-      default:
-        k_rbf_grad_wide<T><<<dim3((unsigned)nblocks, op->ard ? (unsigned)(dpad / kWideGC) : 1u), 256, 0, stream>>>(
-            (const T*)w.xs, (const T*)w.sq, op->n, dpad, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, w.partial, row0, nrow);
-        break;
-    }
-#undef MFX_RBF_GRAD
+    with_dpad(
+        dpad,
+        [&](auto dc) {
+          k_rbf_grad<T, decltype(dc)::value><<<(unsigned)nblocks, 256, 0, stream>>>(
+              (const T*)w.xs, (const T*)w.sq, op->n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, w.partial, row0, nrow);
+        },
+        [&] {
+          k_rbf_grad_wide<T><<<dim3((unsigned)nblocks, op->ard ? (unsigned)(dpad / kWideGC) : 1u), 256, 0, stream>>>(
+              (const T*)w.xs, (const T*)w.sq, op->n, dpad, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, w.partial, row0, nrow);
+        });
     MFX_CHECK_LAUNCH();
   }
   k_rbf_grad_final<T><<<dpad + 2, 256, 0, stream>>>(w.partial, nblocks, dpad, op->d, op->ard, (const T*)op->lengthscale,
@@ -1255,23 +1282,18 @@ static int rbf_grad_x(const mfx_operator* op, const T* L, int64_t ldl, const T* 
   MFX_REQUIRE(rbf_carve(op, ws, ws_bytes, &w, batch) <= ws_bytes && ws, MFX_ERR_WORKSPACE, "RBF workspace too small");
   MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
   const unsigned nblocks = (unsigned)((op->n + 255) / 256);
-#define MFX_RBF_GRAD_X(D)                                                                                                    \
-  k_rbf_grad_x<T, D><<<nblocks, 256, 0, stream>>>((const T*)w.xs, (const T*)w.sq, op->n, op->d, op->ard, op->kernel_fn, L, ldl, \
-                                                  R, ldr, batch, (const T*)op->lengthscale, (const T*)op->outputscale,      \
-                                                  (T*)grads->x)
-  switch (dpad) {
-    case 4: MFX_RBF_GRAD_X(4); break;
-    case 8: MFX_RBF_GRAD_X(8); break;
-    case 12: MFX_RBF_GRAD_X(12); break;
-    case 16: MFX_RBF_GRAD_X(16); break;
-    case 32: MFX_RBF_GRAD_X(32); break;
-    default:
-      k_rbf_grad_x_wide<T><<<dim3(nblocks, (unsigned)(dpad / kWideGC)), 256, 0, stream>>>(
-          (const T*)w.xs, (const T*)w.sq, op->n, dpad, op->d, op->ard, op->kernel_fn, L, ldl, R, ldr, batch,
-          (const T*)op->lengthscale, (const T*)op->outputscale, (T*)grads->x);
-      break;
-  }
-#undef MFX_RBF_GRAD_X
+  with_dpad(
+      dpad,
+      [&](auto dc) {
+        k_rbf_grad_x<T, decltype(dc)::value><<<nblocks, 256, 0, stream>>>(
+            (const T*)w.xs, (const T*)w.sq, op->n, op->d, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, (const T*)op->lengthscale,
+            (const T*)op->outputscale, (T*)grads->x);
+      },
+      [&] {
+        k_rbf_grad_x_wide<T><<<dim3(nblocks, (unsigned)(dpad / kWideGC)), 256, 0, stream>>>(
+            (const T*)w.xs, (const T*)w.sq, op->n, dpad, op->d, op->ard, op->kernel_fn, L, ldl, R, ldr, batch,
+            (const T*)op->lengthscale, (const T*)op->outputscale, (T*)grads->x);
+      });
   MFX_CHECK_LAUNCH();
   return MFX_OK;
 }
@@ -1304,54 +1326,13 @@ static int rbf_cross_apply_t(const mfx_operator* op, const T* xnew, int64_t m, c
   RbfWs w;
   const int64_t base = rbf_carve(op, ws, ws_bytes, &w);
   Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
-  T* xr = (T*)cv.take(m * dpad * sizeof(T));
-  T* sqr = (T*)cv.take(m * sizeof(T));
+  const PointsWs nw = points_carve(cv, op, m, sizeof(T));
   MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "cross-Gram workspace too small");
   MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
-  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
-                                                                xr, sqr);
-  MFX_CHECK_LAUNCH();
-  const T *s = (const T*)op->outputscale, *xrow = (const T*)w.xs, *sqrow = (const T*)w.sq;
-  const int64_t nrow = op->n;
-  const unsigned gx = (unsigned)((nrow + 255) / 256);
-  if (dpad <= 32) {
-#define MFX_RBF_T_LAUNCH(D, PB)                                                                                                \
-  k_rbf_apply<T, D, PB><<<dim3(gx, (unsigned)((p + PB - 1) / PB)), 256, 0, stream>>>(xr, sqr, m, s, s, u, ldu, y, ldy, p,      \
-                                                                                      op->kernel_fn, xrow, sqrow, nrow, -1)
-#define MFX_RBF_T_D(D)              \
-  if (p == 1) {                     \
-    MFX_RBF_T_LAUNCH(D, 1);         \
-  } else if (p == 2) {              \
-    MFX_RBF_T_LAUNCH(D, 2);         \
-  } else if (p <= 4) {              \
-    MFX_RBF_T_LAUNCH(D, 4);         \
-  } else {                          \
-    MFX_RBF_T_LAUNCH(D, 8);         \
-  }
-    switch (dpad) {
-      case 4: MFX_RBF_T_D(4); break;
-      case 8: MFX_RBF_T_D(8); break;
-      case 12: MFX_RBF_T_D(12); break;
-      case 16: MFX_RBF_T_D(16); break;
-      default: MFX_RBF_T_D(32); break;
-    }
-#undef MFX_RBF_T_D
-#undef MFX_RBF_T_LAUNCH
-  } else {
-#define MFX_RBF_T_LAUNCH(PB)                                                                                                      \
-  k_rbf_apply_wide<T, PB><<<dim3(gx, (unsigned)((p + PB - 1) / PB)), 256, 0, stream>>>(xr, sqr, m, dpad, s, s, u, ldu, y, ldy, p, \
-                                                                                        op->kernel_fn, xrow, sqrow, nrow, -1)
-    if (p == 1) {
-      MFX_RBF_T_LAUNCH(1);
-    } else if (p <= 4 || sizeof(T) == 8) {
-      MFX_RBF_T_LAUNCH(4);
-    } else {
-      if constexpr (sizeof(T) == 4) MFX_RBF_T_LAUNCH(8);
-    }
-#undef MFX_RBF_T_LAUNCH
-  }
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  Points<T> Xnew;
+  MFX_TRY(points_prep<T>(op, xnew, m, nw, stream, &Xnew));
+  const T* s = (const T*)op->outputscale;
+  return rbf_apply_valu<T>(dpad, own_points<T>(op, w), Xnew, s, /* noise, not read: */ s, -1, op->kernel_fn, u, ldu, y, ldy, p, stream);
 }
 
 int op_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const void* u, int64_t ldu, void* y, int64_t ldy,
@@ -1398,66 +1379,61 @@ static int64_t cross_vjp_extra(const mfx_operator* op, int64_t m, int64_t* theta
   }
   if (theta_bytes) *theta_bytes = tb;
   if (gpart_bytes) *gpart_bytes = gb;
-  const size_t es = dtype_size(op->dtype);
-  return align_up(m * dpad * es, 256) + align_up(m * es, 256) + align_up(tb, 256) + align_up(gb, 256);
+  return points_ws_bytes(op, m) + align_up(tb, 256) + align_up(gb, 256);
 }
 
 int64_t rbf_cross_vjp_ws_bytes(const mfx_operator* op, int64_t m) {
   return rbf_carve(op, nullptr, 0, nullptr) + cross_vjp_extra(op, m, nullptr, nullptr);
 }
 
-// one sweep with owner rows (xo, sqo, mo) against the columns (xc, sqc, nc); src gives S (owners x columns): FactoredSrc with
-// L (batch, mo), R (batch, nc), or DenseSrc.  The l / s sums and the owner gradient share one sweep where both sets of fp64 sums
+// one sweep with the owner rows `own` against the columns `col`; src gives S (owners x columns): FactoredSrc with
+// L (batch, own.m), R (batch, col.m), or DenseSrc.  The l / s sums and the owner gradient share one sweep where both sets of fp64 sums
 // fit the registers (d <= 16); at padded d = 32 and for wide inputs the shared form spills (34 registers at DPAD 32 in fp32), so
 // there they are two sweeps.
 template <typename T, typename Src>
-static int cross_sweep(const mfx_operator* op, int dpad, const T* xo, const T* sqo, int64_t mo, const T* xc, const T* sqc, int64_t nc,
-                       const Src& src, bool theta, T* go, double* gpart, double* partial, int64_t* nblocks, hipStream_t stream) {
+static int cross_sweep(const mfx_operator* op, int dpad, const Points<T>& own, const Points<T>& col, const Src& src, bool theta, T* go,
+                       double* gpart, double* partial, int64_t* nblocks, hipStream_t stream) {
   const bool shared = dpad < 32;
   if (theta && go && !shared) {
-    MFX_TRY(cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, src, true, nullptr, gpart, partial, nblocks, stream));
-    return cross_sweep<T>(op, dpad, xo, sqo, mo, xc, sqc, nc, src, false, go, gpart, partial, nblocks, stream);
+    MFX_TRY(cross_sweep<T>(op, dpad, own, col, src, true, nullptr, gpart, partial, nblocks, stream));
+    return cross_sweep<T>(op, dpad, own, col, src, false, go, gpart, partial, nblocks, stream);
   }
+  const int64_t mo = own.m;
   const int64_t sel = dpad > 32 && (op->ard || go) ? dpad / kWideGC : 1;
-  const CrossPlan pl = cross_plan(mo, nc, sel);
+  const CrossPlan pl = cross_plan(mo, col.m, sel);
   T* gdirect = pl.gy == 1 ? go : nullptr;
   double* gp = go && pl.gy > 1 ? gpart : nullptr;
   if (theta) *nblocks = pl.gx * pl.gy;
   const T *ls = (const T*)op->lengthscale, *s = (const T*)op->outputscale;
-  if (dpad <= 32) {
-    const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
-#define MFX_CROSS_GRAD(D, TH, GX)                                                                                                \
-  k_rbf_cross_grad<T, D, TH, GX, Src><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, op->d, op->ard, op->kernel_fn, \
-                                                                src, ls, s, gdirect, gp, partial)
-#define MFX_CROSS_GRAD_D(D)                      \
-  if (!go) {                                     \
-    MFX_CROSS_GRAD(D, true, false);              \
-  } else if (!theta) {                           \
-    MFX_CROSS_GRAD(D, false, true);              \
-  } else {                                       \
-    if constexpr (D < 32) MFX_CROSS_GRAD(D, true, true); \
-  }
-    switch (dpad) {
-      case 4: MFX_CROSS_GRAD_D(4); break;
-      case 8: MFX_CROSS_GRAD_D(8); break;
-      case 12: MFX_CROSS_GRAD_D(12); break;
-      case 16: MFX_CROSS_GRAD_D(16); break;
-      default: MFX_CROSS_GRAD_D(32); break;
-    }
-#undef MFX_CROSS_GRAD_D
-#undef MFX_CROSS_GRAD
-  } else {
-    const dim3 grid((unsigned)pl.gx, (unsigned)sel, (unsigned)pl.gy);
-#define MFX_CROSS_GRAD_W(TH, GX)                                                                                               \
-  k_rbf_cross_grad_wide<T, TH, GX, Src><<<grid, 256, 0, stream>>>(xo, sqo, mo, xc, sqc, nc, pl.chunk, dpad, op->d, op->ard,    \
-                                                                  op->kernel_fn, src, ls, s, gdirect, gp, partial)
-    if (!go) {
-      MFX_CROSS_GRAD_W(true, false);
-    } else {
-      MFX_CROSS_GRAD_W(false, true);
-    }
-#undef MFX_CROSS_GRAD_W
-  }
+  with_dpad(
+      dpad,
+      [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+        auto launch = [&](auto th, auto gx) {
+          k_rbf_cross_grad<T, D, decltype(th)::value, decltype(gx)::value, Src><<<grid, 256, 0, stream>>>(
+              own.x, own.sq, mo, col.x, col.sq, col.m, pl.chunk, op->d, op->ard, op->kernel_fn, src, ls, s, gdirect, gp, partial);
+        };
+        if (!go) {
+          launch(std::true_type{}, std::false_type{});
+        } else if (!theta) {
+          launch(std::false_type{}, std::true_type{});
+        } else {
+          if constexpr (D < 32) launch(std::true_type{}, std::true_type{});
+        }
+      },
+      [&] {
+        const dim3 grid((unsigned)pl.gx, (unsigned)sel, (unsigned)pl.gy);
+        auto launch = [&](auto th, auto gx) {
+          k_rbf_cross_grad_wide<T, decltype(th)::value, decltype(gx)::value, Src><<<grid, 256, 0, stream>>>(
+              own.x, own.sq, mo, col.x, col.sq, col.m, pl.chunk, dpad, op->d, op->ard, op->kernel_fn, src, ls, s, gdirect, gp, partial);
+        };
+        if (!go) {
+          launch(std::true_type{}, std::false_type{});
+        } else {
+          launch(std::false_type{}, std::true_type{});
+        }
+      });
   MFX_CHECK_LAUNCH();
   if (gp) {
     k_rbf_cross_gx_final<T><<<(unsigned)((mo * op->d + 255) / 256), 256, 0, stream>>>(gp, pl.gy, mo, dpad, op->d, op->ard, ls, s, go);
@@ -1479,8 +1455,7 @@ static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const
   int64_t tb = 0, gb = 0;
   cross_vjp_extra(op, m, &tb, &gb);
   Carver cv(ws ? (char*)ws + base : nullptr, ws_bytes - base);
-  T* xr = (T*)cv.take(m * dpad * sizeof(T));
-  T* sqr = (T*)cv.take(m * sizeof(T));
+  const PointsWs nw = points_carve(cv, op, m, sizeof(T));
   double* partial = (double*)cv.take(tb);
   double* gpart = (double*)cv.take(gb);
   MFX_REQUIRE(ws && base + cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "%scross-covariance VJP workspace too small", what);
@@ -1488,14 +1463,12 @@ static int rbf_cross_vjp(const mfx_operator* op, const T* xnew, int64_t m, const
   T* gx = (T*)grads->x;
   if (!theta && !gx && !gxnew) return MFX_OK;
   MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
-  k_rbf_prep<T><<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(xnew, m, op->d, dpad, (const T*)op->lengthscale, op->ard,
-                                                                xr, sqr);
-  MFX_CHECK_LAUNCH();
-  const T *xs = (const T*)w.xs, *sq = (const T*)w.sq;
+  Points<T> Xnew;
+  MFX_TRY(points_prep<T>(op, xnew, m, nw, stream, &Xnew));
+  const Points<T> X = own_points<T>(op, w);
   int64_t nblocks = 0;
-  if (gxnew || (theta && !gx))
-    MFX_TRY(cross_sweep<T>(op, dpad, xr, sqr, m, xs, sq, op->n, by_new, theta, gxnew, gpart, partial, &nblocks, stream));
-  if (gx) MFX_TRY(cross_sweep<T>(op, dpad, xs, sq, op->n, xr, sqr, m, by_x, theta && !gxnew, gx, gpart, partial, &nblocks, stream));
+  if (gxnew || (theta && !gx)) MFX_TRY(cross_sweep<T>(op, dpad, Xnew, X, by_new, theta, gxnew, gpart, partial, &nblocks, stream));
+  if (gx) MFX_TRY(cross_sweep<T>(op, dpad, X, Xnew, by_x, theta && !gxnew, gx, gpart, partial, &nblocks, stream));
   if (theta) {
     k_rbf_grad_final<T><<<dpad + 2, 256, 0, stream>>>(partial, nblocks, dpad, op->d, op->ard, (const T*)op->lengthscale,
                                                       (const T*)op->outputscale, (T*)grads->lengthscale, (T*)grads->outputscale,
@@ -1807,21 +1780,17 @@ __global__ __launch_bounds__(256) void k_gram_block_wide(const T* __restrict__ x
   gram_block_store<T>(tile, a0, ma, b0, mb, out, ldo);
 }
 
-// workspace: the scaled, zero-padded copies of xa and xb and their squared norms (the carve of the cross-covariance matvec for
-// its X_new, once per point set; the symmetric block leaves the second pair unused)
+// workspace: the prepared forms of xa and xb (the symmetric block leaves the second unused)
 struct BlockWs {
-  void *xa, *sqa, *xb, *sqb;
+  PointsWs a, b;
 };
 static int64_t gram_block_carve(const mfx_operator* op, int64_t ma, int64_t mb, void* ws, int64_t ws_bytes, BlockWs* out) {
-  const int64_t es = (int64_t)dtype_size(op->dtype);
-  const int64_t dpad = rbf_dpad(op->d) > 0 ? rbf_dpad(op->d) : 1;
+  const size_t es = dtype_size(op->dtype);
   Carver cv(ws, ws_bytes);
-  BlockWs b;
-  b.xa = cv.take(ma * dpad * es);
-  b.sqa = cv.take(ma * es);
-  b.xb = cv.take(mb * dpad * es);
-  b.sqb = cv.take(mb * es);
-  if (out) *out = b;
+  BlockWs w;
+  w.a = points_carve(cv, op, ma, es);
+  w.b = points_carve(cv, op, mb, es);
+  if (out) *out = w;
   return cv.off;
 }
 
@@ -1829,33 +1798,19 @@ template <typename T>
 static int gram_block_t(const mfx_operator* op, const T* xa, int64_t ma, const T* xb, int64_t mb, T* out, int64_t ldo,
                         const BlockWs& w, hipStream_t stream) {
   const int dpad = rbf_dpad(op->d);
-  const T* ls = (const T*)op->lengthscale;
   const int sym = xb == nullptr;
-  T *xar = (T*)w.xa, *sqar = (T*)w.sqa;
-  k_rbf_prep<T><<<(unsigned)((ma + 255) / 256), 256, 0, stream>>>(xa, ma, op->d, dpad, ls, op->ard, xar, sqar);
-  MFX_CHECK_LAUNCH();
-  const T *xbr = xar, *sqbr = sqar;
-  if (!sym) {
-    k_rbf_prep<T><<<(unsigned)((mb + 255) / 256), 256, 0, stream>>>(xb, mb, op->d, dpad, ls, op->ard, (T*)w.xb, (T*)w.sqb);
-    MFX_CHECK_LAUNCH();
-    xbr = (const T*)w.xb;
-    sqbr = (const T*)w.sqb;
-  }
+  Points<T> A, B;
+  MFX_TRY(points_prep<T>(op, xa, ma, w.a, stream, &A));
+  B = A;
+  if (!sym) MFX_TRY(points_prep<T>(op, xb, mb, w.b, stream, &B));
   const dim3 grid((unsigned)((mb + kBlkT - 1) / kBlkT), (unsigned)((ma + kBlkT - 1) / kBlkT));
   const T* s = (const T*)op->outputscale;
-#define MFX_GRAM_BLOCK(D) \
-  k_gram_block<T, D><<<grid, 256, 0, stream>>>(xar, sqar, ma, xbr, sqbr, mb, s, op->kernel_fn, sym, out, ldo)
-  switch (dpad) {
-    case 4: MFX_GRAM_BLOCK(4); break;
-    case 8: MFX_GRAM_BLOCK(8); break;
-    case 12: MFX_GRAM_BLOCK(12); break;
-    case 16: MFX_GRAM_BLOCK(16); break;
-    case 32: MFX_GRAM_BLOCK(32); break;
-    default:
-      k_gram_block_wide<T><<<grid, 256, 0, stream>>>(xar, sqar, ma, xbr, sqbr, mb, dpad, s, op->kernel_fn, sym, out, ldo);
-      break;
-  }
-#undef MFX_GRAM_BLOCK
+  with_dpad(
+      dpad,
+      [&](auto dc) {
+        k_gram_block<T, decltype(dc)::value><<<grid, 256, 0, stream>>>(A.x, A.sq, ma, B.x, B.sq, mb, s, op->kernel_fn, sym, out, ldo);
+      },
+      [&] { k_gram_block_wide<T><<<grid, 256, 0, stream>>>(A.x, A.sq, ma, B.x, B.sq, mb, dpad, s, op->kernel_fn, sym, out, ldo); });
   MFX_CHECK_LAUNCH();
   return MFX_OK;
 }

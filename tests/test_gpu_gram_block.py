@@ -97,7 +97,7 @@ def identity_block(xa, xb, kind, raw):
 
 
 SHAPES = [(1, 1), (63, 65), (64, 64), (65, 257), (300, 37)]
-DIMS = [(1, False), (3, False), (9, True), (20, False), (40, True)]  # register path (4, 4, 12), padded 32, wide (64)
+DIMS = [(1, False), (3, False), (8, False), (9, True), (16, True), (20, False), (40, True)]  # register path (4, 4, 8, 12, 16), padded 32, wide (64)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["fp64", "fp32"])

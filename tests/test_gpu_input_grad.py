@@ -90,6 +90,7 @@ CASES = [
     ("matern12", True, torch.float32, "fp32", 8, 300, 16, False),
     ("matern32", True, torch.float64, "f16x3", 8, 300, 40, True),  # two batch chunks of 32, the second partial
     ("rbf", False, torch.float32, "f16x3", 40, 300, 40, False),
+    ("rbf", True, torch.float64, "f16x3", 24, 300, 3, False),  # padded d = 32 in fp64
 ]
 
 

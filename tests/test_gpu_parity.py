@@ -117,7 +117,9 @@ def test_csr_skewed_rows_pick_the_step_kernel_by_the_longest_row(skew):
                                    # d <= 4 ON the matrix-core gradient kernels (batch > 32 or n >= 2048): the register epilogue of the split
                                    # GEMM with its 2-MFMA distance chain -- wrong by O(1) in rounds 2-4 for non-ARD RBF (an inline-asm v_exp
                                    # read the distance block before the MFMA had written it), never reached by the small d = 3 case above
-                                   (2100, 2, 40), (2304, 4, 3), (700, 3, 33)])
+                                   (2100, 2, 40), (2304, 4, 3), (700, 3, 33),
+                                   # padded d = 12 and 16 with 2 and 3 vectors: the VALU matvec and sweep in fp32 as well (n < 2048)
+                                   (300, 11, 2), (300, 16, 3)])
 def test_rbf_op_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kernel):
     """p >= 4 in fp32 takes the MFMA kernels (exact fp32 or the 3 x f16 split), everything else the VALU kernel;
     kernels: util/gp_util.py:69-184 (scaled RBF, Matern-3/2, Matern-1/2)."""
@@ -148,7 +150,9 @@ def test_rbf_op_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kerne
                                    # 16 < d <= 128 in fp32 with >= 4 vectors (or n >= 2048): the exact-fp32 matrix-core matvec in EVERY mode;
                                    # d <= 32 and batch >= 16 (or n >= 2048): the exact-fp32 matrix-core sweep as well
                                    (600, 20, 8), (2304, 32, 3), (900, 27, 40), (520, 50, 8), (2100, 64, 5), (1000, 40, 70), (777, 17, 33),
-                                   (2100, 128, 5), (640, 97, 70), (300, 129, 8)])
+                                   (2100, 128, 5), (640, 97, 70), (300, 129, 8),
+                                   # padded d = 32 with 2 vectors at n < 2048: the VALU matvec and sweep in fp32 as well
+                                   (300, 24, 2)])
 def test_rbf_wide_inputs_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kernel):
     """d > 32: the reference's kernels take any input dimension (util/gp_util.py:151-184) and its UCI loaders reach d = 90 (song) and
     385 (slice) (util/uci_util.py:85-99,303-310).  The wide kernels of csrc/mfx_ops.hip (distance as a small GEMM over chunks of the d

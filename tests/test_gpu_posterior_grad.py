@@ -82,7 +82,7 @@ def check(got, want, scale, tol, what):
     assert float(err.max()) <= tol, (what, float(err.max()))
 
 
-# (kernel, ard, dtype, d, m, n, p, duplicates): every kernel, both lengthscale forms and dtypes, d in {1, 3, 8, 17, 40} -- the
+# (kernel, ard, dtype, d, m, n, p, duplicates): every kernel, both lengthscale forms and dtypes, d in {1, 3, 8, 11, 16, 17, 40} -- the
 # register sweeps with the shared and the separate lengthscale / input forms (padded d <= 16 and 32) and the wide sweep
 CASES = [
     ("rbf", True, torch.float64, 3, 70, 700, 3, True),
@@ -99,6 +99,10 @@ CASES = [
     ("matern12", True, torch.float32, 40, 333, 2049, 3, True),
     ("matern32", False, torch.float32, 1, 70, 700, 9, True),
     ("rbf", True, torch.float32, 17, 70, 700, 1, False),
+    ("matern32", True, torch.float64, 11, 70, 300, 2, True),  # padded d = 12 and 16
+    ("rbf", False, torch.float64, 16, 70, 300, 5, False),
+    ("rbf", True, torch.float32, 11, 70, 300, 5, True),
+    ("matern32", False, torch.float32, 16, 70, 300, 2, False),
 ]
 
 
@@ -144,6 +148,30 @@ def test_cross_vjp_matches_fp64_autograd(kind, ard, dtype, d, m, n, p, dups):
     check(gx, rx, t_x, tol, "X")
     check(gl.reshape(-1), rl * sig_l, (t_ls if ard else t_ls.sum()) * sig_l, tol, "lengthscale")
     check(gs, rs * sig_s, t_s * sig_s, tol, "outputscale")
+
+
+# The VALU matvec picks its kernel from the padded dimension (d = 3, 8, 11, 16, 24 pad to 4, 8, 12, 16, 32; 40 is wide) and the
+# vectors per workgroup from p (1, 2, 3, 9 -> 1, 2, 4, 8, the last two with a ragged last chunk; wide: 1, 4 and, in fp32 only, 8):
+# every pair in both dtypes, forward (rows X_new, columns X) and transposed (rows X, columns X_new); m != n, neither a tile multiple
+MATVEC = [(dtype, d, p) for dtype in (torch.float64, torch.float32) for d in (3, 8, 11, 16, 24, 40) for p in (1, 2, 3, 9)
+          if d < 40 or p in (1, 3) or (p == 9 and dtype == torch.float32)]
+
+
+@pytest.mark.parametrize("dtype,d,p", MATVEC, ids=[f"{'fp64' if t == torch.float64 else 'fp32'}-d{d}-p{p}" for t, d, p in MATVEC])
+def test_cross_matvec_and_its_transpose_at_every_padded_dimension_and_vector_count(dtype, d, p):
+    kind, m, n = ("rbf", "matern32")[(d + p) % 2], 70, 300
+    X0, Xn0, V0, Ybar = _problem(d, m, n, p, True, dtype, seed=10 * d + p)
+    raw = raw_params(d, True)
+    V = V0.to(dtype).requires_grad_(True)
+    y = RbfGramOp(X0.to(dtype), kernel=kind).cross_apply(Xn0, V, *raw)
+    (gv,) = torch.autograd.grad((Ybar.to(dtype) * y).sum(), V)  # K(X, X_new) ybar: mfx_gram_cross_apply_t
+    assert y.shape == (p, m) and gv.shape == (p, n)
+    with torch.no_grad():
+        sp = torch.nn.functional.softplus
+        ls, s = sp(raw[0]).to(dtype).double().reshape(-1), sp(raw[1]).to(dtype).double()
+        K = ref_cross(Xn0, X0, ls, s, kind, float(torch.finfo(dtype).eps))  # (m, n), every entry positive
+        check(y.double(), V0 @ K.T, V0.abs() @ K.T, TOL[dtype], "y")
+        check(gv.double(), Ybar @ K, Ybar.abs() @ K, TOL[dtype], "v")
 
 
 @pytest.mark.parametrize("d", [3, 40])

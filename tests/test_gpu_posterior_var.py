@@ -101,6 +101,10 @@ CASES = [
     ("matern12", False, torch.float32, 3, 70, 300),
     ("rbf", False, torch.float32, 40, 1, 300),
     ("matern32", True, torch.float32, 1, 333, 200),
+    ("rbf", True, torch.float64, 11, 70, 300),  # padded d = 12 and 16
+    ("matern32", False, torch.float64, 16, 70, 300),
+    ("matern32", True, torch.float32, 11, 70, 300),
+    ("rbf", False, torch.float32, 16, 70, 300),
 ]
 # (Matern-1/2 at d = 1 is fp64-only: 333 test points among 200 on a line put pairs at distances ~1e-4, where the fp32 expansion's
 # rounding of dist (~eps |x|^2) moves the weight exp(-r) / r of the input gradient by tens of percent -- measured 0.23 of the largest
