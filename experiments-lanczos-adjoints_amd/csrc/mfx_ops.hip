@@ -8,6 +8,7 @@
 
 #include "mfx_internal.h"
 #include "mfx_kernel_fn.h"
+#include "mfx_rbf.h"
 
 namespace mfx {
 
@@ -984,27 +985,8 @@ __global__ __launch_bounds__(256) void k_rbf_cross_gx_final(const double* __rest
   go[e] += (T)(-(double)outputscale[0] / (double)ls[ard ? c : 0] * acc);
 }
 
-constexpr int kRbfMaxD = 1024;  // wide inputs (d > 32): padded to a multiple of 32, k_rbf_apply_wide / k_rbf_grad_wide
-static int rbf_dpad(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 12 ? 12 : d <= 16 ? 16 : d <= kRbfMaxD ? (d + 31) / 32 * 32 : -1; }
-
-// The launch layer of the VALU kernel-Gram kernels.  Every launch site goes through with_dpad; the matvec sites also through one
-// of the two vectors-per-workgroup choosers.  A compile-time value arrives as a std::integral_constant argument of a generic lambda.
-template <int V>
-using Const = std::integral_constant<int, V>;
-
-// rbf_dpad's value as a compile-time constant: narrow(Const<DPAD>) for the register kernels (a point in DPAD registers), wide() for
-// d > 32 (the padded dimension stays a run-time argument of the *_wide kernels)
-template <typename Narrow, typename WideFn>
-static void with_dpad(int dpad, Narrow&& narrow, WideFn&& wide) {
-  switch (dpad) {
-    case 4: narrow(Const<4>{}); break;
-    case 8: narrow(Const<8>{}); break;
-    case 12: narrow(Const<12>{}); break;
-    case 16: narrow(Const<16>{}); break;
-    case 32: narrow(Const<32>{}); break;
-    default: wide(); break;
-  }
-}
+// The launch layer of the VALU kernel-Gram kernels.  Every launch site goes through with_dpad (mfx_rbf.h, with rbf_dpad and Const);
+// the matvec sites also through one of the two vectors-per-workgroup choosers.
 
 // vectors per workgroup (PB) of k_rbf_apply: launch(Const<PB>)
 template <typename Launch>
@@ -1040,10 +1022,6 @@ struct RbfWs {
   int64_t pk_bytes;
 };
 
-int64_t rbf_grad_h_ws_bytes(int64_t n, int64_t batch);
-int64_t rbf_pack_ws_bytes(const mfx_operator* op, int64_t p);
-int rbf_mode(const mfx_operator* op);
-
 static int64_t rbf_carve(const mfx_operator* op, void* ws, int64_t ws_bytes, RbfWs* out, int64_t batch_hint = 0,
                          int64_t p_apply = 0) {
   const size_t es = dtype_size(op->dtype);
@@ -1053,32 +1031,15 @@ static int64_t rbf_carve(const mfx_operator* op, void* ws, int64_t ws_bytes, Rbf
   r.xs = cv.take(op->n * (dpad > 0 ? dpad : 1) * es);
   r.sq = cv.take(op->n * es);
   // per-workgroup gradient partials: VALU sweep n/256 rows, MFMA sweep 8 * n/128 rows, <= 34 doubles each
-  r.partial = static_cast<double*>(cv.take(((op->n + 127) / 128) * 64 * (dpad > 32 && dpad <= 64 ? dpad + 2 : 34) * sizeof(double)));  // 8 XCDs x 8 sub-ranges (DPAD 64: the matrix-core sweep writes 66 per workgroup; wider: the VALU sweep, dpad + 2 per 256 rows)
-  r.vscale = static_cast<float*>(cv.take(65536 * 3 * sizeof(float)));  // [s, 1/s] per row + |max| bit patterns
-  r.hws_bytes = (op->dtype == MFX_F32 && rbf_mode(op) == MFX_RBF_F16X3 && batch_hint > 0) ? rbf_grad_h_ws_bytes(op->n, batch_hint) : 0;
+  r.partial = static_cast<double*>(cv.take(rbf_mfma_grad_partial_rows(op->n) * (dpad > 32 && dpad <= 64 ? dpad + 2 : 34) * sizeof(double)));  // 8 XCDs x 8 sub-ranges (DPAD 64: the matrix-core sweep writes 66 per workgroup; wider: the VALU sweep, dpad + 2 per 256 rows)
+  r.vscale = static_cast<float*>(cv.take(kRbfVscaleFloats * sizeof(float)));  // RbfVscaleLayout
+  r.hws_bytes = (op->dtype == MFX_F32 && op->rbf_mode == MFX_RBF_F16X3 && batch_hint > 0) ? rbf_grad_h_ws_bytes(op->n, batch_hint) : 0;
   r.hws = r.hws_bytes ? cv.take(r.hws_bytes) : nullptr;
   r.pk_bytes = (op->dtype == MFX_F32 && p_apply > 0) ? rbf_pack_ws_bytes(op, p_apply) : 0;
   r.pk = r.pk_bytes ? cv.take(r.pk_bytes) : nullptr;
   if (out) *out = r;
   return cv.off;
 }
-
-// MFMA path (mfx_rbf_mfma.hip)
-bool rbf_mfma_supported(const mfx_operator* op, int64_t p);
-int rbf_mfma_apply(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* x, int64_t ldx,
-                   float* y, int64_t ldy, int64_t p, hipStream_t stream);
-int rbf_mfma_apply_h3(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* x, int64_t ldx,
-                      float* y, int64_t ldy, int64_t p, float* vscale, void* pk, hipStream_t stream);
-int rbf_mfma_grad_h(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* L, int64_t ldl,
-                    const float* R, int64_t ldr, int64_t batch, int64_t inner, double* partial, int64_t* nblocks_out, void* hws,
-                    const float** scales_out, hipStream_t stream);
-bool rbf_mfma_grad_supported(const mfx_operator* op, int64_t batch);
-bool rbf_mfma_exact_wide_supported(const mfx_operator* op, int64_t p);         // 16 < d <= 128: the exact-fp32 kernels, in every mode
-bool rbf_mfma_h3_wide_supported(const mfx_operator* op, int64_t p);            // 16 < d <= 32, split modes: fp32 distances + f16x3 contraction
-bool rbf_mfma_grad_exact_wide_supported(const mfx_operator* op, int64_t batch);  // 16 < d <= 64
-int rbf_mfma_grad(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* L, int64_t ldl,
-                  const float* R, int64_t ldr, int64_t batch, double* partial, int64_t* nblocks_out,
-                  hipStream_t stream);
 
 // what the last k_rbf_prep inside the current PrepScope of this thread prepared (null: nothing yet)
 struct PrepKey {
@@ -1173,19 +1134,13 @@ static int rbf_apply(const mfx_operator* op, const T* x, int64_t ldx, T* y, int6
   MFX_REQUIRE(rbf_carve(op, ws, ws_bytes, &w, 0, p) <= ws_bytes && ws, MFX_ERR_WORKSPACE, "RBF workspace too small");
   MFX_TRY(rbf_prep<T>(op, w, dpad, stream));
   if constexpr (sizeof(T) == 4) {
-    // 1-3 vectors (the CG solves of the log-marginal likelihood): the VALU kernel below costs 2-2.7x a matrix-core
-    // sweep over one 32-probe block (measured, n = 131072: 12.9 vs 5.9 ms), whose probe guards handle any p >= 1
-    if (p < 4 && op->n >= 2048 && rbf_mfma_supported(op, 4) && rbf_mode(op) >= MFX_RBF_F16X3_MATVEC)
-      return rbf_mfma_apply_h3(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, w.vscale, w.pk, stream);
-    if (rbf_mfma_supported(op, p)) {
-      if (rbf_mode(op) >= MFX_RBF_F16X3_MATVEC)
+    switch (rbf_apply_path(op, p)) {
+      case RbfApplyPath::h3:
         return rbf_mfma_apply_h3(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, w.vscale, w.pk, stream);
-      return rbf_mfma_apply(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, stream);
+      case RbfApplyPath::exact:
+        return rbf_mfma_apply(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, stream);
+      case RbfApplyPath::valu: break;
     }
-    if (rbf_mfma_h3_wide_supported(op, p) && rbf_mode(op) >= MFX_RBF_F16X3_MATVEC)
-      return rbf_mfma_apply_h3(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, w.vscale, w.pk, stream);
-    if (rbf_mfma_exact_wide_supported(op, p))
-      return rbf_mfma_apply(op, (const float*)w.xs, (const float*)w.sq, dpad, x, ldx, y, ldy, p, stream);
   }
   const Points<T> X = own_points<T>(op, w);
   const int64_t row0 = op_row0(op);
@@ -1237,18 +1192,18 @@ static int rbf_grad(const mfx_operator* op, const T* L, int64_t ldl, const T* R,
   bool done = false;
   const float* scales = nullptr;
   if constexpr (sizeof(T) == 4) {
-    // the split GEMM stages its packed operands through 32-bit byte offsets: 2 B x padded batch x padded n < 4 GiB
-    const bool fits32 = ((batch + 31) / 32 * 32) * ((op->n + 255) / 256 * 256) * 2 < ((int64_t)1 << 32);
-    // (16 < d <= 32: the split sweep's 256 x 128 form with 64-column epilogue passes -- 249 registers, 140 KB of LDS)
-    const bool split_ok = rbf_mfma_grad_supported(op, batch) || (rbf_mfma_grad_exact_wide_supported(op, batch) && op->d <= 32);
-    if (split_ok && rbf_mode(op) == MFX_RBF_F16X3 && w.hws && fits32) {
-      MFX_TRY(rbf_mfma_grad_h(op, (const float*)w.xs, (const float*)w.sq, dpad, L, ldl, R, ldr, batch, inner, w.partial, &nblocks,
-                              w.hws, &scales, stream));
-      done = true;
-    } else if (rbf_mfma_grad_supported(op, batch) || rbf_mfma_grad_exact_wide_supported(op, batch)) {
-      MFX_TRY(rbf_mfma_grad(op, (const float*)w.xs, (const float*)w.sq, dpad, L, ldl, R, ldr, batch, w.partial,
-                            &nblocks, stream));
-      done = true;
+    switch (rbf_grad_path(op, batch, w.hws != nullptr)) {
+      case RbfGradPath::split:
+        MFX_TRY(rbf_mfma_grad_h(op, (const float*)w.xs, (const float*)w.sq, dpad, L, ldl, R, ldr, batch, inner, w.partial, &nblocks,
+                                w.hws, &scales, stream));
+        done = true;
+        break;
+      case RbfGradPath::exact:
+        MFX_TRY(rbf_mfma_grad(op, (const float*)w.xs, (const float*)w.sq, dpad, L, ldl, R, ldr, batch, w.partial,
+                              &nblocks, stream));
+        done = true;
+        break;
+      case RbfGradPath::valu: break;
     }
   }
   if (!done) {

@@ -2,6 +2,7 @@
 // family's constants, the hi / lo f16 split, the LDS-DMA copy and the layout of the pre-packed tile images.
 #pragma once
 #include "mfx_internal.h"
+#include "mfx_rbf.h"
 
 namespace mfx {
 
@@ -106,12 +107,5 @@ struct RbfTileH3 {
   _Float16 vlo[(kTJ / 32) * 4][ROW];
 };
 
-
-// launcher of the fat-wave matvec kernel (mfx_rbf_fat.hip): RBF, d <= 8, chunks of nb * 32 vectors (nb = 1, 2);
-// grid = (ceil(rows / 512), chunks, splits)
-int rbf_fat_launch(int dpad, int nb, bool vec4, dim3 grid, hipStream_t stream, const float* xs, const float* sq, int64_t n,
-                   const float* outputscale, const float* noise, const float* vscale, const float* x, int64_t ldx, float* y,
-                   int64_t ldy, int64_t p, const void* pkv, const void* pka, float* part, const int* rangeflag, int64_t ldpart,
-                   int64_t row0, int64_t rend);
 
 }  // namespace mfx

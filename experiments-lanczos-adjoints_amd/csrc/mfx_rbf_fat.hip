@@ -428,38 +428,21 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply(const float* __restric
 #undef MFX_WN
 #undef MFX_WD
 
-template <int DPAD, int NB>
-static int fat_launch_dn(bool vec4, dim3 grid, hipStream_t stream, const float* xs, const float* sq, int64_t n,
-                         const float* outputscale, const float* noise, const float* vscale, const float* x, int64_t ldx, float* y,
-                         int64_t ldy, int64_t p, const void* pkv, const void* pka, float* part, const int* rangeflag,
-                         int64_t ldpart, int64_t row0, int64_t rend) {
-  constexpr int kSm = FatSmem<DPAD, NB>::kTotal;
-#define MFX_FAT_LAUNCH(V4)                                                                                                   \
-  k_rbf_fat_apply<DPAD, V4, NB><<<grid, 256, kSm, stream>>>(xs, sq, n, outputscale, noise, vscale, x, ldx, y, ldy, p,         \
-                                                            static_cast<const uintx4*>(pkv), static_cast<const uintx4*>(pka), \
-                                                            part, rangeflag, ldpart, row0, rend)
-  if (vec4) MFX_FAT_LAUNCH(true); else MFX_FAT_LAUNCH(false);
-#undef MFX_FAT_LAUNCH
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
-}
-
-int rbf_fat_launch(int dpad, int nb, bool vec4, dim3 grid, hipStream_t stream, const float* xs, const float* sq, int64_t n,
-                   const float* outputscale, const float* noise, const float* vscale, const float* x, int64_t ldx, float* y,
-                   int64_t ldy, int64_t p, const void* pkv, const void* pka, float* part, const int* rangeflag, int64_t ldpart,
-                   int64_t row0, int64_t rend) {
-#define MFX_FAT_ARGS vec4, grid, stream, xs, sq, n, outputscale, noise, vscale, x, ldx, y, ldy, p, pkv, pka, part, rangeflag, ldpart, row0, rend
-  if (dpad == 4 && nb == 1) return fat_launch_dn<4, 1>(MFX_FAT_ARGS);
-  if (dpad == 4 && nb == 2) return fat_launch_dn<4, 2>(MFX_FAT_ARGS);
-  if (dpad == 8 && nb == 1) return fat_launch_dn<8, 1>(MFX_FAT_ARGS);
-  if (dpad == 8 && nb == 2) return fat_launch_dn<8, 2>(MFX_FAT_ARGS);
-  if (dpad == 12 && nb == 1) return fat_launch_dn<12, 1>(MFX_FAT_ARGS);
-  if (dpad == 12 && nb == 2) return fat_launch_dn<12, 2>(MFX_FAT_ARGS);
-  if (dpad == 16 && nb == 1) return fat_launch_dn<16, 1>(MFX_FAT_ARGS);
-  if (dpad == 16 && nb == 2) return fat_launch_dn<16, 2>(MFX_FAT_ARGS);
-#undef MFX_FAT_ARGS
-  set_error("fat-wave Gram matvec supports d <= 16 and chunks of 32 or 64 vectors");
-  return MFX_ERR_UNSUPPORTED;
+int rbf_fat_launch(int dpad, int nb, bool vec4, dim3 grid, hipStream_t stream, const RbfMatvecArgs& a) {
+  const char* not_built = "fat-wave Gram matvec supports d <= 16 and chunks of 32 or 64 vectors";
+  MFX_REQUIRE(nb == 1 || nb == 2, MFX_ERR_UNSUPPORTED, "%s", not_built);
+  return with_mfma_dpad<16>(dpad, not_built, [&](auto dc) -> int {
+    return with_bool(nb == 2, [&](auto two) -> int {
+      return with_bool(vec4, [&](auto v4) -> int {
+        constexpr int DPAD = decltype(dc)::value, NB = decltype(two)::value ? 2 : 1;
+        k_rbf_fat_apply<DPAD, decltype(v4)::value, NB><<<grid, 256, FatSmem<DPAD, NB>::kTotal, stream>>>(
+            a.xs, a.sq, a.n, a.outputscale, a.noise, a.vscale, a.x, a.ldx, a.y, a.ldy, a.p, static_cast<const uintx4*>(a.pkv),
+            static_cast<const uintx4*>(a.pka), a.part, a.rangeflag, a.ldpart, a.row0, a.rend);
+        MFX_CHECK_LAUNCH();
+        return MFX_OK;
+      });
+    });
+  });
 }
 
 }  // namespace mfx

@@ -336,14 +336,28 @@ __global__ __launch_bounds__(256) void k_row_amax_part(const float* __restrict__
   }
 }
 
-// scale (rows, 2) = [s, 1/s]; the amax bit patterns live right behind it in the caller's buffer
-static int row_scales(const float* x, int64_t ldx, int64_t n, int64_t rows, float* scale, hipStream_t stream) {
-  unsigned* bits = reinterpret_cast<unsigned*>(scale + 2 * rows);
-  MFX_TRY(zero_async(bits, sizeof(unsigned) * (rows + 1), stream));  // + the f16 range flag behind them
-  int64_t gx = (n + 8191) / 8192;
-  if (gx > 64) gx = 64;
-  k_row_amax_bits<<<dim3((unsigned)gx, (unsigned)rows), 256, 0, stream>>>(x, ldx, n, bits);
-  k_row_scale_from_bits<<<(unsigned)((rows + 255) / 256), 256, 0, stream>>>(bits, rows, scale);
+// slices of a vector for the row-maximum kernels
+static int64_t amax_slices(int64_t n) { return (n + 8191) / 8192 < 64 ? (n + 8191) / 8192 : 64; }
+
+RbfVscaleLayout rbf_vscale_layout(int64_t n, int64_t p) {
+  RbfVscaleLayout v;
+  v.scales = 0;
+  v.amax_bits = 2 * p;
+  v.rangeflag = 3 * p;
+  v.amax_part = 3 * p + 64;
+  v.gx = amax_slices(n);
+  while (v.gx > 1 && v.amax_part + p * v.gx > kRbfVscaleFloats) --v.gx;
+  v.ok = v.amax_part + p * v.gx <= kRbfVscaleFloats;  // p <= kRbfVscaleMaxP -- far beyond any probe count
+  return v;
+}
+
+// in-kernel-split path: scale (rows, 2) = [s, 1/s] from the |max| bit patterns behind it
+static int row_scales(const float* x, int64_t ldx, int64_t n, int64_t rows, float* vscale, const RbfVscaleLayout& v, hipStream_t stream) {
+  unsigned* bits = reinterpret_cast<unsigned*>(vscale + v.amax_bits);
+  static_assert(sizeof(unsigned) == sizeof(float), "the range flag sits one element behind the bit patterns");
+  MFX_TRY(zero_async(bits, sizeof(unsigned) * (v.rangeflag + 1 - v.amax_bits), stream));  // + the f16 range flag behind them
+  k_row_amax_bits<<<dim3((unsigned)amax_slices(n), (unsigned)rows), 256, 0, stream>>>(x, ldx, n, bits);
+  k_row_scale_from_bits<<<(unsigned)((rows + 255) / 256), 256, 0, stream>>>(bits, rows, vscale + v.scales);
   MFX_CHECK_LAUNCH();
   return MFX_OK;
 }
@@ -1002,11 +1016,6 @@ __global__ __launch_bounds__(256) void k_pack_tiles(const float* __restrict__ xs
   }
 }
 
-// column splits of the pipelined matvec (grid.z), for OCCUPANCY: too few 512-row workgroups to fill 256 CUs (small n, or a row
-// shard of a large n).  512-row workgroups of 8 waves, one per CU and round: with s column splits the launch takes
-// ceil(wgs s / 256) rounds of 1/s of the columns each; pick the s (at most 16, at least 8 tiles per split) that minimises
-// rounds / s, plus a small charge per split for the prologue and the partial sums.  (n = 45 730: 90 row blocks -> s = 8, 720
-// workgroups in 3 rounds = 0.375 of an unsplit launch, where "fill one round" (s = 2) gives 0.5.)
 // Which kernel runs the chunks (of 64 vectors, or one of at most 32) of an RBF operator with d <= 8 (BASELINE config 4's matvec,
 // config 2's): the fat-wave kernel (mfx_rbf_fat.hip: one wave per SIMD; at 64 vectors 82 % matrix-pipe share, -16 % cycles
 // against h3).  MFX_RBF_FAT=0 runs the same-program
@@ -1020,12 +1029,21 @@ static bool rbf_fat() {
   return v != 0;
 }
 
+// vectors per chunk of the pre-packed matvec: 64 from 33 vectors on; DPAD = 32 is built with one probe block per chunk only (the
+// tile images and the chain masters of two blocks do not fit the 160 KB of LDS)
+static int64_t chunk_width(int64_t p, int dpad) { return (p <= 32 || dpad > 16) ? 32 : 64; }
+
+// column splits of the pipelined matvec (grid.z), for OCCUPANCY: too few 512-row workgroups to fill 256 CUs (small n, or a row
+// shard of a large n).  512-row workgroups of 8 waves, one per CU and round: with s column splits the launch takes
+// ceil(wgs s / 256) rounds of 1/s of the columns each; pick the s (at most 16, at least 8 tiles per split) that minimises
+// rounds / s, plus a small charge per split for the prologue and the partial sums.  (n = 45 730: 90 row blocks -> s = 8, 720
+// workgroups in 3 rounds = 0.375 of an unsplit launch, where "fill one round" (s = 2) gives 0.5.)
 static int rbf_split_count(int64_t nrow, int64_t n, int64_t p, int dpad) {
   static const int forced = [] {
     const char* e = getenv("MFX_RBF_SPLIT");  // A/B: force the split count
     return e ? atoi(e) : 0;
   }();
-  const int64_t pw = (p <= 32 || dpad > 16) ? 32 : 64;  // vectors per chunk (DPAD 32: one probe block per chunk)
+  const int64_t pw = chunk_width(p, dpad);
   const int64_t wgs = ((nrow + 511) / 512) * ((p + pw - 1) / pw);
   const int64_t ntile = (n + 63) / 64;
   int64_t smax = ntile / 8;
@@ -1045,17 +1063,37 @@ static int rbf_split_count(int64_t nrow, int64_t n, int64_t p, int dpad) {
   return best;
 }
 
-static int64_t rbf_pack_bytes_v(int64_t n, int64_t p, int dpad) {
-  const int64_t P = (p <= 32 || dpad > 16) ? 32 : 64, chunks = (p + P - 1) / P, ntile = (n + 63) / 64;
-  return chunks * ntile * 2 * 8 * P * 16;
+RbfPackLayout rbf_pack_layout(int64_t n, int64_t nrow, int64_t p, int dpad) {
+  RbfPackLayout k;
+  k.P = chunk_width(p, dpad);
+  k.chunks = (p + k.P - 1) / k.P;
+  k.ntile = (n + 63) / 64;
+  const int64_t arow = ((3 * (dpad + 2) + 15) / 16) * 16 + 8;  // RbfTileH3::AROW
+  k.off_a = align_up(k.chunks * k.ntile * 2 * 8 * k.P * 16, 256);
+  k.off_part = k.off_a + align_up(k.ntile * 64 * arow * 2, 256);
+  k.nsplit = rbf_split_count(nrow, n, p, dpad);
+  k.ldpart = align_up(nrow, 4);  // the partials have their own stride (any n, any ldy)
+  k.bytes = k.off_part + align_up((int64_t)k.nsplit * p * k.ldpart * 4, 256);
+  return k;
 }
 int64_t rbf_pack_ws_bytes(const mfx_operator* op, int64_t p) {
   if (op->dtype != MFX_F32 || op->d > 32 || p < 1) return 0;
-  const int64_t ntile = (op->n + 63) / 64;
-  const int dpad = op->d <= 4 ? 4 : op->d <= 8 ? 8 : op->d <= 12 ? 12 : op->d <= 16 ? 16 : 32;
-  const int64_t arow = ((3 * (dpad + 2) + 15) / 16) * 16 + 8;
-  return align_up(rbf_pack_bytes_v(op->n, p, dpad), 256) + align_up(ntile * 64 * arow * 2, 256) +
-         align_up((int64_t)rbf_split_count(op_nrows(op), op->n, p, dpad) * p * align_up(op_nrows(op), 4) * 4, 256);
+  return rbf_pack_layout(op->n, op_nrows(op), p, rbf_dpad(op->d)).bytes;
+}
+
+// the one launch site of k_rbf_mfma_apply_h3; PK: the pre-packed variant (f16 distances: DH = PK in every instance that is built)
+template <int DPAD, int NB, int KIND, bool PK>
+static int launch_h3(bool vec4, dim3 grid, hipStream_t stream, const RbfMatvecArgs& a) {
+  return with_bool(vec4, [&](auto v4) -> int {
+    // LDS: the two tile buffers + (pre-packed variant) the chain masters of 8 waves x (2 NB - 1) blocks x 16 registers x 64 lanes
+    constexpr size_t kSm = 2 * sizeof(RbfTileH3<DPAD, NB, 64, !PK>) + (PK ? (size_t)8 * (2 * NB - 1) * 16 * 64 * 4 : 0);
+    const auto kernel = k_rbf_mfma_apply_h3<DPAD, NB, decltype(v4)::value, KIND, PK, PK>;
+    MFX_TRY(allow_big_lds(kernel, kSm));
+    kernel<<<grid, 64 * H3Waves<PK>::value, kSm, stream>>>(a.xs, a.sq, a.n, a.outputscale, a.noise, a.vscale, a.x, a.ldx, a.y, a.ldy, a.p,
+                                                           static_cast<const uintx4*>(a.pkv), static_cast<const uintx4*>(a.pka), a.part,
+                                                           a.rangeflag, a.ldpart, a.row0, a.rend);
+    return MFX_OK;
+  });
 }
 
 template <int DPAD, int NB, int KIND>
@@ -1067,112 +1105,66 @@ static int launch_apply_h3k(const mfx_operator* op, const float* xs, const float
   // the pre-packed tile images need the caller's pack workspace (mfx_workspace_bytes sizes it); DPAD = 32 (16 < d <= 32, round 5): only the
   // in-kernel-split form with fp32-MFMA distances is built -- the packed images and the fat-wave kernel keep 3 KD / 16 f16 distance operands
   // per block resident or in the 160 KB of LDS next to the chain masters, which stops at DPAD = 16
-  const bool pack = pk != nullptr && (DPAD <= 16 || NB == 1);
-  // vscale region (65536 x 3 floats): [0, 2p) scales, [2p, 3p) |max| bit patterns (in-kernel-split path only), [3p] f16 range flag,
-  // [3p + 64, ...) slice maxima of the pre-packed path
-  int* rangeflag = reinterpret_cast<int*>(vscale + 3 * p);
-  float* amax_part = vscale + 3 * p + 64;
-  int64_t gx = (n + 8191) / 8192;
-  if (gx > 64) gx = 64;
-  while (gx > 1 && 3 * p + 64 + p * gx > (int64_t)65536 * 3) --gx;
-  // (one slice per vector must fit behind the scales and the flag: p <= 49136 -- far beyond any probe count; unguarded before round 5)
-  MFX_REQUIRE(3 * p + 64 + p * gx <= (int64_t)65536 * 3, MFX_ERR_UNSUPPORTED, "matrix-core Gram matvec: %lld vectors exceed the scale / slice-maximum region of the workspace (at most 49136)", (long long)p);
+  constexpr bool kPackBuilt = DPAD <= 16 || NB == 1;
+  const bool pack = pk != nullptr && kPackBuilt;
+  const RbfVscaleLayout vl = rbf_vscale_layout(n, p);
+  MFX_REQUIRE(vl.ok, MFX_ERR_UNSUPPORTED, "matrix-core Gram matvec: %lld vectors exceed the scale / slice-maximum region of the workspace (at most %lld)", (long long)p, (long long)kRbfVscaleMaxP);
+  int* rangeflag = reinterpret_cast<int*>(vscale + vl.rangeflag);
+  float* amax_part = vscale + vl.amax_part;
   if (pack) {
-    k_row_amax_part<<<dim3((unsigned)gx, (unsigned)p), 256, 0, stream>>>(x, ldx, n, amax_part, rangeflag);
+    k_row_amax_part<<<dim3((unsigned)vl.gx, (unsigned)p), 256, 0, stream>>>(x, ldx, n, amax_part, rangeflag);
     MFX_CHECK_LAUNCH();
   } else {
-    MFX_TRY(row_scales(x, ldx, n, p, vscale, stream));
+    MFX_TRY(row_scales(x, ldx, n, p, vscale, vl, stream));
   }
-  const unsigned chunks = (unsigned)((p + NB * 32 - 1) / (NB * 32));
-  const dim3 grid((unsigned)((nrow + 255) / 256), chunks);  // 4-wave workgroups (256 rows); the pre-packed variant uses grid_pk
-  const bool vec4 = (n % 4 == 0) && (nrow % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(y) % 16 == 0);
-  uintx4* pkv = nullptr;
-  uintx4* pka = nullptr;
-  const int64_t ntile = (n + 63) / 64;
-  const int64_t off_a = align_up((int64_t)chunks * ntile * 2 * 8 * NB * 32 * 16, 256);
-  const int64_t arow = ((3 * (DPAD + 2) + 15) / 16) * 16 + 8;
-  float* part = pk ? reinterpret_cast<float*>(static_cast<char*>(pk) + off_a + align_up(ntile * 64 * arow * 2, 256)) : nullptr;
-  const int64_t ldpart = align_up(nrow, 4);  // the partials have their own stride (any n, any ldy)
-  const int nsplit = part ? rbf_split_count(nrow, n, p, DPAD) : 1;
-  const dim3 grid3(grid.x, grid.y, (unsigned)nsplit);
-  const dim3 grid_pk((unsigned)((nrow + 511) / 512), grid.y, (unsigned)nsplit);
-  if constexpr (DPAD <= 16 || NB == 1) {
+  const unsigned chunks = (unsigned)((p + NB * 32 - 1) / (NB * 32));  // (pack: NB * 32 = chunk_width, so this is pl.chunks)
+  const bool vec4 = vec4_ok(x, ldx, y, ldy, n, nrow);
+  const RbfPackLayout pl = rbf_pack_layout(n, nrow, p, DPAD);
+  char* pkb = static_cast<char*>(pk);
+  const int nsplit = pk ? pl.nsplit : 1;
+  RbfMatvecArgs a{xs, sq, n, (const float*)op->outputscale, (const float*)op->noise, vscale, x, ldx, y, ldy, p, nullptr, nullptr,
+                  pk ? reinterpret_cast<float*>(pkb + pl.off_part) : nullptr, nullptr, pl.ldpart, row0, rend};
+  // 4-wave workgroups (256 rows); the pre-packed variants: 8 waves (512 rows)
+  const dim3 grid((unsigned)((nrow + 255) / 256), chunks, (unsigned)nsplit);
+  const dim3 grid_pk((unsigned)((nrow + 511) / 512), chunks, (unsigned)nsplit);
+  if constexpr (kPackBuilt) {
     if (pack) {
-      pkv = static_cast<uintx4*>(pk);
-      pka = reinterpret_cast<uintx4*>(static_cast<char*>(pk) + off_a);
-      k_pack_tiles<DPAD, NB, KIND><<<dim3((unsigned)ntile, chunks + 1), 256, 0, stream>>>(xs, sq, n, vscale, amax_part, (int)gx, x, ldx, p, pkv, pka, rangeflag);
+      a.pkv = pkb;
+      a.pka = pkb + pl.off_a;
+      a.rangeflag = rangeflag;
+      k_pack_tiles<DPAD, NB, KIND><<<dim3((unsigned)pl.ntile, chunks + 1), 256, 0, stream>>>(
+          xs, sq, n, vscale, amax_part, (int)vl.gx, x, ldx, p, static_cast<uintx4*>(pk), reinterpret_cast<uintx4*>(pkb + pl.off_a), rangeflag);
       MFX_CHECK_LAUNCH();
+      bool fat = false;  // fat waves (mfx_rbf_fat.hip): four waves of 128 rows, one per SIMD
+      if constexpr (KIND == MFX_KERNEL_RBF && DPAD <= 16) fat = rbf_fat();
+      if (fat) MFX_TRY(rbf_fat_launch(DPAD, NB, vec4, grid_pk, stream, a));
+      else MFX_TRY((launch_h3<DPAD, NB, KIND, true>(vec4, grid_pk, stream, a)));
+      // f16 range guard: the launch below returns at once unless k_pack_tiles raised the flag, in which case the one above did
     }
   }
-  // LDS: the two tile buffers + (pre-packed variant) the chain masters of 8 waves x (2 NB - 1) blocks x 16 registers x 64 lanes
-#define MFX_H3_LAUNCH(V4, DHV, PKV, FLAG)                                                                            \
-  {                                                                                                                  \
-    constexpr size_t kSm = 2 * sizeof(RbfTileH3<DPAD, NB, 64, !(PKV)>) + ((PKV) ? (size_t)8 * (2 * NB - 1) * 16 * 64 * 4 : 0); \
-    if (kSm > 64 * 1024)                                                                                             \
-      MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_apply_h3<DPAD, NB, V4, KIND, DHV, PKV>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSm));                       \
-    k_rbf_mfma_apply_h3<DPAD, NB, V4, KIND, DHV, PKV><<<(PKV) ? grid_pk : grid3, 64 * H3Waves<PKV>::value, kSm, stream>>>( \
-        xs, sq, n, (const float*)op->outputscale, (const float*)op->noise, vscale, x, ldx, y, ldy, p, pkv, pka, part, FLAG, ldpart, row0, rend); \
-  }
-  if constexpr (DPAD > 16 && NB > 1) {
-    if (vec4) MFX_H3_LAUNCH(true, false, false, nullptr) else MFX_H3_LAUNCH(false, false, false, nullptr)
-  } else if (pack) {
-    bool done = false;
-    if constexpr (KIND == MFX_KERNEL_RBF && DPAD <= 16) {
-      if (rbf_fat()) {  // fat waves (mfx_rbf_fat.hip): four waves of 128 rows, one per SIMD
-        MFX_TRY(rbf_fat_launch(DPAD, NB, vec4, grid_pk, stream, xs, sq, n, (const float*)op->outputscale, (const float*)op->noise, vscale,
-                               x, ldx, y, ldy, p, pkv, pka, part, rangeflag, ldpart, row0, rend));
-        done = true;
-      }
-    }
-    if (!done) {
-      if (vec4) MFX_H3_LAUNCH(true, true, true, rangeflag) else MFX_H3_LAUNCH(false, true, true, rangeflag)
-    }
-    // f16 range guard: this launch returns at once unless k_pack_tiles raised the flag, in which case the launches above did
-    if (vec4) MFX_H3_LAUNCH(true, false, false, rangeflag) else MFX_H3_LAUNCH(false, false, false, rangeflag)
-  } else {  // no pack workspace: fp32-MFMA distances, in-kernel split of the probe tiles
-    if (vec4) MFX_H3_LAUNCH(true, false, false, nullptr) else MFX_H3_LAUNCH(false, false, false, nullptr)
-  }
-#undef MFX_H3_LAUNCH
+  // fp32-MFMA distances, in-kernel split of the probe tiles: all the work without the pack workspace
+  MFX_TRY((launch_h3<DPAD, NB, KIND, false>(vec4, grid, stream, a)));
   MFX_CHECK_LAUNCH();
   if (nsplit > 1) {
-    k_split_reduce<<<dim3((unsigned)((nrow + 255) / 256), (unsigned)p), 256, 0, stream>>>(part, ldpart, nsplit, p, nrow, ldy,
+    k_split_reduce<<<dim3((unsigned)((nrow + 255) / 256), (unsigned)p), 256, 0, stream>>>(a.part, a.ldpart, nsplit, p, nrow, ldy,
                                                                                         (const float*)op->noise, x, ldx, y, row0);
     MFX_CHECK_LAUNCH();
   }
   return MFX_OK;
 }
 
-template <int DPAD, int NB>
-static int launch_apply_h3(const mfx_operator* op, const float* xs, const float* sq, const float* x, int64_t ldx,
-                           float* y, int64_t ldy, int64_t p, float* vscale, void* pk, hipStream_t stream) {
-  switch (op->kernel_fn) {
-    case MFX_KERNEL_RBF: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_RBF>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
-    case MFX_KERNEL_MATERN12: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_MATERN12>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
-    case MFX_KERNEL_MATERN32: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_MATERN32>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
-    case MFX_KERNEL_MATERN52: return launch_apply_h3k<DPAD, NB, MFX_KERNEL_MATERN52>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
-    default: set_error("unknown kernel_fn %d", op->kernel_fn); return MFX_ERR_INVALID;
-  }
-}
-
 int rbf_mfma_apply_h3(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* x, int64_t ldx,
                       float* y, int64_t ldy, int64_t p, float* vscale, void* pk, hipStream_t stream) {
-#define MFX_H3_CASE(D)                                                                             \
-  case D:                                                                                          \
-    return p <= 32 ? launch_apply_h3<D, 1>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream)      \
-                   : launch_apply_h3<D, 2>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream)
-  switch (dpad) {
-    MFX_H3_CASE(4);
-    MFX_H3_CASE(8);
-    MFX_H3_CASE(12);
-    MFX_H3_CASE(16);
-    case 32:  // the pre-packed form exists with one probe block per chunk only (LDS); without the pack workspace: in-kernel split
-      return (p <= 32 || pk) ? launch_apply_h3<32, 1>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream)
-                             : launch_apply_h3<32, 2>(op, xs, sq, x, ldx, y, ldy, p, vscale, pk, stream);
-    default: set_error("split matrix-core Gram matvec supports d <= 32"); return MFX_ERR_UNSUPPORTED;
-  }
-#undef MFX_H3_CASE
+  // chunks of 64 vectors from 33 on; DPAD = 32 with the pack workspace: chunk_width's one block; without it: in-kernel split, two
+  const bool two_blocks = pk ? chunk_width(p, dpad) == 64 : p > 32;
+  return with_mfma_dpad<32>(dpad, "split matrix-core Gram matvec supports d <= 32", [&](auto dc) -> int {
+    return with_bool(two_blocks, [&](auto two) -> int {
+      return with_kind(op->kernel_fn, [&](auto kind) -> int {
+        return launch_apply_h3k<decltype(dc)::value, decltype(two)::value ? 2 : 1, decltype(kind)::value>(op, xs, sq, x, ldx, y, ldy, p,
+                                                                                                         vscale, pk, stream);
+      });
+    });
+  });
 }
 
 // ================================================================================================
@@ -1779,8 +1771,8 @@ __device__ __forceinline__ void rbf_mfma_grad_h_body(const float* __restrict__ x
   }
 }
 
-// the instance of RBF / Matern-1/2 / Matern-3/2 (runtime `kind`) and, as an overload, the Matern-5/2 one (KIND at compile time)
-template <int DPAD, int NBW, bool REGEPI>
+// M52 = false: RBF / Matern-1/2 / Matern-3/2 (runtime `kind`); true: the Matern-5/2 instance
+template <int DPAD, int NBW, bool REGEPI, bool M52>
 __global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restrict__ xs, const float* __restrict__ sq,
                                                             int64_t n, int64_t npad_l, int64_t npad_r, int ard, int kind,
                                                             const _Float16* __restrict__ Lh, const _Float16* __restrict__ Ll,
@@ -1788,63 +1780,47 @@ __global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restr
                                                             int64_t nkb /* batch_pad / 8 */, int tiles_per_block,
                                                             uint32_t salt_l, uint32_t salt_r, double* __restrict__ partial,
                                                             int64_t row0, int64_t nrow, const int* __restrict__ one_product) {
-  rbf_mfma_grad_h_body<DPAD, NBW, REGEPI, false>(xs, sq, n, npad_l, npad_r, ard, kind, Lh, Ll, Rh, Rl, nkb, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
-}
-template <int DPAD, int NBW, bool REGEPI, int KIND>
-__global__ __launch_bounds__(512, 1) void k_rbf_mfma_grad_h(const float* __restrict__ xs, const float* __restrict__ sq,
-                                                            int64_t n, int64_t npad_l, int64_t npad_r, int ard, int kind,
-                                                            const _Float16* __restrict__ Lh, const _Float16* __restrict__ Ll,
-                                                            const _Float16* __restrict__ Rh, const _Float16* __restrict__ Rl,
-                                                            int64_t nkb /* batch_pad / 8 */, int tiles_per_block,
-                                                            uint32_t salt_l, uint32_t salt_r, double* __restrict__ partial,
-                                                            int64_t row0, int64_t nrow, const int* __restrict__ one_product) {
-  static_assert(KIND == MFX_KERNEL_MATERN52 && !REGEPI, "the register epilogue is RBF only");
-  rbf_mfma_grad_h_body<DPAD, NBW, REGEPI, true>(xs, sq, n, npad_l, npad_r, ard, kind, Lh, Ll, Rh, Rl, nkb, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
+  static_assert(!(M52 && REGEPI), "the register epilogue is RBF only");
+  rbf_mfma_grad_h_body<DPAD, NBW, REGEPI, M52>(xs, sq, n, npad_l, npad_r, ard, kind, Lh, Ll, Rh, Rl, nkb, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
 }
 
-int64_t rbf_grad_h_ws_bytes(int64_t n, int64_t batch) {
-  const int64_t npad = (n + kHM - 1) / kHM * kHM, bpad = (batch + 31) / 32 * 32;
-  return 4 * bpad * npad * (int64_t)sizeof(_Float16) + 3 * bpad * (int64_t)sizeof(float) + 1536;
+RbfGradHLayout rbf_grad_h_layout(int64_t n, int64_t nrow, int64_t batch) {
+  RbfGradHLayout h;
+  h.bpad = (batch + 31) / 32 * 32;
+  h.npad = (n + kHM - 1) / kHM * kHM;
+  h.npad_l = (nrow + kHM - 1) / kHM * kHM;
+  const int64_t f16 = sizeof(_Float16);
+  h.amaxL = 0;
+  h.amaxR = h.bpad * 4;
+  h.scl = 2 * h.bpad * 4;  // [sL, 1/sL, sR, 1/sR]
+  h.tail = h.scl + 64;     // n3: the first one-product stage (k_order_rows)
+  h.perm = h.tail + 64;    // packed row -> source row, bpad ints
+  h.Lh = align_up(h.perm + h.bpad * 4, 256);
+  h.Ll = h.Lh + h.bpad * h.npad_l * f16;
+  h.Rh = h.Ll + h.bpad * h.npad_l * f16;
+  h.Rl = h.Rh + h.bpad * h.npad * f16;
+  // The total is sized for a whole operator (npad_l = npad).  The header needs align_up(12 bpad + 128, 256) <= 12 bpad + 383 bytes;
+  // the 1536 the size has always carried covers that with 1153 to spare.
+  h.bytes = 4 * h.bpad * h.npad * f16 + 3 * h.bpad * 4 + 1536;
+  return h;
 }
 
-template <int DPAD, int NBW>
-static int launch_grad_h_t(const mfx_operator* op, const float* xs, const float* sq, int64_t n, int64_t npad_l, int64_t npad,
-                           const _Float16* Lh, const _Float16* Ll, const _Float16* Rh, const _Float16* Rl, int64_t bpad,
-                           uint32_t salt_l, uint32_t salt_r, double* partial, int64_t* nblocks_out, const int* one_product,
-                           hipStream_t stream) {
+// the one launch site of k_rbf_mfma_grad_h
+template <int DPAD, int NBW, bool REGEPI, bool M52>
+static int launch_grad_h_k(const mfx_operator* op, const float* xs, const float* sq, const RbfGradHLayout& h, char* base, double* partial,
+                           int64_t* nblocks_out, hipStream_t stream) {
   constexpr int TN = GradSmemH<DPAD, NBW>::TN;
-  const int64_t row0 = op_row0(op), nrow = op_nrows(op);
+  const int64_t n = op->n, row0 = op_row0(op), nrow = op_nrows(op);
   const int64_t nti = (nrow + kHM - 1) / kHM, ntj = (n + TN - 1) / TN;
   const int tiles_per_block = (int)((ntj + kGSplit * kGSub - 1) / (kGSplit * kGSub));
   const dim3 grid(kGSplit, (unsigned)(nti * kGSub));
-  // RBF kernel, one lengthscale, d <= 8: the register epilogue; Matern / ARD / d > 8: the LDS epilogue
-  bool launched = false;
-  if constexpr (DPAD <= 8) {
-    if (!op->ard && op->kernel_fn == MFX_KERNEL_RBF) {
-      const size_t sh = sizeof(GradSmemH<DPAD, NBW, true>);
-      MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad_h<DPAD, NBW, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-      k_rbf_mfma_grad_h<DPAD, NBW, true><<<grid, 512, sh, stream>>>(xs, sq, n, npad_l, npad, op->ard, op->kernel_fn, Lh, Ll, Rh, Rl,
-                                                                    bpad / 8, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
-      launched = true;
-    }
-  }
-  if (!launched && op->kernel_fn == MFX_KERNEL_MATERN52) {
-    const size_t sh = sizeof(GradSmemH<DPAD, NBW, false>);
-    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad_h<DPAD, NBW, false, MFX_KERNEL_MATERN52>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    k_rbf_mfma_grad_h<DPAD, NBW, false, MFX_KERNEL_MATERN52><<<grid, 512, sh, stream>>>(
-        xs, sq, n, npad_l, npad, op->ard, op->kernel_fn, Lh, Ll, Rh, Rl, bpad / 8, tiles_per_block, salt_l, salt_r, partial, row0, nrow,
-        one_product);
-    launched = true;
-  }
-  if (!launched) {
-    const size_t sh = sizeof(GradSmemH<DPAD, NBW, false>);
-    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad_h<DPAD, NBW, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    k_rbf_mfma_grad_h<DPAD, NBW, false><<<grid, 512, sh, stream>>>(xs, sq, n, npad_l, npad, op->ard, op->kernel_fn, Lh, Ll, Rh, Rl,
-                                                                   bpad / 8, tiles_per_block, salt_l, salt_r, partial, row0, nrow, one_product);
-  }
+  auto pack = [&](int64_t off) { return reinterpret_cast<const _Float16*>(base + off); };
+  const size_t sh = sizeof(GradSmemH<DPAD, NBW, REGEPI>);
+  const auto kernel = k_rbf_mfma_grad_h<DPAD, NBW, REGEPI, M52>;
+  MFX_TRY(allow_big_lds(kernel, sh));
+  kernel<<<grid, 512, sh, stream>>>(xs, sq, n, h.npad_l, h.npad, op->ard, op->kernel_fn, pack(h.Lh), pack(h.Ll), pack(h.Rh), pack(h.Rl),
+                                    h.bpad / 8, tiles_per_block, kSaltL, kSaltR, partial, row0, nrow,
+                                    reinterpret_cast<const int*>(base + h.tail));
   MFX_CHECK_LAUNCH();
   *nblocks_out = nti * kGSub * kGSplit;
   return MFX_OK;
@@ -1853,20 +1829,16 @@ static int launch_grad_h_t(const mfx_operator* op, const float* xs, const float*
 template <int DPAD>
 static int launch_grad_h(const mfx_operator* op, const float* xs, const float* sq, const float* L, int64_t ldl,
                          const float* R, int64_t ldr, int64_t batch, int64_t inner, double* partial, int64_t* nblocks_out,
-                         void* hws, hipStream_t stream) {
-  const int64_t n = op->n, nrow = op_nrows(op);
-  const int64_t npad = (n + kHM - 1) / kHM * kHM, npad_l = (nrow + kHM - 1) / kHM * kHM, bpad = (batch + 31) / 32 * 32;
+                         void* hws, const RbfGradHLayout& h, hipStream_t stream) {
+  const int64_t n = op->n, nrow = op_nrows(op), bpad = h.bpad;
   if (inner < 1 || batch % inner != 0) inner = 1;
   char* base = static_cast<char*>(hws);
-  float* amaxL = reinterpret_cast<float*>(base);
-  float* amaxR = amaxL + bpad;
-  float* scl = amaxR + bpad;  // [sL, 1/sL, sR, 1/sR]
-  int* tail = reinterpret_cast<int*>(base + 2 * bpad * 4 + 64);  // n3: the first one-product stage (k_order_rows)
-  int* perm = tail + 16;                                          // packed row -> source row
-  _Float16* Lh = reinterpret_cast<_Float16*>(base + align_up(2 * bpad * 4 + 128 + bpad * 4, 256));
-  _Float16* Ll = Lh + bpad * npad_l;
-  _Float16* Rh = Ll + bpad * npad_l;
-  _Float16* Rl = Rh + bpad * npad;
+  float* amaxL = reinterpret_cast<float*>(base + h.amaxL);
+  float* amaxR = reinterpret_cast<float*>(base + h.amaxR);
+  float* scl = reinterpret_cast<float*>(base + h.scl);
+  int* tail = reinterpret_cast<int*>(base + h.tail);
+  int* perm = reinterpret_cast<int*>(base + h.perm);
+  auto pack = [&](int64_t off) { return reinterpret_cast<_Float16*>(base + off); };
   k_row_amax<<<(unsigned)batch, 256, 0, stream>>>(L, ldl, nrow, amaxL);
   k_row_amax<<<(unsigned)batch, 256, 0, stream>>>(R, ldr, n, amaxR);
   k_global_scale<<<1, 256, 0, stream>>>(amaxL, batch, scl);
@@ -1874,112 +1846,98 @@ static int launch_grad_h(const mfx_operator* op, const float* xs, const float* s
   if (bpad <= kSortMax) {
     int npow2 = 64;
     while (npow2 < bpad) npow2 <<= 1;
-    if (npow2 * 8 > 48 * 1024)
-      MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_order_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kSortMax * 8));
+    // (the keys of kSortMax rows are the 64 KiB a kernel gets by default: its static LDS then needs the attribute)
+    MFX_TRY(allow_big_lds(k_order_rows, (size_t)npow2 * 8 + 16 * sizeof(double) + sizeof(int)));
     k_order_rows<<<1, 1024, (size_t)npow2 * 8, stream>>>(amaxL, amaxR, batch, inner, bpad, npow2, grad_one_product_log2(), perm, tail);
   } else {
     k_order_default<<<(unsigned)((bpad + 255) / 256), 256, 0, stream>>>(batch, inner, bpad, perm, tail);
   }
-  const dim3 pgrid((unsigned)((npad + 255) / 256), (unsigned)(bpad / 8));
-  const dim3 pgrid_l((unsigned)((npad_l + 255) / 256), (unsigned)(bpad / 8));
-  const uint32_t salt_l = kSaltL, salt_r = kSaltR;
-  k_pack_f16<<<pgrid_l, 256, 0, stream>>>(L, ldl, batch, nrow, npad_l, scl, salt_l, perm, Lh, Ll);
-  k_pack_f16<<<pgrid, 256, 0, stream>>>(R, ldr, batch, n, npad, scl + 2, salt_r, perm, Rh, Rl);
+  const dim3 pgrid((unsigned)((h.npad + 255) / 256), (unsigned)(bpad / 8));
+  const dim3 pgrid_l((unsigned)((h.npad_l + 255) / 256), (unsigned)(bpad / 8));
+  k_pack_f16<<<pgrid_l, 256, 0, stream>>>(L, ldl, batch, nrow, h.npad_l, scl, kSaltL, perm, pack(h.Lh), pack(h.Ll));
+  k_pack_f16<<<pgrid, 256, 0, stream>>>(R, ldr, batch, n, h.npad, scl + 2, kSaltR, perm, pack(h.Rh), pack(h.Rl));
   MFX_CHECK_LAUNCH();
   // 256 x 256 workgroup tile (NBW = 4) for d <= 8; d = 9..16 keeps the 256 x 128 tile (the epilogue registers on top of 128
   // accumulators spill there)
-  if constexpr (DPAD <= 8)
-    return launch_grad_h_t<DPAD, 4>(op, xs, sq, n, npad_l, npad, Lh, Ll, Rh, Rl, bpad, salt_l, salt_r, partial, nblocks_out, tail, stream);
-  return launch_grad_h_t<DPAD, 2>(op, xs, sq, n, npad_l, npad, Lh, Ll, Rh, Rl, bpad, salt_l, salt_r, partial, nblocks_out, tail, stream);
+  auto gemm = [&](auto nbw) -> int {
+    constexpr int NBW = decltype(nbw)::value;
+    // RBF kernel, one lengthscale, d <= 8: the register epilogue; Matern / ARD / d > 8: the LDS epilogue
+    if constexpr (DPAD <= 8) {
+      if (!op->ard && op->kernel_fn == MFX_KERNEL_RBF)
+        return launch_grad_h_k<DPAD, NBW, true, false>(op, xs, sq, h, base, partial, nblocks_out, stream);
+    }
+    return with_bool(op->kernel_fn == MFX_KERNEL_MATERN52, [&](auto m52) -> int {
+      return launch_grad_h_k<DPAD, NBW, false, decltype(m52)::value>(op, xs, sq, h, base, partial, nblocks_out, stream);
+    });
+  };
+  if constexpr (DPAD <= 8) return gemm(Const<4>{});
+  return gemm(Const<2>{});  // (d <= 8 never gets here, but its 256 x 128 instances have always been part of the code object)
 }
 
 // returns the device pointer holding [sL, 1/sL, sR, 1/sR] through scales_out
 int rbf_mfma_grad_h(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* L, int64_t ldl,
                     const float* R, int64_t ldr, int64_t batch, int64_t inner, double* partial, int64_t* nblocks_out, void* hws,
                     const float** scales_out, hipStream_t stream) {
-  const int64_t bpad = (batch + 31) / 32 * 32;
-  *scales_out = reinterpret_cast<const float*>(hws) + 2 * bpad;
-  switch (dpad) {
-    case 4: return launch_grad_h<4>(op, xs, sq, L, ldl, R, ldr, batch, inner, partial, nblocks_out, hws, stream);
-    case 8: return launch_grad_h<8>(op, xs, sq, L, ldl, R, ldr, batch, inner, partial, nblocks_out, hws, stream);
-    case 12: return launch_grad_h<12>(op, xs, sq, L, ldl, R, ldr, batch, inner, partial, nblocks_out, hws, stream);
-    case 16: return launch_grad_h<16>(op, xs, sq, L, ldl, R, ldr, batch, inner, partial, nblocks_out, hws, stream);
-    case 32: return launch_grad_h<32>(op, xs, sq, L, ldl, R, ldr, batch, inner, partial, nblocks_out, hws, stream);
-    default: set_error("split parameter sweep supports d <= 32"); return MFX_ERR_UNSUPPORTED;
+  const RbfGradHLayout h = rbf_grad_h_layout(op->n, op_nrows(op), batch);
+  *scales_out = reinterpret_cast<const float*>(static_cast<const char*>(hws) + h.scl);
+  return with_mfma_dpad<32>(dpad, "split parameter sweep supports d <= 32", [&](auto dc) -> int {
+    return launch_grad_h<decltype(dc)::value>(op, xs, sq, L, ldl, R, ldr, batch, inner, partial, nblocks_out, hws, h, stream);
+  });
+}
+
+// Which matvec runs.  rbf_mode 0: exact fp32 MFMA, 1: 3 x f16 matvec (fat-wave / pipelined kernels), 2: also the gradient GEMM split.
+//   d <= 16: from 4 probes on, padding the probe dimension to 32 already beats the VALU kernel (C2-like: 12 ms -> ~1 ms).  1-3 vectors
+//     (the CG solves of the log-marginal likelihood) in the split modes at n >= 2048: the VALU kernel costs 2-2.7x a matrix-core sweep
+//     over one 32-probe block (measured, n = 131072: 12.9 vs 5.9 ms), whose probe guards handle any p >= 1.
+//   16 < d <= 128 (round 5): the split kernels keep their distance operands resident and stop at d = 16, the exact-fp32 kernels of this
+//     file are generic in the padded dimension (the distance product is KD / 2 = 17 or 33 fp32 MFMAs per block) -- every arithmetic mode
+//     runs them there.  About half of the datasets the reference's UCI loaders fetch have 17 .. 27 input columns
+//     (util/uci_util.py:68-316); the VALU kernel they fell to is 18 x slower per matvec than d = 16 on the matrix cores (profiles/r05k_*).
+//   16 < d <= 32 in the split modes: the h3 kernel's in-kernel-split form -- fp32-MFMA distances (17 per block), the CONTRACTION on the
+//     f16 pipe.
+//   Everything else (fp64, d > 128, 1-3 vectors below n = 2048 or in the exact mode at d <= 16): the VALU kernel.
+RbfApplyPath rbf_apply_path(const mfx_operator* op, int64_t p) {
+  if (op->dtype != MFX_F32 || op->d > 128) return RbfApplyPath::valu;
+  const bool split = op->rbf_mode >= MFX_RBF_F16X3_MATVEC;
+  const bool few_ok = p >= 4 || op->n >= 2048;
+  if (op->d <= 16) {
+    if (p >= 4) return split ? RbfApplyPath::h3 : RbfApplyPath::exact;
+    return split && few_ok ? RbfApplyPath::h3 : RbfApplyPath::valu;
   }
+  if (!few_ok) return RbfApplyPath::valu;
+  return split && op->d <= 32 ? RbfApplyPath::h3 : RbfApplyPath::exact;
 }
 
-// 0: exact fp32 MFMA, 1: 3 x f16 matvec (fat-wave / pipelined kernels), 2: also the gradient GEMM split
-int rbf_mode(const mfx_operator* op) { return op->rbf_mode; }
-
-bool rbf_mfma_supported(const mfx_operator* op, int64_t p) {
-  // from 4 probes on, padding the probe dimension to 32 already beats the VALU kernel (C2-like: 12 ms -> ~1 ms)
-  return op->dtype == MFX_F32 && p >= 4 && op->d <= 16;
-}
-
-// 16 < d <= 64 (round 5): the split kernels keep their distance operands resident and stop at d = 16, the exact-fp32 kernels of this
-// file are generic in the padded dimension (the distance product is KD / 2 = 17 or 33 fp32 MFMAs per block) -- every arithmetic mode
-// runs them there.  About half of the datasets the reference's UCI loaders fetch have 17 .. 27 input columns (util/uci_util.py:68-316);
-// the VALU kernel they fell to is 18 x slower per matvec than d = 16 on the matrix cores (profiles/r05k_*).
-// 16 < d <= 32 in the split modes: the h3 kernel's in-kernel-split form -- fp32-MFMA distances (17 per block), the CONTRACTION on the f16 pipe
-bool rbf_mfma_h3_wide_supported(const mfx_operator* op, int64_t p) {
-  return op->dtype == MFX_F32 && op->d > 16 && op->d <= 32 && (p >= 4 || op->n >= 2048);
-}
-bool rbf_mfma_exact_wide_supported(const mfx_operator* op, int64_t p) {
-  return op->dtype == MFX_F32 && op->d > 16 && op->d <= 128 && (p >= 4 || op->n >= 2048);
-}
-
-template <int DPAD, int NB, int MI, int TJ>
-static int launch_apply_mi(const mfx_operator* op, const float* xs, const float* sq, const float* x, int64_t ldx,
-                           float* y, int64_t ldy, int64_t p, hipStream_t stream) {
+// the one launch site of k_rbf_mfma_apply; MI: 32-row blocks per wave
+template <int DPAD, int NB, int MI>
+static int launch_apply(const mfx_operator* op, const float* xs, const float* sq, const float* x, int64_t ldx,
+                        float* y, int64_t ldy, int64_t p, hipStream_t stream) {
   const int64_t n = op->n;
   const int64_t row0 = op_row0(op), nrow = op_nrows(op), rend = row0 + nrow;
   MFX_REQUIRE(row0 % 64 == 0, MFX_ERR_INVALID, "matrix-core Gram matvec: row0 = %lld must be a multiple of 64", (long long)row0);
   const dim3 grid((unsigned)((nrow + 4 * MI * 32 - 1) / (4 * MI * 32)), (unsigned)((p + NB * 32 - 1) / (NB * 32)));
-  const bool vec4 = (n % 4 == 0) && (nrow % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(y) % 16 == 0);
-  if (vec4) {
-    k_rbf_mfma_apply<DPAD, NB, true, MI, TJ><<<grid, 256, 0, stream>>>(xs, sq, n, (const float*)op->outputscale,
-                                                                   (const float*)op->noise, x, ldx, y, ldy, p, op->kernel_fn, row0, rend);
-  } else {
-    k_rbf_mfma_apply<DPAD, NB, false, MI, TJ><<<grid, 256, 0, stream>>>(xs, sq, n, (const float*)op->outputscale,
-                                                                    (const float*)op->noise, x, ldx, y, ldy, p, op->kernel_fn, row0, rend);
-  }
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
-}
-
-template <int DPAD, int NB>
-static int launch_apply(const mfx_operator* op, const float* xs, const float* sq, const float* x, int64_t ldx,
-                        float* y, int64_t ldy, int64_t p, hipStream_t stream) {
-  // 64 rows per wave (2 workgroups per CU at n = 131072) unless the problem is too small to fill the chip
-  // (DPAD = 64: the resident row operand of the distance product is 33 registers per 32 rows -- one row block per wave)
-  const bool small = (op_nrows(op) + 255) / 256 < 512;
-  if (small || DPAD > 32) return launch_apply_mi<DPAD, NB, 1, 64>(op, xs, sq, x, ldx, y, ldy, p, stream);
-  if constexpr (DPAD <= 32) return launch_apply_mi<DPAD, NB, 2, 64>(op, xs, sq, x, ldx, y, ldy, p, stream);
-  return MFX_ERR_UNSUPPORTED;
-}
-
-template <int DPAD>
-static int launch_apply_d(const mfx_operator* op, const float* xs, const float* sq, const float* x, int64_t ldx,
-                          float* y, int64_t ldy, int64_t p, hipStream_t stream) {
-  if (p <= 32) return launch_apply<DPAD, 1>(op, xs, sq, x, ldx, y, ldy, p, stream);
-  return launch_apply<DPAD, 2>(op, xs, sq, x, ldx, y, ldy, p, stream);  // chunks of 64 probes in grid.y
+  return with_bool(vec4_ok(x, ldx, y, ldy, n, nrow), [&](auto v4) -> int {
+    k_rbf_mfma_apply<DPAD, NB, decltype(v4)::value, MI, 64><<<grid, 256, 0, stream>>>(
+        xs, sq, n, (const float*)op->outputscale, (const float*)op->noise, x, ldx, y, ldy, p, op->kernel_fn, row0, rend);
+    MFX_CHECK_LAUNCH();
+    return MFX_OK;
+  });
 }
 
 int rbf_mfma_apply(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* x, int64_t ldx,
                    float* y, int64_t ldy, int64_t p, hipStream_t stream) {
-  switch (dpad) {
-    case 4: return launch_apply_d<4>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 8: return launch_apply_d<8>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 12: return launch_apply_d<12>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 16: return launch_apply_d<16>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 32: return launch_apply_d<32>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 64: return launch_apply_d<64>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 96: return launch_apply_d<96>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    case 128: return launch_apply_d<128>(op, xs, sq, x, ldx, y, ldy, p, stream);
-    default: set_error("exact-fp32 matrix-core Gram matvec supports d <= 128"); return MFX_ERR_UNSUPPORTED;
-  }
+  // 64 rows per wave (2 workgroups per CU at n = 131072) unless the problem is too small to fill the chip
+  // (DPAD >= 64: the resident row operand of the distance product is 33 registers per 32 rows -- one row block per wave)
+  const bool small = (op_nrows(op) + 255) / 256 < 512;
+  return with_mfma_dpad<128>(dpad, "exact-fp32 matrix-core Gram matvec supports d <= 128", [&](auto dc) -> int {
+    return with_bool(p > 32, [&](auto two) -> int {  // chunks of 64 probes in grid.y
+      constexpr int DPAD = decltype(dc)::value, NB = decltype(two)::value ? 2 : 1;
+      if constexpr (DPAD <= 32) {
+        if (!small) return launch_apply<DPAD, NB, 2>(op, xs, sq, x, ldx, y, ldy, p, stream);
+      }
+      return launch_apply<DPAD, NB, 1>(op, xs, sq, x, ldx, y, ldy, p, stream);
+    });
+  });
 }
 
 // ================================================================================================
@@ -2213,83 +2171,53 @@ __device__ __forceinline__ void rbf_mfma_grad_body(const float* __restrict__ xs,
   }
 }
 
-// as for the split GEMM: one instance for the three runtime families, an overload for Matern-5/2
-template <int DPAD, bool VEC4>
+// as for the split GEMM: M52 = false is the instance of the three runtime families, true the Matern-5/2 one
+template <int DPAD, bool VEC4, bool M52>
 __global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS, one workgroup per CU anyway */ void k_rbf_mfma_grad(const float* __restrict__ xs, const float* __restrict__ sq,
                                                           int64_t n, int ard, int kind, const float* __restrict__ L,
                                                           int64_t ldl, const float* __restrict__ R, int64_t ldr,
                                                           int64_t batch, int tiles_per_block,
                                                           double* __restrict__ partial, int64_t row0, int64_t nrow) {
-  rbf_mfma_grad_body<DPAD, VEC4, false>(xs, sq, n, ard, kind, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
-}
-template <int DPAD, bool VEC4, int KIND>
-__global__ __launch_bounds__(256, DPAD > 16 ? 1 : 2) /* DPAD = 32: 97 KB of LDS, one workgroup per CU anyway */ void k_rbf_mfma_grad(const float* __restrict__ xs, const float* __restrict__ sq,
-                                                          int64_t n, int ard, int kind, const float* __restrict__ L,
-                                                          int64_t ldl, const float* __restrict__ R, int64_t ldr,
-                                                          int64_t batch, int tiles_per_block,
-                                                          double* __restrict__ partial, int64_t row0, int64_t nrow) {
-  static_assert(KIND == MFX_KERNEL_MATERN52, "the other families share the runtime instance");
-  rbf_mfma_grad_body<DPAD, VEC4, true>(xs, sq, n, ard, kind, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
+  rbf_mfma_grad_body<DPAD, VEC4, M52>(xs, sq, n, ard, kind, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
 }
 
-bool rbf_mfma_grad_supported(const mfx_operator* op, int64_t batch) {
-  // from n = 2048 on even ONE (lambda, x) pair (the PCG backward of the log-marginal likelihood) is cheaper here: the cost is
-  // the n^2 epilogue, which the VALU sweep pays at a quarter of the rate (16.8 vs ~4 ms at n = 36 584)
-  return op->dtype == MFX_F32 && (batch >= 16 || op->n >= 2048) && op->d <= 16 && op->n >= 256;
-}
-
-bool rbf_mfma_grad_exact_wide_supported(const mfx_operator* op, int64_t batch) {  // 16 < d <= 64: see rbf_mfma_exact_wide_supported
-  // (beyond: x_i and x_j of a 128 x 128 tile, 2 x 128 x DPAD floats, no longer fit the LDS next to the operand stages)
-  return op->dtype == MFX_F32 && (batch >= 16 || op->n >= 2048) && op->d > 16 && op->d <= 64 && op->n >= 256;
+// Which parameter sweep runs.  The matrix-core GEMMs need n >= 256 and 16 rows -- or n >= 2048: from there on even ONE (lambda, x)
+// pair (the PCG backward of the log-marginal likelihood) is cheaper here: the cost is the n^2 epilogue, which the VALU sweep pays at a
+// quarter of the rate (16.8 vs ~4 ms at n = 36 584).
+//   exact fp32, d <= 64 (beyond: x_i and x_j of a 128 x 128 tile, 2 x 128 x DPAD floats, no longer fit the LDS next to the operand stages);
+//   3 x f16 split, d <= 32 (16 < d <= 32: its 256 x 128 form with 64-column epilogue passes -- 249 registers, 140 KB of LDS), in
+//     rbf_mode MFX_RBF_F16X3 when the split-gradient region was carved and the packs fit the GEMM's 32-bit byte offsets:
+//     2 B x padded batch x padded n < 4 GiB.
+RbfGradPath rbf_grad_path(const mfx_operator* op, int64_t batch, bool have_hws) {
+  if (op->dtype != MFX_F32 || op->d > 64 || op->n < 256 || !(batch >= 16 || op->n >= 2048)) return RbfGradPath::valu;
+  const RbfGradHLayout h = rbf_grad_h_layout(op->n, op_nrows(op), batch);
+  const bool fits32 = h.bpad * h.npad * 2 < ((int64_t)1 << 32);
+  return op->d <= 32 && op->rbf_mode == MFX_RBF_F16X3 && have_hws && fits32 ? RbfGradPath::split : RbfGradPath::exact;
 }
 
 int64_t rbf_mfma_grad_partial_rows(int64_t n) { return ((n + kGM - 1) / kGM) * kGSplit * kGSub; }
 
-template <int DPAD>
-static int launch_grad(const mfx_operator* op, const float* xs, const float* sq, const float* L, int64_t ldl,
-                       const float* R, int64_t ldr, int64_t batch, double* partial, int64_t* nblocks_out,
-                       hipStream_t stream) {
+int rbf_mfma_grad(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* L, int64_t ldl,
+                  const float* R, int64_t ldr, int64_t batch, double* partial, int64_t* nblocks_out,
+                  hipStream_t stream) {
   const int64_t n = op->n, row0 = op_row0(op), nrow = op_nrows(op);
   const int64_t nti = (nrow + kGM - 1) / kGM, ntj = (n + kGN - 1) / kGN;
   const int tiles_per_block = (int)((ntj + kGSplit * kGSub - 1) / (kGSplit * kGSub));
   const dim3 grid(kGSplit, (unsigned)(nti * kGSub));
-  const size_t sh = sizeof(GradSmem<DPAD>);
-  const bool vec4 = (n % 4 == 0) && (nrow % 4 == 0) && (ldl % 4 == 0) && (ldr % 4 == 0) && (reinterpret_cast<uintptr_t>(L) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(R) % 16 == 0);
-  if (op->kernel_fn == MFX_KERNEL_MATERN52) {
-#define MFX_GRAD52(V4)                                                                                                        \
-  MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad<DPAD, V4, MFX_KERNEL_MATERN52>),            \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));                                    \
-  k_rbf_mfma_grad<DPAD, V4, MFX_KERNEL_MATERN52><<<grid, 256, sh, stream>>>(xs, sq, n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, \
-                                                                            tiles_per_block, partial, row0, nrow);
-    if (vec4) { MFX_GRAD52(true) } else { MFX_GRAD52(false) }
-#undef MFX_GRAD52
-  } else if (vec4) {
-    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad<DPAD, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    k_rbf_mfma_grad<DPAD, true><<<grid, 256, sh, stream>>>(xs, sq, n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
-  } else {
-    MFX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rbf_mfma_grad<DPAD, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    k_rbf_mfma_grad<DPAD, false><<<grid, 256, sh, stream>>>(xs, sq, n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
-  }
-  MFX_CHECK_LAUNCH();
   *nblocks_out = nti * kGSub * kGSplit;
-  return MFX_OK;
-}
-
-int rbf_mfma_grad(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* L, int64_t ldl,
-                  const float* R, int64_t ldr, int64_t batch, double* partial, int64_t* nblocks_out,
-                  hipStream_t stream) {
-  switch (dpad) {
-    case 4: return launch_grad<4>(op, xs, sq, L, ldl, R, ldr, batch, partial, nblocks_out, stream);
-    case 8: return launch_grad<8>(op, xs, sq, L, ldl, R, ldr, batch, partial, nblocks_out, stream);
-    case 12: return launch_grad<12>(op, xs, sq, L, ldl, R, ldr, batch, partial, nblocks_out, stream);
-    case 16: return launch_grad<16>(op, xs, sq, L, ldl, R, ldr, batch, partial, nblocks_out, stream);
-    case 32: return launch_grad<32>(op, xs, sq, L, ldl, R, ldr, batch, partial, nblocks_out, stream);
-    case 64: return launch_grad<64>(op, xs, sq, L, ldl, R, ldr, batch, partial, nblocks_out, stream);
-    default: set_error("exact-fp32 matrix-core parameter sweep supports d <= 64"); return MFX_ERR_UNSUPPORTED;
-  }
+  return with_mfma_dpad<64>(dpad, "exact-fp32 matrix-core parameter sweep supports d <= 64", [&](auto dc) -> int {
+    return with_bool(vec4_ok(L, ldl, R, ldr, n, nrow), [&](auto v4) -> int {
+      return with_bool(op->kernel_fn == MFX_KERNEL_MATERN52, [&](auto m52) -> int {
+        constexpr int DPAD = decltype(dc)::value;
+        const size_t sh = sizeof(GradSmem<DPAD>);
+        const auto kernel = k_rbf_mfma_grad<DPAD, decltype(v4)::value, decltype(m52)::value>;
+        MFX_TRY(allow_big_lds(kernel, sh));
+        kernel<<<grid, 256, sh, stream>>>(xs, sq, n, op->ard, op->kernel_fn, L, ldl, R, ldr, batch, tiles_per_block, partial, row0, nrow);
+        MFX_CHECK_LAUNCH();
+        return MFX_OK;
+      });
+    });
+  });
 }
 
 }  // namespace mfx

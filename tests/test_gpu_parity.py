@@ -152,7 +152,11 @@ def test_rbf_op_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kerne
                                    (600, 20, 8), (2304, 32, 3), (900, 27, 40), (520, 50, 8), (2100, 64, 5), (1000, 40, 70), (777, 17, 33),
                                    (2100, 128, 5), (640, 97, 70), (300, 129, 8),
                                    # padded d = 32 with 2 vectors at n < 2048: the VALU matvec and sweep in fp32 as well
-                                   (300, 24, 2)])
+                                   (300, 24, 2),
+                                   # the exact-fp32 matvec's instances the list above leaves out: padded d = 96 with 16-byte vector access
+                                   # (n % 4 == 0) and with two probe blocks per chunk (p > 32), padded 128 and 64 with two blocks at a
+                                   # scalar-access n -- the last one also the exact-fp32 sweep at padded 64 with scalar access below n = 2048
+                                   (300, 70, 8), (300, 90, 40), (301, 90, 40), (301, 100, 40), (301, 40, 40)])
 def test_rbf_wide_inputs_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kernel):
     """d > 32: the reference's kernels take any input dimension (util/gp_util.py:151-184) and its UCI loaders reach d = 90 (song) and
     385 (slice) (util/uci_util.py:85-99,303-310).  The wide kernels of csrc/mfx_ops.hip (distance as a small GEMM over chunks of the d

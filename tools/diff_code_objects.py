@@ -3,9 +3,10 @@
 
   python tools/diff_code_objects.py OLD/libmfx.so NEW/libmfx.so
 
-Instructions are compared as llvm-objdump prints them, without addresses and encodings.  The dense cross sweeps of the old
+Instructions are compared as llvm-objdump prints them, without addresses, encodings and the padding between functions.  The dense cross sweeps of the old
 naming (k_rbf_cross_grad_dense[_wide]<.., TRANS>) are matched with the weight-source instantiations that replaced them
-(k_rbf_cross_grad[_wide]<.., DenseSrc<T, TRANS>> / <.., FactoredSrc<T>>).  For every function that differs, the register, LDS,
+(k_rbf_cross_grad[_wide]<.., DenseSrc<T, TRANS>> / <.., FactoredSrc<T>>), and the two overloads each of k_rbf_mfma_grad[_h] (runtime
+families <..>, Matern-5/2 <.., 3>) with the one template that replaced them (<.., false> / <.., true>).  For every function that differs, the register, LDS,
 scratch and spill figures of both builds are printed.  Exit status 1 if anything differs or is unmatched."""
 import os
 import re
@@ -15,7 +16,7 @@ import sys
 import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin/"
-KEYS = ("vgpr_count", "agpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count")
+KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count")
 
 
 def canonical(name):
@@ -31,6 +32,13 @@ def canonical(name):
         args = rest.split(", ")
         src = f"mfx::DenseSrc<{t}, {args.pop()}>" if dense else f"mfx::FactoredSrc<{t}>"
         name = f"mfx::k_rbf_cross_grad{wide or ''}<{t}, {', '.join(args)}, {src}>"
+    if name.startswith("_ZN3mfx17k_rbf_mfma_grad_hI"):  # (c++filt does not know the _Float16 parameters: stays mangled)
+        name = re.sub(r"^(\w+?ILi\d+ELi\d+ELb[01]E)(EEv)", r"\1Lb0E\2", name).replace("ELb0ELi3EEEv", "ELb0ELb1EEEv")
+    m = re.match(r"mfx::k_rbf_mfma_grad(_h)?<(.*)>$", name)
+    if m and len(m.group(2).split(", ")) == (3 if m.group(1) else 2):  # the runtime-family overload of the old naming
+        name = f"mfx::k_rbf_mfma_grad{m.group(1) or ''}<{m.group(2)}, false>"
+    elif m and m.group(2).endswith(", 3"):  # ... and its Matern-5/2 overload (KIND = MFX_KERNEL_MATERN52)
+        name = f"mfx::k_rbf_mfma_grad{m.group(1) or ''}<{m.group(2)[:-3]}, true>"
     return name
 
 
@@ -57,7 +65,9 @@ def load(so):
             names = subprocess.run(["c++filt"], input="\n".join(syms), check=True, capture_output=True, text=True).stdout.split("\n")
             pretty = dict(zip(syms, names))
             for sym, body in re.findall(r"^[0-9a-f]+ <(\S+)>:\n(.*?)(?=^[0-9a-f]+ <\S+>:$|\Z)", dis, flags=re.M | re.S):
-                text = "\n".join(re.sub(r"\s*//.*$", "", line).strip() for line in body.split("\n") if line.strip())
+                text = "\n".join(re.sub(r"\s*//.*$", "", line).strip() for line in body.split("\n")
+                                 if line.strip() and line.strip() != "...")  # ("...": zero padding behind a function)
+                text = text.replace(sym, "SELF")  # branch targets are printed as <symbol+offset>
                 out[canonical(pretty[sym])] = (text, meta.get(sym, {}))
     return out
 
