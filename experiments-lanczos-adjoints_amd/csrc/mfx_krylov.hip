@@ -4,7 +4,9 @@
 // below uses grid = (slices, p): one workgroup (4 waves) owns a slice of ONE probe's vectors -- 2048 elements,
 // 8 per thread, or 512 / 1024 (one 16-byte load per thread and row) when that leaves most CUs idle (Ctx::fine) --
 // and keeps its elements in registers across the whole multi-row sweep (double-buffered, mfx_vec.h: sweep_rows).
-// Dot products are accumulated in fp64, reduced lane -> wave (DPP, several rows at once: wave_sums) -> workgroup (LDS)
+// Dot products are accumulated in fp64 (DotAcc; the three dots of the Lanczos adjoint, k_lz_adj_dots, are the exception: they
+// accumulate in T, and tests/test_gpu_lanczos_kernels.py holds them to the fp32 oracle's own error all the same),
+// reduced lane -> wave (DPP, several rows at once: wave_sums) -> workgroup (LDS)
 // and written as per-slice partials (p, kmax, nslices); the consumer kernel re-reduces the partials in its
 // prologue (deterministic, no atomics, and no host round trip: the whole k-loop is enqueued on one stream,
 // and replayed from a hipGraph when the call repeats: mfx_core.hip).
