@@ -166,6 +166,14 @@ int op_vjp_params(const mfx_operator* op, const void* L, int64_t ldl, const void
 // MFX_ERR_UNSUPPORTED on row blocks (nrows > 0) and on the row-sharded drivers (sharded = true)
 int check_grads_x(const mfx_operator* op, const mfx_op_grads* grads, bool sharded);
 
+// 3x3 stencil operator (mfx_stencil.hip).  check_stencil: every refusal of the kind, before any launch (MFX_OK for other kinds);
+// stencil_grad adds to the coefficient-field gradient gval (NULL: no launch)
+int check_stencil(const mfx_operator* op);
+int stencil_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t p, int transpose,
+                  hipStream_t stream);
+int stencil_grad(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr, int64_t batch, void* gval,
+                 hipStream_t stream);
+
 int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m);
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);

@@ -990,6 +990,7 @@ static int check_common(const mfx_operator* op, int64_t n, int64_t k, int64_t p)
   MFX_REQUIRE(n >= 1 && p >= 1, MFX_ERR_INVALID, "n=%lld, p=%lld must be positive", (long long)n, (long long)p);
   MFX_REQUIRE(op->n == n, MFX_ERR_INVALID, "operator size %lld != n=%lld", (long long)op->n, (long long)n);
   MFX_CHECK_KERNEL_FN(op);
+  MFX_TRY(check_stencil(op));
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_INVALID, "the Krylov drivers take the whole operator (nrows = 0); row shards go through mfx_*_sharded");
   MFX_REQUIRE(k >= 1 && k <= n, MFX_ERR_INVALID, "Parameter depth %lld is outside the expected range", (long long)k);
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "p=%lld exceeds the grid limit 65535", (long long)p);
@@ -1116,6 +1117,7 @@ static int check_sharded(const mfx_operator* op, const mfx_comm* cm, int64_t n, 
   MFX_TRY(check_common(op, n, k, p));
   MFX_REQUIRE(cm && cm->allreduce_sum && cm->allgather, MFX_ERR_INVALID, "communicator without callbacks");
   MFX_REQUIRE(op->kind != MFX_OP_CALLBACK, MFX_ERR_UNSUPPORTED, "row sharding needs a native operator");
+  MFX_REQUIRE(op->kind != MFX_OP_STENCIL, MFX_ERR_UNSUPPORTED, "row sharding a stencil operator needs a halo exchange");
   MFX_REQUIRE(cm->world >= 1 && cm->rank >= 0 && cm->rank < cm->world, MFX_ERR_INVALID, "bad rank %d of %d", cm->rank, cm->world);
   MFX_REQUIRE(cm->nloc >= 64 && cm->nloc % 64 == 0, MFX_ERR_INVALID, "rows per rank (%lld) must be a positive multiple of 64", (long long)cm->nloc);
   MFX_REQUIRE((int64_t)cm->world * cm->nloc >= n && (int64_t)(cm->world - 1) * cm->nloc < n, MFX_ERR_INVALID,

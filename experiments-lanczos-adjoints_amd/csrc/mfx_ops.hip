@@ -1493,6 +1493,7 @@ static int op_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int
                       void* ws, int64_t ws_bytes, hipStream_t stream) {
   const int64_t n = op->n;
   const int64_t row0 = op_row0(op), nrow = op_nrows(op);
+  MFX_TRY(check_stencil(op));
   MFX_REQUIRE(row0 >= 0 && nrow >= 1 && row0 + nrow <= n, MFX_ERR_INVALID, "row block [%lld, +%lld) outside the operator (n = %lld)",
               (long long)row0, (long long)nrow, (long long)n);
   switch (op->kind) {
@@ -1530,6 +1531,8 @@ static int op_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int
                   "RBF operator with null pointers");
       MFX_CHECK_KERNEL_FN(op);
       return rbf_apply<T>(op, x, ldx, y, ldy, p, ws, ws_bytes, stream);  // symmetric: transpose ignored
+    case MFX_OP_STENCIL:
+      return stencil_apply(op, x, ldx, y, ldy, p, transpose, stream);
     default:
       set_error("unknown operator kind %d", op->kind);
       return MFX_ERR_UNSUPPORTED;
@@ -1568,6 +1571,7 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
                            int64_t inner, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, hipStream_t stream) {
   const int64_t n = op->n;
   const int64_t row0 = op_row0(op), nrow = op_nrows(op);
+  MFX_TRY(check_stencil(op));
   MFX_REQUIRE(row0 >= 0 && nrow >= 1 && row0 + nrow <= n, MFX_ERR_INVALID, "row block [%lld, +%lld) outside the operator (n = %lld)",
               (long long)row0, (long long)nrow, (long long)n);
   MFX_TRY(check_grads_x(op, grads, false));
@@ -1596,6 +1600,8 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
       if (params) MFX_TRY(rbf_grad<T>(op, L, ldl, R, ldr, batch, inner, grads, ws, ws_bytes, stream));
       return rbf_grad_x<T>(op, L, ldl, R, ldr, batch, grads, ws, ws_bytes, stream);
     }
+    case MFX_OP_STENCIL:
+      return stencil_grad(op, L, ldl, R, ldr, batch, grads->val, stream);
     default:
       set_error("unknown operator kind %d", op->kind);
       return MFX_ERR_UNSUPPORTED;

@@ -1,0 +1,239 @@
+// libmfx: the matrix-free 3x3 stencil operator (MFX_OP_STENCIL) -- heat and wave systems of the reference's PDE experiment
+// (util/pde_util.py:18-157: a padded 3x3 convolution scaled by a coefficient field) without an assembled matrix.
+//
+//   (S u)[r, c] = sum_{dr, dc in -1..1} w[dr + 1][dc + 1] u_pad[r + dr, c + dc]      u_pad: zeros (Dirichlet) or the nearest cell (Neumann)
+//   HEAT   y = coef o S u            HEAT2  y = (-coef o S u, du)            WAVE  y = (du, coef o S u)
+//
+// Three kernels, all HBM-bound: apply, transposed apply (a gather over the preimages of a cell under the
+// padding rule), and the coefficient-field gradient.  A thread owns one cell per row step; a 256-thread workgroup owns a tile of
+// kStX = 64 columns x kStY = 16 rows (wave w: rows 4 w .. 4 w + 3, lane = column), so every load and store instruction of a wave
+// covers 64 consecutive cells of one grid row, and the rows above and below come from the cache (the three rows a wave reads are
+// the rows its neighbours in the tile read too).  Weights that are exactly 0 are skipped through a mask that is a kernel argument
+// (wave-uniform): the 5-point Laplacian reads 5 neighbours.  No atomics, no cross-workgroup state, a fixed summation order per
+// cell: bit-identical from run to run.
+#include "mfx_internal.h"
+
+namespace mfx {
+
+constexpr int kStX = 64;       // columns of a workgroup's tile (one wave per row)
+constexpr int kStRows = 4;     // rows per wave
+constexpr int kStY = 4 * kStRows;  // rows of a workgroup's tile
+constexpr int64_t kStMaxGrid = 1 << 20;  // workgroups per launch along x; larger grids walk their tiles in a loop
+
+template <typename T>
+struct StencilArgs {
+  int ny, nx, form, neumann;
+  unsigned mask;  // bit t set: w[t] != 0
+  T w[9];
+  const T* coef;  // (ny, nx) or null = ones
+  int64_t tiles;  // tiles_x * tiles_y
+  int tiles_x;
+};
+
+// u_pad[rr, cc] for a cell or a cell of the padding ring
+template <typename T>
+__device__ __forceinline__ T padded(const T* __restrict__ u, int rr, int cc, int ny, int nx, int neumann) {
+  if (neumann) {
+    rr = rr < 0 ? 0 : (rr >= ny ? ny - 1 : rr);
+    cc = cc < 0 ? 0 : (cc >= nx ? nx - 1 : cc);
+    return u[(int64_t)rr * nx + cc];
+  }
+  return (rr >= 0 && rr < ny && cc >= 0 && cc < nx) ? u[(int64_t)rr * nx + cc] : T(0);
+}
+
+// (S u)[r, c], the terms in the order of the weights
+template <typename T>
+__device__ __forceinline__ T stencil_at(const StencilArgs<T>& a, const T* __restrict__ u, int r, int c) {
+  T s = T(0);
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    if (a.mask >> t & 1u) s += a.w[t] * padded<T>(u, r + t / 3 - 1, c + t % 3 - 1, a.ny, a.nx, a.neumann);
+  }
+  return s;
+}
+
+// z[i] = coef[i] x[i]: the operand of S^T
+template <typename T>
+__device__ __forceinline__ T scaled(const T* __restrict__ coef, const T* __restrict__ x, int64_t i) {
+  return coef ? coef[i] * x[i] : x[i];
+}
+
+// (S^T z)[r, c] = sum_t w[t] sum_{cells i whose neighbour t is (r, c)} z[i].  Dirichlet: i = (r, c) - delta_t when that is a cell.
+// Neumann: over the preimages of r under the clamp -- r itself, -1 when r == 0, ny when r == ny - 1 -- and of c likewise;
+// i = preimage - delta_t when that is a cell (correct down to ny == 1 or nx == 1, where -1, 0 and 1 all clamp to 0).
+template <typename T>
+__device__ __forceinline__ T stencil_t_at(const StencilArgs<T>& a, const T* __restrict__ x, int r, int c) {
+  const int ny = a.ny, nx = a.nx;
+  T s = T(0);
+  const bool inner = r > 0 && r < ny - 1 && c > 0 && c < nx - 1;
+  if (inner || !a.neumann) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      if (!(a.mask >> t & 1u)) continue;
+      const int ir = r - (t / 3 - 1), ic = c - (t % 3 - 1);
+      if (ir >= 0 && ir < ny && ic >= 0 && ic < nx) s += a.w[t] * scaled<T>(a.coef, x, (int64_t)ir * nx + ic);
+    }
+    return s;
+  }
+  const int prow[3] = {r, -1, ny}, pcol[3] = {c, -1, nx};
+  const bool vrow[3] = {true, r == 0, r == ny - 1}, vcol[3] = {true, c == 0, c == nx - 1};
+#pragma unroll 1
+  for (int t = 0; t < 9; ++t) {
+    if (!(a.mask >> t & 1u)) continue;
+    const int dr = t / 3 - 1, dc = t % 3 - 1;
+    T zt = T(0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int ir = prow[i] - dr;
+      if (!vrow[i] || ir < 0 || ir >= ny) continue;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int ic = pcol[j] - dc;
+        if (!vcol[j] || ic < 0 || ic >= nx) continue;
+        zt += scaled<T>(a.coef, x, (int64_t)ir * nx + ic);
+      }
+    }
+    s += a.w[t] * zt;
+  }
+  return s;
+}
+
+// the cells of this thread, tile by tile: fn(r, c, i = r nx + c)
+template <typename T, typename F>
+__device__ __forceinline__ void for_cells(const StencilArgs<T>& a, F fn) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+    const int c = (int)(tile % a.tiles_x) * kStX + lane;
+    const int r0 = (int)(tile / a.tiles_x) * kStY + wave * kStRows;
+    if (c >= a.nx) continue;
+#pragma unroll
+    for (int k = 0; k < kStRows; ++k) {
+      const int r = r0 + k;
+      if (r < a.ny) fn(r, c, (int64_t)r * a.nx + c);
+    }
+  }
+}
+
+// y_b = A x_b (TRANS = false) or A^T x_b (TRANS = true), b = blockIdx.y; the pass-through block is written here too
+template <typename T, bool TRANS>
+__global__ __launch_bounds__(256) void k_stencil_apply(StencilArgs<T> a, const T* __restrict__ x, int64_t ldx, T* __restrict__ y,
+                                                       int64_t ldy) {
+  const int64_t m = (int64_t)a.ny * a.nx;
+  x += (int64_t)blockIdx.y * ldx;
+  y += (int64_t)blockIdx.y * ldy;
+  for_cells<T>(a, [&](int r, int c, int64_t i) {
+    if (!TRANS) {
+      T v = stencil_at<T>(a, x, r, c);
+      if (a.coef) v *= a.coef[i];
+      if (a.form == MFX_STENCIL_HEAT) {
+        y[i] = v;
+      } else if (a.form == MFX_STENCIL_HEAT2) {
+        y[i] = -v;
+        y[m + i] = x[m + i];
+      } else {
+        y[i] = x[m + i];
+        y[m + i] = v;
+      }
+    } else {
+      if (a.form == MFX_STENCIL_HEAT) {
+        y[i] = stencil_t_at<T>(a, x, r, c);
+      } else if (a.form == MFX_STENCIL_HEAT2) {  // A^T (a, b) = (-S^T (coef o a), b)
+        y[i] = -stencil_t_at<T>(a, x, r, c);
+        y[m + i] = x[m + i];
+      } else {  // A^T (a, b) = (S^T (coef o b), a)
+        y[i] = stencil_t_at<T>(a, x + m, r, c);
+        y[m + i] = x[i];
+      }
+    }
+  });
+}
+
+// g[i] += sigma sum_b L_b[blk + i] (S R_b.u)[i]: the batch loop inside, one add per field entry
+template <typename T>
+__global__ __launch_bounds__(256) void k_stencil_grad(StencilArgs<T> a, const T* __restrict__ L, int64_t ldl, const T* __restrict__ R,
+                                                      int64_t ldr, int64_t batch, T sigma, int64_t blk, T* __restrict__ g) {
+  for_cells<T>(a, [&](int r, int c, int64_t i) {
+    T acc = T(0);
+    for (int64_t b = 0; b < batch; ++b) acc += L[b * ldl + blk + i] * stencil_at<T>(a, R + b * ldr, r, c);
+    g[i] += sigma * acc;
+  });
+}
+
+int check_stencil(const mfx_operator* op) {
+  if (!op || op->kind != MFX_OP_STENCIL) return MFX_OK;
+  MFX_REQUIRE(op->st_ny >= 1 && op->st_nx >= 1, MFX_ERR_INVALID, "stencil operator: grid %d x %d must be at least 1 x 1", op->st_ny,
+              op->st_nx);
+  MFX_REQUIRE(op->st_form == MFX_STENCIL_HEAT || op->st_form == MFX_STENCIL_HEAT2 || op->st_form == MFX_STENCIL_WAVE, MFX_ERR_INVALID,
+              "stencil operator: unknown st_form %d", op->st_form);
+  MFX_REQUIRE(op->st_boundary == MFX_BOUNDARY_DIRICHLET || op->st_boundary == MFX_BOUNDARY_NEUMANN, MFX_ERR_INVALID,
+              "stencil operator: unknown st_boundary %d", op->st_boundary);
+  const int64_t m = (int64_t)op->st_ny * op->st_nx;
+  MFX_REQUIRE(m <= 2147483647LL, MFX_ERR_UNSUPPORTED, "stencil operator: %d x %d cells exceed 2^31 - 1", op->st_ny, op->st_nx);
+  const int64_t want = op->st_form == MFX_STENCIL_HEAT ? m : 2 * m;
+  MFX_REQUIRE(op->n == want, MFX_ERR_INVALID, "stencil operator: n = %lld, but form %d on a %d x %d grid has %lld unknowns",
+              (long long)op->n, op->st_form, op->st_ny, op->st_nx, (long long)want);
+  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED,
+              "stencil operator: no row block (nrows > 0): sharding a stencil needs a halo exchange");
+  return MFX_OK;
+}
+
+template <typename T>
+static StencilArgs<T> stencil_args(const mfx_operator* op) {
+  StencilArgs<T> a;
+  a.ny = op->st_ny;
+  a.nx = op->st_nx;
+  a.form = op->st_form;
+  a.neumann = op->st_boundary == MFX_BOUNDARY_NEUMANN;
+  a.mask = 0;
+  for (int t = 0; t < 9; ++t) {
+    a.w[t] = (T)op->st_w[t];
+    if (op->st_w[t] != 0.0) a.mask |= 1u << t;
+  }
+  a.coef = (const T*)op->val;
+  a.tiles_x = (a.nx + kStX - 1) / kStX;
+  a.tiles = (int64_t)a.tiles_x * ((a.ny + kStY - 1) / kStY);
+  return a;
+}
+
+template <typename T>
+static int stencil_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int64_t ldy, int64_t p, int transpose,
+                           hipStream_t stream) {
+  const StencilArgs<T> a = stencil_args<T>(op);
+  const dim3 grid((unsigned)(a.tiles < kStMaxGrid ? a.tiles : kStMaxGrid), (unsigned)p);
+  if (!transpose) {
+    k_stencil_apply<T, false><<<grid, 256, 0, stream>>>(a, x, ldx, y, ldy);
+  } else {
+    k_stencil_apply<T, true><<<grid, 256, 0, stream>>>(a, x, ldx, y, ldy);
+  }
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+int stencil_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t p, int transpose,
+                  hipStream_t stream) {
+  MFX_TRY(check_stencil(op));
+  if (op->dtype == MFX_F32) return stencil_apply_t<float>(op, (const float*)x, ldx, (float*)y, ldy, p, transpose, stream);
+  return stencil_apply_t<double>(op, (const double*)x, ldx, (double*)y, ldy, p, transpose, stream);
+}
+
+template <typename T>
+static int stencil_grad_t(const mfx_operator* op, const T* L, int64_t ldl, const T* R, int64_t ldr, int64_t batch, T* g,
+                          hipStream_t stream) {
+  const StencilArgs<T> a = stencil_args<T>(op);
+  const int64_t m = (int64_t)a.ny * a.nx;
+  const T sigma = op->st_form == MFX_STENCIL_HEAT2 ? T(-1) : T(1);
+  const int64_t blk = op->st_form == MFX_STENCIL_WAVE ? m : 0;
+  k_stencil_grad<T><<<(unsigned)(a.tiles < kStMaxGrid ? a.tiles : kStMaxGrid), 256, 0, stream>>>(a, L, ldl, R, ldr, batch, sigma, blk, g);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+int stencil_grad(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr, int64_t batch, void* gval,
+                 hipStream_t stream) {
+  MFX_TRY(check_stencil(op));
+  if (!gval) return MFX_OK;
+  if (op->dtype == MFX_F32) return stencil_grad_t<float>(op, (const float*)L, ldl, (const float*)R, ldr, batch, (float*)gval, stream);
+  return stencil_grad_t<double>(op, (const double*)L, ldl, (const double*)R, ldr, batch, (double*)gval, stream);
+}
+
+}  // namespace mfx

@@ -17,7 +17,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFX_LIBRARY_PATH") or os.path.join(_HERE, "libmfx.so")  # override: A/B builds
 
 MFX_F32, MFX_F64 = 0, 1
-OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK = 0, 1, 2, 3
+OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL = 0, 1, 2, 3, 4
+STENCIL_HEAT, STENCIL_HEAT2, STENCIL_WAVE = 0, 1, 2
+BOUNDARY_DIRICHLET, BOUNDARY_NEUMANN = 0, 1
 REORTHO_NONE, REORTHO_FULL = 0, 1
 RBF_FP32, RBF_F16X3_MATVEC, RBF_F16X3 = 0, 1, 2
 KERNEL_RBF, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 1, 2, 3
@@ -68,6 +70,11 @@ class Operator(C.Structure):
         ("ctx", C.c_void_p),
         ("row0", C.c_int64),
         ("nrows", C.c_int64),
+        ("st_ny", C.c_int32),
+        ("st_nx", C.c_int32),
+        ("st_form", C.c_int32),
+        ("st_boundary", C.c_int32),
+        ("st_w", C.c_double * 9),
     ]
 
 

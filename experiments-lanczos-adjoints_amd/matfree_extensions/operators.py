@@ -13,6 +13,7 @@ whole Krylov loop, the transposed matvec and the parameter-gradient sweep run as
                                                                   util/gp_util.py:151-201,225-226,525-549
                                     (and X itself when X.requires_grad: the reference's closure conversion
                                     makes the inputs its lazy kernel closes over differentiable too)
+  StencilOp(shape, stencil, ...)    params = (coef,) or ()        util/pde_util.py:74-157 (3x3 heat / wave systems, matrix-free)
   CallbackOp(fn)                    any Python ``fn(v, *params)`` (torch ops); per-step host control
 
 ``op.bind(*params)`` freezes the parameters into a zero-argument-parameter matvec (what the GP code
@@ -97,6 +98,9 @@ class RowShardedOp:
     def __init__(self, op, comm, exchange="auto"):
         if not isinstance(op, NativeOp):
             raise TypeError("row sharding needs a native operator (DenseOp, CsrOp, RbfGramOp)")
+        if isinstance(op, StencilOp):
+            raise NotImplementedError("row sharding a StencilOp needs a halo exchange of the grid rows next to a shard's edge, which is "
+                                      "not implemented; shard the probes, or assemble the system (pde_util.wave_operator) as a CsrOp")
         _refuse_input_grad(op)
         self.op, self.comm = op, comm
         # sparse operators: neighbour exchange of the entries this rank's rows read (the halo of a stencil) instead of
@@ -548,6 +552,65 @@ class CsrOp(NativeOp):
     def new_grads(self, vals):
         g = torch.zeros_like(vals)
         s = _lib.OpGrads()
+        s.val = g.data_ptr()
+        return s, (g,)
+
+
+class StencilOp(NativeOp):
+    """The reference's PDE vector fields (util/pde_util.py:74-157) without a matrix: a padded 3x3 convolution S of the (ny, nx) grid
+    ``u``, scaled by a coefficient field.  On flattened states (row-major grid, blocks stacked):
+
+      form="heat"   v = u        (ny nx,)    ->  coef o S u              pde_heat
+      form="heat2"  v = (u, du)  (2 ny nx,)  ->  (-coef o S u, du)       pde_heat_anisotropic
+      form="wave"   v = (u, du)  (2 ny nx,)  ->  (du, coef o S u)        pde_wave_anisotropic
+
+    ``stencil`` is 3x3 in the reference's orientation, ``convolve2d(stencil, padded, "valid")``; boundary="dirichlet" pads with
+    zeros, "neumann" with the nearest cell.  ``op(v, coef)`` takes the field as (ny, nx) or flat and is differentiable with respect
+    to both; ``op(v)`` is the operator without a field (all ones).  The apply, the transposed apply and the field gradient are
+    HIP kernels (csrc/mfx_stencil.hip); nothing is assembled."""
+
+    kind = _lib.OP_STENCIL
+    _FORMS = {"heat": _lib.STENCIL_HEAT, "heat2": _lib.STENCIL_HEAT2, "wave": _lib.STENCIL_WAVE}
+    _BOUNDARIES = {"dirichlet": _lib.BOUNDARY_DIRICHLET, "neumann": _lib.BOUNDARY_NEUMANN}
+
+    def __init__(self, shape, stencil, *, form="wave", boundary="neumann"):
+        if form not in self._FORMS:
+            raise ValueError(f"form must be one of {sorted(self._FORMS)}")
+        if boundary not in self._BOUNDARIES:
+            raise ValueError(f"boundary must be one of {sorted(self._BOUNDARIES)}")
+        self.ny, self.nx = (int(shape), int(shape)) if isinstance(shape, int) else (int(shape[0]), int(shape[1]))
+        if self.ny < 1 or self.nx < 1:
+            raise ValueError(f"StencilOp: the grid must be at least 1 x 1, got {self.ny} x {self.nx}")
+        w = torch.as_tensor(stencil).detach().to(device="cpu", dtype=torch.float64)
+        if tuple(w.shape) != (3, 3):
+            raise ValueError(f"StencilOp expects a 3 x 3 stencil, got {tuple(w.shape)}")
+        # convolve2d flips the stencil: weights[(dr + 1) * 3 + (dc + 1)] multiplies u_pad[r + dr, c + dc]
+        self.weights = [float(x) for x in torch.flip(w, (0, 1)).reshape(-1)]
+        self.form, self.boundary = form, boundary
+        self.cells = self.ny * self.nx
+        self.n = self.cells if form == "heat" else 2 * self.cells
+
+    def constrain(self, coef=None):
+        return () if coef is None else (coef.reshape(-1).contiguous(),)
+
+    def size(self, *_):
+        return self.n
+
+    def fill(self, desc, coef=None):
+        if coef is not None:
+            _check_dtype(desc, coef, "StencilOp: the coefficient field")
+            if coef.numel() != self.cells:
+                raise ValueError(f"StencilOp expects a field of {self.ny} x {self.nx} = {self.cells} values, got {coef.numel()}")
+            desc.val = coef.data_ptr()
+        desc.st_ny, desc.st_nx = self.ny, self.nx
+        desc.st_form, desc.st_boundary = self._FORMS[self.form], self._BOUNDARIES[self.boundary]
+        desc.st_w = (C.c_double * 9)(*self.weights)
+
+    def new_grads(self, coef=None):
+        s = _lib.OpGrads()
+        if coef is None:
+            return s, ()
+        g = torch.zeros_like(coef)
         s.val = g.data_ptr()
         return s, (g,)
 

@@ -5,6 +5,10 @@ Covers the pieces of the reference's ``util/pde_util.py`` that are thin composit
 the small helpers ``mesh_tensorproduct`` / ``loss_mse`` / ``loss_mse_relative`` (:14-15, :160-173) and the 5-point wave operator
 (:18-20,126-157) expressed as a native CSR operator so that the non-symmetric Arnoldi forward/adjoint kernels run it
 end to end.  The dense k x k ``expm`` / ``eigh`` are torch calls (k <= ~100: plumbing, differentiable).
+
+The reference's stencil vector fields themselves -- ``pde_heat`` / ``pde_heat_affine`` / ``pde_heat_anisotropic`` /
+``pde_wave_anisotropic`` with ``boundary_dirichlet`` / ``boundary_neumann`` and any 3x3 stencil (:18-157) -- run matrix-free on
+``operators.StencilOp``; ``wave_operator`` (the assembled CSR form of one of them) stays.
 """
 
 from __future__ import annotations
@@ -13,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import arnoldi, lanczos
-from ..operators import CsrOp, RowShardedOp, as_operator
+from ..operators import BoundOp, CsrOp, NativeOp, RowShardedOp, StencilOp, as_operator
 
 
 def expm_arnoldi(krylov_depth, *, max_squarings: int = 32, reortho="full", custom_vjp=True):
@@ -89,10 +93,15 @@ def loss_mse_relative(*, nugget, reduce=torch.mean):
 
 
 def solver_expm(t0, t1, vector_field, /, expm):
-    """util/pde_util.py:240-252 for flat states: y(t1) = exp((t1 - t0) A) y0 with A v = vector_field(v, *p)."""
+    """util/pde_util.py:240-252 for flat states: y(t1) = exp((t1 - t0) A) y0 with A v = vector_field(v, *p).  A native operator or
+    a bound one (``rhs.flat`` of the stencil vector fields below) acts on the flattened state and goes to ``expm`` as it is: the
+    Krylov loop then applies it natively instead of calling back into Python."""
 
     def solve(y0, *p):
         shape = y0.shape
+        if isinstance(vector_field, (NativeOp, BoundOp, RowShardedOp)):
+            out, info = expm(vector_field, t1 - t0, y0.reshape(-1), *p)
+            return out.reshape(shape), info
         out, info = expm(lambda v, *q: vector_field(v.reshape(shape), *q).reshape(-1), t1 - t0, y0.reshape(-1), *p)
         return out.reshape(shape), info
 
@@ -126,6 +135,102 @@ def sampler_lanczos(*, mean, cov_matvec, num, lanczos_rank):
 def stencil_laplacian(dx):
     """util/pde_util.py:18-20."""
     return torch.tensor([[0.0, 1.0, 0.0], [1.0, -2.0, 1.0], [0.0, 1.0, 0.0]], dtype=torch.float64) / dx**2
+
+
+def stencil_advection_diffusion(dx):
+    """util/pde_util.py:23-28 (asymmetric: the advection part changes sign under a flip)."""
+    diffusion = torch.tensor([[0.0, 1.0, 0.0], [1.0, -2.0, 1.0], [0.0, 1.0, 0.0]], dtype=torch.float64) / dx**2
+    advection = torch.tensor([[0.0, 1.0, 0.0], [1.0, 0.0, -1.0], [0.0, -1.0, 0.0]], dtype=torch.float64) / (2 * dx)
+    return diffusion + advection
+
+
+def boundary_dirichlet():
+    """util/pde_util.py:146-150: zero padding by one cell.  ``pad.kind`` names the rule for the native operator."""
+
+    def pad(x, /):
+        return torch.nn.functional.pad(x, (1, 1, 1, 1))
+
+    pad.kind = "dirichlet"
+    return pad
+
+
+def boundary_neumann():
+    """util/pde_util.py:153-157: edge padding by one cell (the nearest cell, per axis)."""
+
+    def pad(x, /):
+        return torch.nn.functional.pad(x[None, None], (1, 1, 1, 1), mode="replicate")[0, 0]
+
+    pad.kind = "neumann"
+    return pad
+
+
+def _boundary_kind(boundary):
+    kind = boundary if isinstance(boundary, str) else getattr(boundary, "kind", None)
+    if kind not in ("dirichlet", "neumann"):
+        raise TypeError("boundary must be boundary_dirichlet() or boundary_neumann() (the native stencil operator implements these "
+                        "two padding rules; an arbitrary pad callable has no kind)")
+    return kind
+
+
+def _stencil_rhs(form, stencil, boundary, coef, shape, drift=None):
+    """rhs(x) on (ny, nx) / (2, ny, nx) states through StencilOp; ``rhs.flat`` (when the grid is known up front): the bound
+    operator on flattened states, for solver_expm / expm_arnoldi / arnoldi.hessenberg."""
+    kind = _boundary_kind(boundary)
+    blocks = 1 if form == "heat" else 2
+    ops = {}
+
+    def operator(grid):
+        if grid not in ops:
+            ops[grid] = StencilOp(grid, stencil, form=form, boundary=kind)
+        return ops[grid]
+
+    def rhs(x, /):
+        if x.dim() != blocks + 1 or (blocks == 2 and x.shape[0] != 2):
+            raise ValueError(f"expected a state of shape {'(ny, nx)' if blocks == 1 else '(2, ny, nx)'}, got {tuple(x.shape)}")
+        op = operator(tuple(x.shape[-2:]))
+        fx = (op(x.reshape(-1)) if coef is None else op(x.reshape(-1), coef.to(x.dtype))).reshape(x.shape)
+        return fx if drift is None else fx + drift
+
+    if shape is not None and drift is None:
+        rhs.flat = operator(tuple(shape)).bind(*(() if coef is None else (coef,)))
+    return rhs
+
+
+def pde_heat(c: float, /, stencil, *, boundary, shape=None):
+    """util/pde_util.py:74-87: rhs(u) = c conv(stencil, pad(u)); the constant is folded into the stencil weights.  ``shape``
+    (ny, nx), optional: also provide ``rhs.flat``."""
+
+    def parametrize():
+        return _stencil_rhs("heat", c * torch.as_tensor(stencil, dtype=torch.float64), boundary, None, shape)
+
+    return parametrize, {}
+
+
+def pde_heat_affine(c: float, drift_like, /, stencil, *, boundary):
+    """util/pde_util.py:90-103: pde_heat plus a drift field, added in torch (affine, so there is no ``rhs.flat``)."""
+
+    def parametrize(*, drift):
+        return _stencil_rhs("heat", c * torch.as_tensor(stencil, dtype=torch.float64), boundary, None, None, drift=drift)
+
+    return parametrize, {"drift": torch.empty_like(drift_like)}
+
+
+def pde_heat_anisotropic(scale_like, /, stencil, *, constrain, boundary):
+    """util/pde_util.py:106-123: rhs(u, du) = (-constrain(scale) o conv(stencil, pad(u)), du)."""
+
+    def parametrize(*, scale):
+        return _stencil_rhs("heat2", stencil, boundary, constrain(scale), tuple(scale_like.shape))
+
+    return parametrize, {"scale": torch.empty_like(scale_like)}
+
+
+def pde_wave_anisotropic(scale_like, /, stencil, *, constrain, boundary):
+    """util/pde_util.py:126-143: rhs(u, du) = (du, constrain(scale) o conv(stencil, pad(u)))."""
+
+    def parametrize(*, scale):
+        return _stencil_rhs("wave", stencil, boundary, constrain(scale), tuple(scale_like.shape))
+
+    return parametrize, {"scale": torch.empty_like(scale_like)}
 
 
 def wave_operator(res: int, dx: float, *, boundary: str = "neumann", device=None, dtype=torch.float64):

@@ -26,10 +26,20 @@
 extern "C" {
 #endif
 
-#define MFX_VERSION 201 /* 201: + mfx_comm_rccl_count */
+#define MFX_VERSION 201 /* 201: + mfx_comm_rccl_count.  MFX_OP_STENCIL and the st_* fields at the end of mfx_operator are additive (no
+                           bump, as for mfx_op_grads.x): callers that zero-fill the descriptor never select them */
 
 enum { MFX_F32 = 0, MFX_F64 = 1 };
-enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3 };
+enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4 };
+/* Matrix-free 3x3 stencil operator (MFX_OP_STENCIL; util/pde_util.py:18-157).  With S the padded 3x3 correlation below and coef
+ * the coefficient field:
+ *   MFX_STENCIL_HEAT   state u,       n = ny nx:    y = coef o (S u)                  pde_heat                (:74-87)
+ *   MFX_STENCIL_HEAT2  state (u, du), n = 2 ny nx:  y = (-coef o S u, du)             pde_heat_anisotropic    (:106-123)
+ *   MFX_STENCIL_WAVE   state (u, du), n = 2 ny nx:  y = (du, coef o S u)              pde_wave_anisotropic    (:126-143)
+ * MFX_BOUNDARY_DIRICHLET pads with zeros (:146-150); MFX_BOUNDARY_NEUMANN pads with the nearest cell, clamped on each axis
+ * independently (jnp.pad mode="edge", :153-157). */
+enum { MFX_STENCIL_HEAT = 0, MFX_STENCIL_HEAT2 = 1, MFX_STENCIL_WAVE = 2 };
+enum { MFX_BOUNDARY_DIRICHLET = 0, MFX_BOUNDARY_NEUMANN = 1 };
 enum { MFX_REORTHO_NONE = 0, MFX_REORTHO_FULL = 1 };
 /* Arithmetic of the fp32 RBF Gram kernels (wide batches; fp64 operators ignore it):
  *   MFX_RBF_FP32          exact fp32 MFMA everywhere (v_mfma_f32_32x32x2_f32, a round-to-nearest fmaf chain)
@@ -70,11 +80,14 @@ typedef int (*mfx_callback_fn)(void* ctx, int mode, const void* x, int64_t ldx, 
                                int64_t ldaux, void* y, int64_t ldy, int64_t p, int64_t n,
                                void* stream);
 
+typedef double mfx_stencil_weights[9]; /* the 3 x 3 weights of a stencil operator, row-major (mfx_operator.st_w) */
+
 /* Operator descriptor: a POD of borrowed pointers, valid for the duration of one call.
  * Replaces the reference's `matvec(v, *params)` closures:
  *   DENSE    p @ x                          tests/test_lanczos/test_tridiag_forward.py:18
  *   CSR      BCOO((vals, idx)) @ x          experiments/benchmarks/.../suite_sparse/benchmark.py:64-68
  *   RBF      (K(X,X) + noise I) x           util/gp_util.py:69-184 (RBF / Matern kernels),225-226,525-549
+ *   STENCIL  coef o conv3x3(pad(u))         util/pde_util.py:74-157 (heat / wave systems, both boundaries)
  *   CALLBACK any Python callable                                                              */
 typedef struct mfx_operator {
   int32_t kind;  /* MFX_OP_* */
@@ -91,7 +104,7 @@ typedef struct mfx_operator {
   const int32_t* crow;
   const int32_t* col;
   const int32_t* row;
-  const void* val;
+  const void* val; /* CSR: the nnz stored values.  STENCIL: the coefficient field, (st_ny, st_nx) row-major, NULL = all ones */
   int64_t nnz;
   int64_t max_row_nnz; /* longest row of A (of A and A^T when the transpose structure is present); 0 = unknown */
   const int32_t* t_crow;
@@ -123,10 +136,25 @@ typedef struct mfx_operator {
    * The matrix-core Gram kernels need row0 % 64 == 0.  The single-device drivers require nrows == 0. */
   int64_t row0;
   int64_t nrows;
+
+  /* STENCIL: a (st_ny, st_nx) row-major grid, both >= 1, cell (r, c) at index r st_nx + c; st_form = MFX_STENCIL_*, st_boundary =
+   * MFX_BOUNDARY_*.  st_w are HOST values: st_w[(dr + 1) * 3 + (dc + 1)] multiplies u_pad[r + dr, c + dc], so
+   * (S u)[r, c] = sum_{dr, dc} st_w[...] u_pad[r + dr, c + dc] -- a correlation; the reference's convolve2d(stencil, padded, "valid")
+   * is this with the stencil flipped on both axes.  Weights that are exactly 0 are not read.  The coefficient field is `val` above
+   * (a constant factor such as pde_heat's c is folded into st_w by the caller).  The transpose needs no extra structure.
+   * Refused before any launch: MFX_ERR_INVALID for st_ny or st_nx < 1, n != st_ny st_nx (HEAT) or != 2 st_ny st_nx (HEAT2, WAVE), an
+   * unknown st_form or st_boundary; MFX_ERR_UNSUPPORTED for more than 2^31 - 1 cells, a row block (nrows > 0) and the row-sharded
+   * drivers (sharding a stencil needs a halo exchange).  The element access of mfx_partial_cholesky refuses the kind, as for CSR. */
+  int32_t st_ny;
+  int32_t st_nx;
+  int32_t st_form;
+  int32_t st_boundary;
+  mfx_stencil_weights st_w;
 } mfx_operator;
 
 /* Parameter-gradient outputs (device pointers, ACCUMULATED into, caller zero-fills).  NULL = skip.
- *   dense_a (n, n) row-major, leading dimension = n;  val (nnz);
+ *   dense_a (n, n) row-major, leading dimension = n;  val (CSR: nnz stored values; STENCIL: the (st_ny, st_nx) coefficient field,
+ *     val[i] += sigma sum_b L_b[blk + i] (S R_b.u)[i] with (sigma, blk) = (+1, 0) HEAT, (-1, 0) HEAT2, (+1, st_ny st_nx) WAVE);
  *   lengthscale (d if ard else 1), outputscale (1), noise (1);
  *   x (n, d) row-major in the operator's dtype: the gradient with respect to the raw kernel inputs X of a kernel-Gram operator
  *     (the reference differentiates the inputs its lazy kernel closes over, arnoldi.py:21-23, util/gp_util.py:221-231).
