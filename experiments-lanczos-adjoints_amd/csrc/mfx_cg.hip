@@ -771,6 +771,7 @@ int mfx_pcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n,
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
   MFX_CHECK_KERNEL_FN(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   CgWs w;
@@ -810,6 +811,7 @@ int mfx_mbcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "mfx_mbcg_solve: no row block (nrows > 0): mBCG is not row-sharded");
   MFX_CHECK_KERNEL_FN(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   CgWs w;
@@ -868,6 +870,7 @@ int mfx_pcg_solve_sharded(const mfx_operator* op, const mfx_comm* comm, const vo
   MFX_REQUIRE(op->n == n && n >= 1 && p >= 1, MFX_ERR_INVALID, "mfx_pcg_solve_sharded: bad sizes n=%lld p=%lld", (long long)n, (long long)p);
   MFX_REQUIRE(op->kind != MFX_OP_CALLBACK, MFX_ERR_UNSUPPORTED, "row sharding needs a native operator");
   MFX_REQUIRE(op->kind != MFX_OP_STENCIL, MFX_ERR_UNSUPPORTED, "row sharding a stencil operator needs a halo exchange");
+  MFX_REQUIRE(op->kind != MFX_OP_GGN, MFX_ERR_UNSUPPORTED, "row sharding a GGN operator is not implemented: every output row sums over all samples");
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_INVALID, "pass the whole operator: the driver takes this rank's rows itself");
   MFX_REQUIRE(comm->allreduce_sum && comm->allgather, MFX_ERR_INVALID, "communicator without callbacks");
   MFX_REQUIRE(comm->world >= 1 && comm->rank >= 0 && comm->rank < comm->world, MFX_ERR_INVALID, "bad rank %d of %d", comm->rank, comm->world);
@@ -881,6 +884,7 @@ int mfx_pcg_solve_sharded(const mfx_operator* op, const mfx_comm* comm, const vo
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
   MFX_CHECK_KERNEL_FN(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   CgWs w;
@@ -906,6 +910,7 @@ int mfx_pcg_solve_reortho(const mfx_operator* op, const void* b, int64_t ldb, in
   MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
   MFX_CHECK_KERNEL_FN(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   Precond pc{precond_lt, precond_minv, precond_shift, rank};
   if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
   const int64_t kdim = (precond_lt && rank > num_matvecs) ? rank : num_matvecs;

@@ -1,0 +1,379 @@
+// libmfx: the matrix-free generalised Gauss-Newton operator of an MLP (MFX_OP_GGN) -- the linearised-Laplace calibration of the
+// reference (util/bnn_util.py:263-293 ggn_vp_parallel, :477-499 callibration_loss) with theta and the data fixed:
+//
+//   y = sum_i J_i^T H_i J_i v + alpha v        J_i = d f(theta; x_i) / d theta,  H_i = loss Hessian in the logits
+//
+// Everything that depends on theta and the data is a tape (layer inputs a_l, activation slopes dact_l, softmax p) that the caller
+// computes once; include/mfx.h (struct mfx_ggn_net) has the formulas and the theta layout.  One application is two kernels:
+//
+//   k_ggn_tiles   a workgroup takes tiles of kGgnTS = 32 samples and a GROUP of probes (4 in fp32, 2 in fp64): one wave per probe,
+//                 lane j = unit j of the layer at hand.  A chunk of a tape matrix (64 units x 32 samples) is staged ONCE in LDS,
+//                 transposed, and read by every wave of the group -- the reads are wave-uniform, so they broadcast (the slopes
+//                 dact_l and the softmax go through the same buffer: every tape matrix is fetched once per group).  A thread keeps
+//                 its unit's 32 tangents (forward) / cotangents (backward) in registers; between layers they pass through LDS.
+//                 The first layer (d_in up to 65536) streams x in chunks of 64 columns, once forward against V_W_1 and once
+//                 backward into y_W_1; the other layers (<= 64 units) are one chunk each.  Per-workgroup sums over its samples
+//                 go to the workspace: part[workgroup][probe][P], every entry written (first tile) before it is added to.
+//   k_ggn_reduce  y = sum over workgroups, in index order, + alpha v.
+//
+// No atomics and a fixed summation order: bit-identical from run to run; the arithmetic of a probe does not involve its group,
+// so its bits do not depend on how many probes share the call.  The shift gradient (mfx_op_grads.noise += sum_b L_b . R_b) is a
+// two-stage dot product with fp64 partial sums in the workspace.
+#include "mfx_internal.h"
+
+namespace mfx {
+
+constexpr int kGgnTS = 32;           // samples per tile
+constexpr int kGgnW = 64;            // widest layer past the input = lanes of a wave; also the chunk of d_in staged at a time
+constexpr int kGgnMaxIn = 65536;     // widest input
+constexpr int kGgnMaxBlocks = 64;    // workgroups along the samples: bounds the partial sums (nblk x p x P values)
+constexpr int kGgnDotBlocks = 256;   // workgroups of the shift-gradient dot product
+
+template <typename T>
+struct GgnGroup {  // probes per workgroup: LDS holds (1 + group) x 64 x 32 values (46 KiB in fp32, 52 KiB in fp64)
+  static constexpr int value = sizeof(T) == 4 ? 4 : 2;
+};
+
+template <typename T>
+struct GgnArgs {
+  int L, loss;
+  int64_t N, P, ntiles;
+  int w[MFX_GGN_MAX_LAYERS + 1];
+  int64_t off[MFX_GGN_MAX_LAYERS + 1];  // off[l], l = 1..L: bias of layer l in theta; its kernel follows at off[l] + w[l]
+  const T* theta;
+  const T* act[MFX_GGN_MAX_LAYERS];
+  const T* dact[MFX_GGN_MAX_LAYERS];
+  const T* prob;
+};
+
+template <typename T>
+struct GgnLds {
+  static constexpr int TSP = kGgnTS + 16 / (int)sizeof(T);  // row padded by 16 bytes: the column writes of a wave spread over banks
+  T aT[kGgnW][TSP];                                         // chunk of a tape matrix, [unit][sample]
+  T tb[GgnGroup<T>::value][kGgnW][TSP];                     // per probe: tangents t_l / cotangents g_l, [unit][sample]
+};
+
+// aT[kk][i] = M[i0 + i][k0 + kk] for the nv samples of the tile and the units of the chunk, 0 elsewhere (M: (N, width) row-major)
+template <typename T>
+__device__ __forceinline__ void ggn_stage(GgnLds<T>& sm, const T* __restrict__ M, int width, int k0, int64_t i0, int nv) {
+  for (int e = threadIdx.x; e < kGgnW * kGgnTS; e += blockDim.x) {
+    const int kk = e & (kGgnW - 1), i = e / kGgnW;
+    const int k = k0 + kk;
+    sm.aT[kk][i] = (i < nv && k < width) ? M[(i0 + i) * width + k] : T(0);
+  }
+}
+
+// part[idx] = val on a workgroup's first tile, += afterwards: the workspace is never read before it is written
+template <typename T>
+__device__ __forceinline__ void ggn_accumulate(T* __restrict__ out, int64_t idx, T val, bool first) {
+  out[idx] = first ? val : out[idx] + val;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T> a, const T* __restrict__ x, int64_t ldx, int64_t p,
+                                                                       T* __restrict__ part) {
+  constexpr int G = GgnGroup<T>::value, TS = kGgnTS, W = kGgnW;
+  __shared__ __attribute__((aligned(16))) GgnLds<T> sm;
+  const int j = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.y * G + g;
+  const bool live = b < p;  // wave-uniform; a wave without a probe still stages and meets the barriers
+  const T* __restrict__ v = x + (live ? b : 0) * ldx;
+  T* __restrict__ out = part + ((int64_t)blockIdx.x * p + (live ? b : 0)) * a.P;
+  const int L = a.L, c = a.w[L];
+  T s[TS];  // this unit's tangents, then cotangents, for the samples of the tile
+
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const bool first = tile == (int64_t)blockIdx.x;
+    const int64_t i0 = tile * TS;
+    const int nv = a.N - i0 < TS ? (int)(a.N - i0) : TS;
+
+    // ---- forward tangent: s_l = V_W_l^T a_{l-1} + v_b_l + W_l^T t_{l-1} ----
+    for (int l = 1; l <= L; ++l) {
+      const int wi = a.w[l - 1], wo = a.w[l];
+      const bool on = live && j < wo;
+      const T* __restrict__ vW = v + a.off[l] + wo;
+      const T* __restrict__ Wl = a.theta + a.off[l] + wo;
+      const T vb = on ? v[a.off[l] + j] : T(0);
+#pragma unroll
+      for (int i = 0; i < TS; ++i) s[i] = vb;
+      for (int k0 = 0; k0 < wi; k0 += W) {
+        __syncthreads();  // the chunk before this one has been consumed
+        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        __syncthreads();
+        if (on) {
+          const int kc = wi - k0 < W ? wi - k0 : W;
+          if (l == 1) {
+#pragma unroll 2
+            for (int kk = 0; kk < kc; ++kk) {
+              const T vw = vW[(int64_t)(k0 + kk) * wo + j];
+#pragma unroll
+              for (int i = 0; i < TS; ++i) s[i] += sm.aT[kk][i] * vw;
+            }
+          } else {  // wi <= 64: one chunk, kk is the unit of layer l - 1
+#pragma unroll 2
+            for (int kk = 0; kk < kc; ++kk) {
+              const T vw = vW[kk * wo + j], wt = Wl[kk * wo + j];
+#pragma unroll
+              for (int i = 0; i < TS; ++i) s[i] += sm.aT[kk][i] * vw + sm.tb[g][kk][i] * wt;
+            }
+          }
+        }
+      }
+      __syncthreads();  // every wave is done with t_{l-1} and with the last chunk
+      if (l < L) {      // the slopes of the tile, staged once for the whole group (0 past the end of the tape)
+        ggn_stage<T>(sm, a.dact[l], wo, 0, i0, nv);
+        __syncthreads();
+      }
+      if (on) {
+        if (l < L) {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = sm.aT[j][i] * s[i];
+        } else {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
+        }
+      }
+    }
+
+    // ---- H product: u = p o t_L - p (p . t_L), or u = t_L; samples past the end of the tape contribute nothing ----
+    if (a.loss == MFX_GGN_CROSS_ENTROPY) ggn_stage<T>(sm, a.prob, c, 0, i0, nv);  // aT is free: the barrier above
+    __syncthreads();
+    if (live && j < c) {
+      if (a.loss == MFX_GGN_CROSS_ENTROPY) {
+#pragma unroll
+        for (int i = 0; i < TS; ++i) s[i] = T(0);
+        for (int m = 0; m < c; ++m) {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) s[i] += sm.aT[m][i] * sm.tb[g][m][i];
+        }
+#pragma unroll
+        for (int i = 0; i < TS; ++i) {
+          const T pj = sm.aT[j][i];
+          s[i] = pj * sm.tb[g][j][i] - pj * s[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < TS; ++i) s[i] = i < nv ? sm.tb[g][j][i] : T(0);
+      }
+    }
+
+    // ---- backward: y_b_l += g_l, y_W_l += a_{l-1} g_l^T, g_{l-1} = dact_{l-1} o (W_l g_l) ----
+    for (int l = L; l >= 1; --l) {
+      const int wi = a.w[l - 1], wo = a.w[l];
+      const bool on = live && j < wo;
+      if (on) {
+        T sb = T(0);
+#pragma unroll
+        for (int i = 0; i < TS; ++i) sb += s[i];
+        ggn_accumulate<T>(out, a.off[l] + j, sb, first);
+      }
+      for (int k0 = 0; k0 < wi; k0 += W) {
+        __syncthreads();
+        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        __syncthreads();
+        if (on) {
+          const int kc = wi - k0 < W ? wi - k0 : W;
+          const int64_t base = a.off[l] + wo + (int64_t)k0 * wo + j;
+#pragma unroll 2
+          for (int kk = 0; kk < kc; ++kk) {
+            T acc = T(0);
+#pragma unroll
+            for (int i = 0; i < TS; ++i) acc += sm.aT[kk][i] * s[i];
+            ggn_accumulate<T>(out, base + (int64_t)kk * wo, acc, first);
+          }
+        }
+      }
+      if (l > 1) {
+        __syncthreads();  // tb is free (t_L, or the cotangents of the layer above, have been read)
+        if (on) {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
+        }
+        ggn_stage<T>(sm, a.dact[l - 1], wi, 0, i0, nv);  // aT is free as well: the slopes of layer l - 1, staged once for the group
+        __syncthreads();
+        if (live && j < wi) {
+          const T* __restrict__ Wrow = a.theta + a.off[l] + wo + (int64_t)j * wo;
+#pragma unroll
+          for (int i = 0; i < TS; ++i) s[i] = T(0);
+          for (int m = 0; m < wo; ++m) {
+            const T wt = Wrow[m];
+#pragma unroll
+            for (int i = 0; i < TS; ++i) s[i] += sm.tb[g][m][i] * wt;
+          }
+#pragma unroll
+          for (int i = 0; i < TS; ++i) s[i] = sm.aT[j][i] * s[i];
+        }
+      }
+    }
+    __syncthreads();  // the next tile stages into aT and writes tb
+  }
+}
+
+// y_b[i] = sum_blk part[blk][b][i] + alpha x_b[i], the workgroups in index order
+template <typename T>
+__global__ __launch_bounds__(256) void k_ggn_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, const T* __restrict__ alpha,
+                                                    const T* __restrict__ x, int64_t ldx, T* __restrict__ y, int64_t ldy) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, p = gridDim.y;
+  if (i >= P) return;
+  T acc = T(0);
+  for (int64_t blk = 0; blk < nblk; ++blk) acc += part[(blk * p + b) * P + i];
+  y[b * ldy + i] = acc + alpha[0] * x[b * ldx + i];
+}
+
+// partial[blockIdx.x] = this workgroup's share of sum_b L_b . R_b (fp64 sums, fixed order)
+template <typename T>
+__global__ __launch_bounds__(256) void k_ggn_dot(const T* __restrict__ L, int64_t ldl, const T* __restrict__ R, int64_t ldr, int64_t batch,
+                                                 int64_t n, double* __restrict__ partial) {
+  __shared__ double wsum[4];
+  double acc = 0.0;
+  for (int64_t b = 0; b < batch; ++b) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+      acc += (double)L[b * ldl + i] * (double)R[b * ldr + i];
+    }
+  }
+  acc = wave_sum_all<double>(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void k_ggn_dot_final(const double* __restrict__ partial, int nblk, T* __restrict__ g) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) acc += partial[i];
+  acc = wave_sum_all<double>(acc);
+  if (threadIdx.x == 0) g[0] += (T)acc;
+}
+
+static int64_t ggn_params(const mfx_ggn_net* net) {
+  int64_t P = 0;
+  for (int l = 1; l <= net->nlayers; ++l) P += ((int64_t)net->width[l - 1] + 1) * net->width[l];
+  return P;
+}
+
+static int64_t ggn_blocks(int64_t N) {
+  const int64_t tiles = (N + kGgnTS - 1) / kGgnTS;
+  return tiles < kGgnMaxBlocks ? tiles : kGgnMaxBlocks;
+}
+
+static int64_t ggn_dot_blocks(int64_t n) {
+  const int64_t blocks = (n + 255) / 256;
+  return blocks < kGgnDotBlocks ? blocks : kGgnDotBlocks;
+}
+
+int check_ggn(const mfx_operator* op) {
+  if (!op || op->kind != MFX_OP_GGN) return MFX_OK;
+  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
+  MFX_REQUIRE(net, MFX_ERR_INVALID, "GGN operator: ctx (the mfx_ggn_net) is NULL");
+  MFX_REQUIRE(net->nlayers >= 1 && net->nlayers <= MFX_GGN_MAX_LAYERS, MFX_ERR_INVALID, "GGN operator: nlayers = %d is outside 1..%d",
+              net->nlayers, MFX_GGN_MAX_LAYERS);
+  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "GGN operator: unknown loss %d",
+              net->loss);
+  MFX_REQUIRE(net->nsamples >= 1, MFX_ERR_INVALID, "GGN operator: nsamples = %lld must be at least 1", (long long)net->nsamples);
+  const int L = net->nlayers;
+  for (int l = 0; l <= L; ++l) {
+    MFX_REQUIRE(net->width[l] >= 1, MFX_ERR_INVALID, "GGN operator: width[%d] = %d must be at least 1", l, net->width[l]);
+  }
+  MFX_REQUIRE(net->theta, MFX_ERR_INVALID, "GGN operator: theta is NULL");
+  MFX_REQUIRE(op->noise, MFX_ERR_INVALID, "GGN operator: noise (the shift alpha) is NULL");
+  for (int l = 0; l < L; ++l) {
+    MFX_REQUIRE(net->act[l], MFX_ERR_INVALID, "GGN operator: act[%d] is NULL", l);
+    MFX_REQUIRE(l == 0 || net->dact[l], MFX_ERR_INVALID, "GGN operator: dact[%d] is NULL", l);
+  }
+  MFX_REQUIRE(net->loss != MFX_GGN_CROSS_ENTROPY || net->prob, MFX_ERR_INVALID, "GGN operator: prob is NULL (cross-entropy)");
+  const int64_t P = ggn_params(net);
+  MFX_REQUIRE(op->n == P, MFX_ERR_INVALID, "GGN operator: n = %lld, but the widths give P = %lld parameters", (long long)op->n,
+              (long long)P);
+  MFX_REQUIRE(net->width[0] <= kGgnMaxIn, MFX_ERR_UNSUPPORTED, "GGN operator: width[0] = %d exceeds the input limit %d", net->width[0],
+              kGgnMaxIn);
+  for (int l = 1; l <= L; ++l) {
+    MFX_REQUIRE(net->width[l] <= kGgnW, MFX_ERR_UNSUPPORTED, "GGN operator: width[%d] = %d exceeds the layer limit %d", l,
+                net->width[l], kGgnW);
+  }
+  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "GGN operator: no row block (nrows > 0): every output row sums over all samples");
+  return MFX_OK;
+}
+
+int check_ggn_grads(const mfx_operator* op, const mfx_op_grads* grads) {
+  if (!op || op->kind != MFX_OP_GGN || !grads) return MFX_OK;
+  MFX_REQUIRE(!grads->x && !grads->dense_a && !grads->val, MFX_ERR_UNSUPPORTED,
+              "GGN operator: only the shift gradient (grads->noise) exists; x, dense_a and val must be NULL (gradients with respect "
+              "to theta or the inputs need third derivatives)");
+  return MFX_OK;
+}
+
+int64_t ggn_workspace_bytes(const mfx_operator* op, int64_t p_apply) {
+  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
+  if (!net || net->nlayers < 1 || net->nlayers > MFX_GGN_MAX_LAYERS || net->nsamples < 1) return 256;  // refused before any use
+  const int64_t apply = ggn_blocks(net->nsamples) * (p_apply > 0 ? p_apply : 1) * ggn_params(net) * (int64_t)dtype_size(op->dtype);
+  const int64_t dot = kGgnDotBlocks * (int64_t)sizeof(double);
+  return align_up(apply > dot ? apply : dot, 256);
+}
+
+template <typename T>
+static int ggn_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int64_t ldy, int64_t p, void* ws, int64_t ws_bytes,
+                       hipStream_t stream) {
+  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
+  GgnArgs<T> a{};
+  a.L = net->nlayers;
+  a.loss = net->loss;
+  a.N = net->nsamples;
+  a.P = op->n;
+  a.ntiles = (a.N + kGgnTS - 1) / kGgnTS;
+  int64_t off = 0;
+  for (int l = 0; l <= a.L; ++l) {
+    a.w[l] = net->width[l];
+    if (l >= 1) {
+      a.off[l] = off;
+      off += ((int64_t)a.w[l - 1] + 1) * a.w[l];
+    }
+    if (l < a.L) {
+      a.act[l] = (const T*)net->act[l];
+      a.dact[l] = (const T*)net->dact[l];
+    }
+  }
+  a.theta = (const T*)net->theta;
+  a.prob = (const T*)net->prob;
+  const int64_t nblk = ggn_blocks(a.N);
+  const int64_t need = nblk * p * a.P * (int64_t)sizeof(T);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "GGN operator: workspace too small: need %lld bytes", (long long)need);
+  constexpr int G = GgnGroup<T>::value;
+  k_ggn_tiles<T><<<dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G, 0, stream>>>(a, x, ldx, p, (T*)ws);
+  MFX_CHECK_LAUNCH();
+  k_ggn_reduce<T><<<dim3((unsigned)((a.P + 255) / 256), (unsigned)p), 256, 0, stream>>>((const T*)ws, nblk, a.P, (const T*)op->noise, x,
+                                                                                      ldx, y, ldy);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+int ggn_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t p, void* ws, int64_t ws_bytes,
+              hipStream_t stream) {
+  MFX_TRY(check_ggn(op));
+  if (op->dtype == MFX_F32) return ggn_apply_t<float>(op, (const float*)x, ldx, (float*)y, ldy, p, ws, ws_bytes, stream);
+  return ggn_apply_t<double>(op, (const double*)x, ldx, (double*)y, ldy, p, ws, ws_bytes, stream);
+}
+
+template <typename T>
+static int ggn_grad_t(const mfx_operator* op, const T* L, int64_t ldl, const T* R, int64_t ldr, int64_t batch, T* gnoise, void* ws,
+                      int64_t ws_bytes, hipStream_t stream) {
+  const int nblk = (int)ggn_dot_blocks(op->n);
+  MFX_REQUIRE(ws && nblk * (int64_t)sizeof(double) <= ws_bytes, MFX_ERR_WORKSPACE, "GGN operator: workspace too small: need %lld bytes",
+              (long long)(nblk * sizeof(double)));
+  k_ggn_dot<T><<<nblk, 256, 0, stream>>>(L, ldl, R, ldr, batch, op->n, (double*)ws);
+  MFX_CHECK_LAUNCH();
+  k_ggn_dot_final<T><<<1, 64, 0, stream>>>((const double*)ws, nblk, gnoise);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+int ggn_grad(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr, int64_t batch, const mfx_op_grads* grads,
+             void* ws, int64_t ws_bytes, hipStream_t stream) {
+  MFX_TRY(check_ggn(op));
+  MFX_TRY(check_ggn_grads(op, grads));
+  if (!grads->noise) return MFX_OK;
+  if (op->dtype == MFX_F32)
+    return ggn_grad_t<float>(op, (const float*)L, ldl, (const float*)R, ldr, batch, (float*)grads->noise, ws, ws_bytes, stream);
+  return ggn_grad_t<double>(op, (const double*)L, ldl, (const double*)R, ldr, batch, (double*)grads->noise, ws, ws_bytes, stream);
+}
+
+}  // namespace mfx

@@ -174,6 +174,16 @@ int stencil_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, i
 int stencil_grad(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr, int64_t batch, void* gval,
                  hipStream_t stream);
 
+// GGN operator of an MLP (mfx_ggn.hip).  check_ggn: every refusal of the kind, before any launch (MFX_OK for other kinds);
+// check_ggn_grads: the gradient fields the kind does not have; ggn_grad adds sum_b L_b . R_b to grads->noise (NULL: no launch)
+int check_ggn(const mfx_operator* op);
+int check_ggn_grads(const mfx_operator* op, const mfx_op_grads* grads);
+int64_t ggn_workspace_bytes(const mfx_operator* op, int64_t p_apply);
+int ggn_apply(const mfx_operator* op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t p, void* ws, int64_t ws_bytes,
+              hipStream_t stream);
+int ggn_grad(const mfx_operator* op, const void* L, int64_t ldl, const void* R, int64_t ldr, int64_t batch, const mfx_op_grads* grads,
+             void* ws, int64_t ws_bytes, hipStream_t stream);
+
 int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m);
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);

@@ -991,6 +991,7 @@ static int check_common(const mfx_operator* op, int64_t n, int64_t k, int64_t p)
   MFX_REQUIRE(op->n == n, MFX_ERR_INVALID, "operator size %lld != n=%lld", (long long)op->n, (long long)n);
   MFX_CHECK_KERNEL_FN(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_INVALID, "the Krylov drivers take the whole operator (nrows = 0); row shards go through mfx_*_sharded");
   MFX_REQUIRE(k >= 1 && k <= n, MFX_ERR_INVALID, "Parameter depth %lld is outside the expected range", (long long)k);
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "p=%lld exceeds the grid limit 65535", (long long)p);
@@ -1043,6 +1044,7 @@ static GraphKey driver_key(int fn_id, const mfx_operator* op, int64_t n, int64_t
                            const void* ws, int64_t ws_bytes, const void* stream) {
   GraphKey key;
   key.add(fn_id).add(*op).add(n).add(k).add(p).add(ws).add(ws_bytes).add(stream);
+  if (op->kind == MFX_OP_GGN && op->ctx) key.add(*(const mfx_ggn_net*)op->ctx);  // the launches hold what ctx points at, not ctx
   const mfx_op_grads none{};
   key.add(grads ? *grads : none).add(grads != nullptr);
   return key;
@@ -1118,6 +1120,7 @@ static int check_sharded(const mfx_operator* op, const mfx_comm* cm, int64_t n, 
   MFX_REQUIRE(cm && cm->allreduce_sum && cm->allgather, MFX_ERR_INVALID, "communicator without callbacks");
   MFX_REQUIRE(op->kind != MFX_OP_CALLBACK, MFX_ERR_UNSUPPORTED, "row sharding needs a native operator");
   MFX_REQUIRE(op->kind != MFX_OP_STENCIL, MFX_ERR_UNSUPPORTED, "row sharding a stencil operator needs a halo exchange");
+  MFX_REQUIRE(op->kind != MFX_OP_GGN, MFX_ERR_UNSUPPORTED, "row sharding a GGN operator is not implemented: every output row sums over all samples");
   MFX_REQUIRE(cm->world >= 1 && cm->rank >= 0 && cm->rank < cm->world, MFX_ERR_INVALID, "bad rank %d of %d", cm->rank, cm->world);
   MFX_REQUIRE(cm->nloc >= 64 && cm->nloc % 64 == 0, MFX_ERR_INVALID, "rows per rank (%lld) must be a positive multiple of 64", (long long)cm->nloc);
   MFX_REQUIRE((int64_t)cm->world * cm->nloc >= n && (int64_t)(cm->world - 1) * cm->nloc < n, MFX_ERR_INVALID,

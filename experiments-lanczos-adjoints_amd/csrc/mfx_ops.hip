@@ -1254,6 +1254,7 @@ static int rbf_grad_x(const mfx_operator* op, const T* L, int64_t ldl, const T* 
 }
 
 int check_grads_x(const mfx_operator* op, const mfx_op_grads* grads, bool sharded) {
+  MFX_TRY(check_ggn_grads(op, grads));
   if (!op || !grads || !grads->x) return MFX_OK;
   MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_INVALID, "the input gradient (grads->x) needs a kernel-Gram operator");
   MFX_REQUIRE(!sharded && op->nrows == 0, MFX_ERR_UNSUPPORTED,
@@ -1485,6 +1486,7 @@ PrepScope::~PrepScope() {
 
 int64_t op_workspace_bytes(const mfx_operator* op, int64_t batch_hint, int64_t p_apply) {
   if (op->kind == MFX_OP_RBF) return rbf_carve(op, nullptr, 0, nullptr, batch_hint, p_apply);
+  if (op->kind == MFX_OP_GGN) return ggn_workspace_bytes(op, p_apply);
   return 256;
 }
 
@@ -1494,6 +1496,7 @@ static int op_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int
   const int64_t n = op->n;
   const int64_t row0 = op_row0(op), nrow = op_nrows(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   MFX_REQUIRE(row0 >= 0 && nrow >= 1 && row0 + nrow <= n, MFX_ERR_INVALID, "row block [%lld, +%lld) outside the operator (n = %lld)",
               (long long)row0, (long long)nrow, (long long)n);
   switch (op->kind) {
@@ -1533,6 +1536,8 @@ static int op_apply_t(const mfx_operator* op, const T* x, int64_t ldx, T* y, int
       return rbf_apply<T>(op, x, ldx, y, ldy, p, ws, ws_bytes, stream);  // symmetric: transpose ignored
     case MFX_OP_STENCIL:
       return stencil_apply(op, x, ldx, y, ldy, p, transpose, stream);
+    case MFX_OP_GGN:
+      return ggn_apply(op, x, ldx, y, ldy, p, ws, ws_bytes, stream);  // symmetric: transpose ignored
     default:
       set_error("unknown operator kind %d", op->kind);
       return MFX_ERR_UNSUPPORTED;
@@ -1572,6 +1577,7 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
   const int64_t n = op->n;
   const int64_t row0 = op_row0(op), nrow = op_nrows(op);
   MFX_TRY(check_stencil(op));
+  MFX_TRY(check_ggn(op));
   MFX_REQUIRE(row0 >= 0 && nrow >= 1 && row0 + nrow <= n, MFX_ERR_INVALID, "row block [%lld, +%lld) outside the operator (n = %lld)",
               (long long)row0, (long long)nrow, (long long)n);
   MFX_TRY(check_grads_x(op, grads, false));
@@ -1602,6 +1608,8 @@ static int op_vjp_params_t(const mfx_operator* op, const T* L, int64_t ldl, cons
     }
     case MFX_OP_STENCIL:
       return stencil_grad(op, L, ldl, R, ldr, batch, grads->val, stream);
+    case MFX_OP_GGN:
+      return ggn_grad(op, L, ldl, R, ldr, batch, grads, ws, ws_bytes, stream);
     default:
       set_error("unknown operator kind %d", op->kind);
       return MFX_ERR_UNSUPPORTED;

@@ -17,9 +17,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFX_LIBRARY_PATH") or os.path.join(_HERE, "libmfx.so")  # override: A/B builds
 
 MFX_F32, MFX_F64 = 0, 1
-OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL = 0, 1, 2, 3, 4
+OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL, OP_GGN = 0, 1, 2, 3, 4, 5
 STENCIL_HEAT, STENCIL_HEAT2, STENCIL_WAVE = 0, 1, 2
 BOUNDARY_DIRICHLET, BOUNDARY_NEUMANN = 0, 1
+GGN_CROSS_ENTROPY, GGN_MSE = 0, 1
+GGN_MAX_LAYERS = 8
 REORTHO_NONE, REORTHO_FULL = 0, 1
 RBF_FP32, RBF_F16X3_MATVEC, RBF_F16X3 = 0, 1, 2
 KERNEL_RBF, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 1, 2, 3
@@ -75,6 +77,21 @@ class Operator(C.Structure):
         ("st_form", C.c_int32),
         ("st_boundary", C.c_int32),
         ("st_w", C.c_double * 9),
+    ]
+
+
+class GgnNet(C.Structure):
+    """mirror of ``struct mfx_ggn_net``: what ``Operator.ctx`` points at for ``OP_GGN`` (a host struct of device pointers)."""
+
+    _fields_ = [
+        ("nlayers", C.c_int32),
+        ("loss", C.c_int32),
+        ("nsamples", C.c_int64),
+        ("width", C.c_int32 * (GGN_MAX_LAYERS + 1)),
+        ("theta", C.c_void_p),
+        ("act", C.c_void_p * GGN_MAX_LAYERS),
+        ("dact", C.c_void_p * GGN_MAX_LAYERS),
+        ("prob", C.c_void_p),
     ]
 
 

@@ -14,6 +14,7 @@ whole Krylov loop, the transposed matvec and the parameter-gradient sweep run as
                                     (and X itself when X.requires_grad: the reference's closure conversion
                                     makes the inputs its lazy kernel closes over differentiable too)
   StencilOp(shape, stencil, ...)    params = (coef,) or ()        util/pde_util.py:74-157 (3x3 heat / wave systems, matrix-free)
+  GgnMlpOp(x_train, theta, widths)  params = (alpha,)             util/bnn_util.py:263-293,477-499 (GGN of an MLP + alpha I, theta fixed)
   CallbackOp(fn)                    any Python ``fn(v, *params)`` (torch ops); per-step host control
 
 ``op.bind(*params)`` freezes the parameters into a zero-argument-parameter matvec (what the GP code
@@ -101,6 +102,8 @@ class RowShardedOp:
         if isinstance(op, StencilOp):
             raise NotImplementedError("row sharding a StencilOp needs a halo exchange of the grid rows next to a shard's edge, which is "
                                       "not implemented; shard the probes, or assemble the system (pde_util.wave_operator) as a CsrOp")
+        if isinstance(op, GgnMlpOp):
+            raise NotImplementedError("row sharding a GgnMlpOp is not implemented: every output row sums over all samples; shard the probes")
         _refuse_input_grad(op)
         self.op, self.comm = op, comm
         # sparse operators: neighbour exchange of the entries this rank's rows read (the halo of a stencil) instead of
@@ -612,6 +615,99 @@ class StencilOp(NativeOp):
             return s, ()
         g = torch.zeros_like(coef)
         s.val = g.data_ptr()
+        return s, (g,)
+
+
+class GgnMlpOp(NativeOp):
+    """The generalised Gauss-Newton matrix of an MLP plus a shift, matrix-free (the reference's ggn_vp_parallel inside
+    callibration_loss, util/bnn_util.py:263-293, 477-499):
+
+      A(alpha) v = sum_i J_i^T H_i J_i v + alpha v,   J_i = d f(theta; x_i) / d theta,   H_i = loss Hessian in the logits
+
+    ``theta`` is the flat parameter vector in the order of flax's ravel_pytree for ``model_mlp``: per layer the bias (width[l]), then
+    the kernel (width[l-1], width[l]) row-major; ``widths = (d_in, ..., c)``.  theta and x_train are FIXED (the calibration loss is
+    differentiated in alpha alone): everything that depends on them -- layer inputs, activation slopes, softmax probabilities -- is
+    computed once here with torch ops and kept as ``op.tape``; one application is one fused HIP pass over that tape
+    (csrc/mfx_ggn.hip).  ``op(v, alpha)`` is differentiable in v and alpha; gradients with respect to theta or x_train would need
+    third derivatives and are refused."""
+
+    kind = _lib.OP_GGN
+    _LOSSES = {"cross_entropy": _lib.GGN_CROSS_ENTROPY, "mse": _lib.GGN_MSE}
+
+    def __init__(self, x_train, theta, widths, *, activation="tanh", loss="cross_entropy"):
+        if activation not in ("tanh", "relu"):
+            raise ValueError("activation must be 'tanh' or 'relu'")
+        if loss not in self._LOSSES:
+            raise ValueError(f"loss must be one of {sorted(self._LOSSES)}")
+        if theta.requires_grad or x_train.requires_grad:
+            raise NotImplementedError("GgnMlpOp holds theta and x_train fixed: a gradient with respect to them needs third derivatives of "
+                                      "the network, which the reference never takes; pass detached tensors")
+        self.widths = tuple(int(w) for w in widths)
+        nl = len(self.widths) - 1
+        if not 1 <= nl <= _lib.GGN_MAX_LAYERS or min(self.widths) < 1:
+            raise ValueError(f"GgnMlpOp: widths {self.widths} must name 1..{_lib.GGN_MAX_LAYERS} layers of at least one unit")
+        self.n = sum((wi + 1) * wo for wi, wo in zip(self.widths[:-1], self.widths[1:]))
+        if theta.dim() != 1 or theta.numel() != self.n:
+            raise ValueError(f"GgnMlpOp: widths {self.widths} have {self.n} parameters, theta has shape {tuple(theta.shape)}")
+        x = x_train.reshape(x_train.shape[0], -1)
+        if x.shape[0] < 1 or x.shape[1] != self.widths[0] or x.dtype != theta.dtype or x.device != theta.device:
+            raise ValueError(f"GgnMlpOp: x_train {tuple(x_train.shape)} ({x.dtype}, {x.device}) does not match widths[0] = "
+                             f"{self.widths[0]} and theta ({theta.dtype}, {theta.device})")
+        self.activation, self.loss = activation, loss
+        self.theta = theta.detach().contiguous()
+        self.tape = self._build_tape(x)
+        net = _lib.GgnNet()
+        net.nlayers, net.loss, net.nsamples = nl, self._LOSSES[loss], x.shape[0]
+        net.width = (C.c_int32 * (_lib.GGN_MAX_LAYERS + 1))(*self.widths)
+        net.theta = self.theta.data_ptr()
+        for l in range(nl):
+            net.act[l] = self.tape["act"][l].data_ptr()
+            if l >= 1:
+                net.dact[l] = self.tape["dact"][l].data_ptr()
+        if loss == "cross_entropy":
+            net.prob = self.tape["prob"].data_ptr()
+        self.net = net  # the descriptor's ctx points here: lives as long as the operator
+
+    def _build_tape(self, x):
+        """{"act": [a_0 = x, ..., a_{L-1}], "dact": [None, phi'(z_1), ..., phi'(z_{L-1})], "logits", "prob" (None for mse)}"""
+        with torch.no_grad():
+            a, off = x.contiguous(), 0
+            act, dact = [a], [None]
+            nl = len(self.widths) - 1
+            for l in range(1, nl + 1):
+                wi, wo = self.widths[l - 1], self.widths[l]
+                z = a @ self.theta[off + wo : off + wo + wi * wo].reshape(wi, wo) + self.theta[off : off + wo]
+                off += (wi + 1) * wo
+                if l < nl:
+                    if self.activation == "tanh":
+                        a = torch.tanh(z)
+                        d = 1 - a * a
+                    else:
+                        a = torch.relu(z)
+                        d = (z > 0).to(z.dtype)
+                    act.append(a.contiguous())
+                    dact.append(d.contiguous())
+            prob = torch.softmax(z, dim=-1).contiguous() if self.loss == "cross_entropy" else None
+        return {"act": act, "dact": dact, "logits": z, "prob": prob}
+
+    def constrain(self, alpha):
+        return (alpha.reshape(1),)
+
+    def size(self, *_):
+        return self.n
+
+    def fill(self, desc, alpha):
+        _check_dtype(desc, self.theta, "GgnMlpOp: theta and the tape")
+        _check_dtype(desc, alpha, "GgnMlpOp: alpha")
+        if alpha.numel() != 1 or alpha.device != self.theta.device:
+            raise ValueError("GgnMlpOp: alpha is one value on the device of theta")
+        desc.noise = alpha.data_ptr()
+        desc.ctx = C.addressof(self.net)
+
+    def new_grads(self, alpha):
+        g = torch.zeros_like(alpha)
+        s = _lib.OpGrads()
+        s.noise = g.data_ptr()
         return s, (g,)
 
 

@@ -1,16 +1,23 @@
-"""Lanczos posterior samplers of the reference's ``util/bnn_util.py`` (:372-409) -- MI355X build ("next" tier, §8f-3).
+"""The linearised-Laplace side of the reference's ``util/bnn_util.py`` -- MI355X build ("next" tier, §8f-3).
 
-Only the samplers are here: they are compositions of ``lanczos.tridiag(reortho="full")`` (the hot-path kernels) with a small dense
-factorisation of the k x k tridiagonal matrix (torch, k <= ~100).  The network / GGN construction side of bnn_util (flax models,
-``ggn_fun``) is outside SURVEY.md §8; ``ggn_fun`` / ``ggn_vp`` are whatever produces the matrix or the matvec.
+Samplers (:372-409): compositions of ``lanczos.tridiag(reortho="full")`` (the hot-path kernels) with a small dense factorisation of
+the k x k tridiagonal matrix (torch, k <= ~100).
+
+Calibration (:21-40, 43-61, 120-203, 218-228, 477-518): the reference's MLP on a flat parameter vector, the dense GGN baseline
+(``ggn_full``, torch.func), the matrix-free GGN operator (``ggn_operator`` -> ``operators.GgnMlpOp``, one fused HIP pass over a tape
+per matvec), the log-determinant solvers and the calibration losses.  The reference differentiates those losses in ``log_alpha``
+alone, with theta and the data fixed; so does this module: a theta that requires grad is refused.  Conv nets, ViTs,
+``hutchinson_diagonal`` / ``bnn_baselines`` and data loaders are not here.
 """
 
 from __future__ import annotations
 
+import math
+
 import torch
 
-from .. import lanczos
-from ..operators import DenseOp
+from .. import hutchinson, lanczos
+from ..operators import DenseOp, GgnMlpOp
 
 
 def _normal(key, shape, like):
@@ -63,3 +70,228 @@ def lanczos_sampler(*, ggn_vp, num_samples, lanczos_rank, key, params_vec):
     inv_eigvals = torch.where(small, torch.zeros_like(w), 1 / torch.where(small, torch.ones_like(w), w))
     sample = torch.sqrt(inv_eigvals) * eps[:, :lanczos_rank]
     return params_vec + torch.einsum("bnk,bk->bn", eigvecs, sample)
+
+
+# ------------------------------------------------------------------------------------------------
+# the reference's MLP on a flat parameter vector (util/bnn_util.py:21-40, 502-518)
+# ------------------------------------------------------------------------------------------------
+_HIDDEN = (50, 50, 5, 5)
+_ACTIVATIONS = {"tanh": torch.tanh, "relu": torch.relu}
+
+
+def _activation_name(activation):
+    if activation in _ACTIVATIONS:
+        return activation
+    for name, fn in _ACTIVATIONS.items():
+        if activation is fn:
+            return name
+    raise ValueError("activation must be 'tanh' or 'relu' (or torch.tanh / torch.relu)")
+
+
+def mlp_unflatten(theta, widths):
+    """flat theta -> [{"bias": (w_l,), "kernel": (w_{l-1}, w_l)}, ...]: per layer the bias, then the kernel row-major -- the order of
+    flax's ravel_pytree for the reference's model (Dense_0.bias, Dense_0.kernel, Dense_1.bias, ...)."""
+    out, off = [], 0
+    for wi, wo in zip(widths[:-1], widths[1:]):
+        out.append({"bias": theta[off : off + wo], "kernel": theta[off + wo : off + wo + wi * wo].reshape(wi, wo)})
+        off += (wi + 1) * wo
+    if off != theta.numel():
+        raise ValueError(f"widths {tuple(widths)} have {off} parameters, theta has {theta.numel()}")
+    return out
+
+
+def mlp_apply(theta, x, widths, activation="tanh"):
+    """logits of the MLP with flat parameters ``theta`` (plain torch ops: differentiable, torch.func-transformable)"""
+    phi = _ACTIVATIONS[_activation_name(activation)]
+    a = x.reshape(x.shape[0], -1)
+    layers = mlp_unflatten(theta, widths)
+    for l, layer in enumerate(layers):
+        a = a @ layer["kernel"] + layer["bias"]
+        if l + 1 < len(layers):
+            a = phi(a)
+    return a
+
+
+def model_mlp(*, out_dims, activation="tanh"):
+    """util/bnn_util.py:21-40: Dense(50), Dense(50), Dense(5), Dense(5), Dense(out_dims) with ``activation`` between them.
+    Returns (init, apply) on the FLAT theta: ``init(key, x)`` -> theta (kernels LeCun-normal, biases zero, flax's defaults) for
+    widths ``init.widths(d_in) = (d_in, 50, 50, 5, 5, out_dims)``; ``apply(theta, x)`` -> logits."""
+    name = _activation_name(activation)
+
+    def widths(d_in):
+        return (int(d_in), *_HIDDEN, int(out_dims))
+
+    def init(key, x):
+        w = widths(x.reshape(x.shape[0], -1).shape[1])
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(int(key))
+        parts = []
+        for wi, wo in zip(w[:-1], w[1:]):
+            parts += [torch.zeros(wo, dtype=torch.float64), (torch.randn(wi, wo, generator=gen, dtype=torch.float64) / math.sqrt(wi)).reshape(-1)]
+        return torch.cat(parts).to(dtype=x.dtype, device=x.device)
+
+    def apply(theta, x):
+        return mlp_apply(theta, x, widths(x.reshape(x.shape[0], -1).shape[1]), name)
+
+    init.widths = apply.widths = widths
+    apply.activation = name
+    return init, apply
+
+
+def vectorize_nn(model_fn, params):
+    """util/bnn_util.py:502-518 for the parameter trees of this module (a list of {"bias", "kernel"} per layer):
+    -> (params_vec, unflatten_fn, model_apply_vec)."""
+    shapes = [tuple(layer["kernel"].shape) for layer in params]
+    widths = (shapes[0][0], *(s[1] for s in shapes))
+    params_vec = torch.cat([t.reshape(-1) for layer in params for t in (layer["bias"], layer["kernel"])])
+
+    def unflatten_fn(vec):
+        return mlp_unflatten(vec, widths)
+
+    def model_apply_vec(params_vectorized, x):
+        return model_fn(unflatten_fn(params_vectorized), x)
+
+    return params_vec, unflatten_fn, model_apply_vec
+
+
+# ------------------------------------------------------------------------------------------------
+# metrics and losses (util/bnn_util.py:43-61, 106-114)
+# ------------------------------------------------------------------------------------------------
+def metric_accuracy(*, probs, labels_hot):
+    assert probs.dim() == 2 and labels_hot.dim() == 2
+    return (probs.argmax(-1) == labels_hot.argmax(-1)).to(probs.dtype).mean(-1)
+
+
+def metric_nll(*, logits, labels_hot, sum_or_mean_fun=torch.sum):
+    assert logits.dim() == 2 and labels_hot.dim() == 2
+    nll = (labels_hot * torch.log_softmax(logits, -1)).sum(-1)
+    return -sum_or_mean_fun(nll, 0)
+
+
+def metric_confidence(*, probs):
+    assert probs.dim() == 2
+    return probs.max(-1).values.mean(0)
+
+
+def loss_training_cross_entropy_single(logits, labels_hot):
+    return -(torch.log_softmax(logits, -1) * labels_hot).sum(-1)
+
+
+def loss_training_mse_single(pred, target):
+    """0.5 |pred - target|^2: logit Hessian = I (the "mse" loss of GgnMlpOp)"""
+    return 0.5 * ((pred - target) ** 2).sum(-1)
+
+
+# ------------------------------------------------------------------------------------------------
+# the GGN: dense baseline and matrix-free operator (util/bnn_util.py:218-228, 263-293)
+# ------------------------------------------------------------------------------------------------
+def ggn_full(*, loss_single, model_fun, param_unflatten):
+    """util/bnn_util.py:218-228: sum_i J_i^T H_i J_i + alpha I as a dense matrix (torch.func; the baseline the operator is tested against)"""
+
+    def ggn_fun(alpha, variables, x_train, y_train):
+        def f(v):
+            return model_fun(param_unflatten(v), x_train)
+
+        H = torch.func.vmap(torch.func.hessian(loss_single, argnums=0))(f(variables), y_train)
+        J = torch.func.jacrev(f)(variables)  # (N, c, P)
+        ggn = torch.einsum("nci,ncd,ndj->ij", J, H, J)
+        return ggn + alpha * torch.eye(J.shape[-1], dtype=J.dtype, device=J.device)
+
+    return ggn_fun
+
+
+def ggn_operator(theta, x_train, widths, *, activation="tanh", loss="cross_entropy"):
+    """The matrix-free counterpart of ``ggn_full`` for an MLP: ``op(v, alpha)`` = (sum_i J_i^T H_i J_i + alpha I) v as one fused HIP
+    pass over a tape built once here (theta and x_train fixed; with one-hot labels the labels do not enter either Hessian)."""
+    return GgnMlpOp(x_train, theta, widths, activation=_activation_name(activation), loss=loss)
+
+
+# ------------------------------------------------------------------------------------------------
+# log-determinants and the calibration losses (util/bnn_util.py:120-203, 477-499)
+# ------------------------------------------------------------------------------------------------
+def solver_logdet_dense():
+    def logdet(M):
+        return torch.linalg.slogdet(M)[1]
+
+    return logdet
+
+
+def slq_log_clipped(*, clip_value=1.0):
+    def log(x):
+        eps = torch.finfo(x.dtype).eps
+        return torch.log(torch.where(x < eps, torch.full_like(x, clip_value), x))
+
+    return log
+
+
+def _slq_mean(integrand, sampler, key, slq_num_batches, *args):
+    estimate = hutchinson.hutchinson(integrand, sampler)
+    if torch.is_tensor(key):  # explicit probes: one batch
+        return estimate(key, *args)
+    values = torch.stack([estimate(k, *args) for k in hutchinson.split(key, slq_num_batches)])
+    return values.mean(0)
+
+
+def solver_logdet_slq(*, lanczos_rank, slq_num_samples, slq_num_batches):
+    """util/bnn_util.py:173-186: SLQ on a dense matrix M (the clipped log as matrix function)"""
+
+    def logdet(M, key):
+        sampler = hutchinson.sampler_rademacher(M[0], num=slq_num_samples)
+        integrand = lanczos.integrand_spd(slq_log_clipped(), lanczos_rank, DenseOp().bind(M))
+        return _slq_mean(integrand, sampler, key, slq_num_batches)
+
+    return logdet
+
+
+def solver_logdet_slq_implicit(*, lanczos_rank, slq_num_samples, slq_num_batches, N, x_like=None):
+    """util/bnn_util.py:189-203: SLQ on a matvec ``Av(v, *args)`` (a native operator, or any callable).  ``key``: an integer seed, or
+    the (slq_num_samples, N) probes themselves; ``x_like`` fixes dtype and device of generated probes (default: float32 on cuda)."""
+
+    def logdet(Av, key, *args):
+        like = key[0] if torch.is_tensor(key) else (x_like if x_like is not None else torch.ones(N, device="cuda"))[:N]
+        sampler = hutchinson.sampler_rademacher(like, num=slq_num_samples)
+        integrand = lanczos.integrand_spd(torch.log, lanczos_rank, Av)
+        return _slq_mean(integrand, sampler, key, slq_num_batches, *args)
+
+    return logdet
+
+
+def loss_calibration(*, ggn_fun, hyperparam_unconstrain, logdet_fun):
+    """util/bnn_util.py:120-135.  ``ggn_fun(alpha, variables, x_train, y_train)`` returns whatever ``logdet_fun`` takes: a dense matrix
+    (``ggn_full`` with ``solver_logdet_dense`` / ``solver_logdet_slq``) or a bound operator (``ggn_operator(...).bind(alpha)``)."""
+
+    def loss(a, variables, x_train, y_train, *logdet_params):
+        alpha = hyperparam_unconstrain(a)
+        log_prior = len(variables) / 2 * torch.log(alpha) - 0.5 * alpha * torch.dot(variables, variables)
+        M = ggn_fun(alpha, variables, x_train, y_train)
+        return -(log_prior - 0.5 * logdet_fun(M, *logdet_params))
+
+    return loss
+
+
+def callibration_loss(model_apply, unflatten, hyperparam_unconstrain, n_params, *, loss="cross_entropy", operator=None):
+    """util/bnn_util.py:477-499 (the reference's spelling): SLQ with Lanczos rank 10 and 10 probes on the matrix-free GGN + alpha I.
+    ``model_apply`` is ``model_mlp``'s apply (it names the widths and the activation; ``unflatten`` is unused: theta stays flat).
+    ``loss(log_alpha, params_vec, img, label, key)`` is differentiable in ``log_alpha`` only.  The operator (and its tape) is kept
+    while the SAME two tensor objects come back (the cache holds them, so their identity cannot be reused by other tensors; tensors
+    modified in place between calls are the caller's to avoid) and rebuilt otherwise; ``operator=`` fixes what is applied instead (``lambda tape_op, alpha: bound matvec`` --
+    the tests put a DenseOp of the same matrix there)."""
+    cache = {}
+
+    def loss_fn(log_alpha, params_vec, img, label, key):
+        if params_vec.requires_grad or img.requires_grad:
+            raise NotImplementedError("callibration_loss differentiates log_alpha only: theta and the data are fixed (their gradients "
+                                      "need third derivatives of the network, which the reference never takes)")
+        alpha = hyperparam_unconstrain(log_alpha)
+        if cache.get("theta") is not params_vec or cache.get("img") is not img:
+            d_in = img.reshape(img.shape[0], -1).shape[1]
+            cache["theta"], cache["img"] = params_vec, img
+            cache["op"] = ggn_operator(params_vec, img, model_apply.widths(d_in), activation=model_apply.activation, loss=loss)
+        op = cache["op"]
+        bound = op.bind(alpha) if operator is None else operator(op, alpha)
+        logdet_fun = solver_logdet_slq_implicit(lanczos_rank=10, slq_num_samples=10, slq_num_batches=1, N=n_params, x_like=params_vec)
+        logdet = logdet_fun(bound, key)
+        log_prior = torch.log(alpha) * n_params - alpha * torch.dot(params_vec, params_vec)
+        return -(log_prior - logdet)
+
+    return loss_fn

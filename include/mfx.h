@@ -27,10 +27,11 @@ extern "C" {
 #endif
 
 #define MFX_VERSION 201 /* 201: + mfx_comm_rccl_count.  MFX_OP_STENCIL and the st_* fields at the end of mfx_operator are additive (no
-                           bump, as for mfx_op_grads.x): callers that zero-fill the descriptor never select them */
+                           bump, as for mfx_op_grads.x): callers that zero-fill the descriptor never select them.  MFX_OP_GGN is
+                           additive too: its data travels through the existing `ctx` pointer, no struct grows */
 
 enum { MFX_F32 = 0, MFX_F64 = 1 };
-enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4 };
+enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4, MFX_OP_GGN = 5 };
 /* Matrix-free 3x3 stencil operator (MFX_OP_STENCIL; util/pde_util.py:18-157).  With S the padded 3x3 correlation below and coef
  * the coefficient field:
  *   MFX_STENCIL_HEAT   state u,       n = ny nx:    y = coef o (S u)                  pde_heat                (:74-87)
@@ -82,12 +83,46 @@ typedef int (*mfx_callback_fn)(void* ctx, int mode, const void* x, int64_t ldx, 
 
 typedef double mfx_stencil_weights[9]; /* the 3 x 3 weights of a stencil operator, row-major (mfx_operator.st_w) */
 
+/* Matrix-free generalised Gauss-Newton operator of an MLP (MFX_OP_GGN; util/bnn_util.py:263-293, 477-499):
+ *   A(alpha) = sum_i J_i^T H_i J_i + alpha I,   J_i = d f(theta; x_i) / d theta (c x P),   H_i = loss Hessian in the logits (c x c)
+ * with theta and the data FIXED: everything that depends on them is a tape the caller computes once (layer inputs, activation
+ * slopes, softmax probabilities); the operator is one pass over that tape per application.  mfx_operator.ctx points at this HOST
+ * struct (borrowed, valid for the call); its pointers are device pointers in the operator's dtype.  alpha is the device scalar
+ * mfx_operator.noise; its gradient is mfx_op_grads.noise += sum_b L_b . R_b.
+ * theta layout (also the layout of every vector the operator takes and returns): for each layer l = 1..L the bias (width[l]
+ * values), then the kernel (width[l-1], width[l]) row-major -- flax's ravel_pytree order for the reference's model_mlp.
+ * P = sum_l (width[l-1] + 1) width[l] must equal mfx_operator.n.  Per sample i and vector v, in that layout:
+ *   t_0 = 0;  s_l = V_W_l^T a_{l-1} + v_b_l + W_l^T t_{l-1};  t_l = dact_l o s_l (l < L),  t_L = s_L
+ *   u = p o t_L - p (p . t_L)  (MFX_GGN_CROSS_ENTROPY)   or   u = t_L  (MFX_GGN_MSE)
+ *   g_L = u;  y_b_l += g_l;  y_W_l += a_{l-1} g_l^T;  g_{l-1} = dact_{l-1} o (W_l g_l);        y = sum_i (.) + alpha v
+ * Symmetric: `transpose` is ignored.  The sum over samples runs in a fixed order (per-workgroup partial sums in the workspace,
+ * then one pass that adds them and alpha v): no floating-point atomics, bit-identical from run to run, and the bits of a vector's
+ * result do not depend on how many vectors share the call.
+ * Refused before any launch.  MFX_ERR_INVALID: ctx, theta, noise, act[l] (l < L), dact[l] (1 <= l < L) or prob (cross-entropy)
+ * NULL; nlayers outside 1..MFX_GGN_MAX_LAYERS; a width < 1; nsamples < 1; n != P; an unknown loss.  MFX_ERR_UNSUPPORTED:
+ * width[0] > 65536 or width[l] > 64 for l >= 1 (the limits of the kernels); a row block (nrows > 0); the row-sharded drivers;
+ * grads->x, grads->dense_a or grads->val non-NULL (gradients with respect to theta or the inputs need third derivatives; the
+ * reference never takes them).  The element access of mfx_partial_cholesky refuses the kind, as for CSR. */
+enum { MFX_GGN_CROSS_ENTROPY = 0, MFX_GGN_MSE = 1 };
+#define MFX_GGN_MAX_LAYERS 8
+typedef struct mfx_ggn_net {
+  int32_t nlayers;                       /* L >= 1 dense layers */
+  int32_t loss;                          /* MFX_GGN_* */
+  int64_t nsamples;                      /* N >= 1 */
+  int32_t width[MFX_GGN_MAX_LAYERS + 1]; /* width[0] = d_in ... width[L] = c */
+  const void* theta;                     /* device, P values, layout above */
+  const void* act[MFX_GGN_MAX_LAYERS];   /* act[l] = a_l, (N, width[l]) row-major, l = 0..L-1; a_0 = x */
+  const void* dact[MFX_GGN_MAX_LAYERS];  /* dact[l] = phi'(z_l), (N, width[l]), l = 1..L-1; dact[0] unused */
+  const void* prob;                      /* (N, c) softmax; NULL for MSE */
+} mfx_ggn_net;
+
 /* Operator descriptor: a POD of borrowed pointers, valid for the duration of one call.
  * Replaces the reference's `matvec(v, *params)` closures:
  *   DENSE    p @ x                          tests/test_lanczos/test_tridiag_forward.py:18
  *   CSR      BCOO((vals, idx)) @ x          experiments/benchmarks/.../suite_sparse/benchmark.py:64-68
  *   RBF      (K(X,X) + noise I) x           util/gp_util.py:69-184 (RBF / Matern kernels),225-226,525-549
  *   STENCIL  coef o conv3x3(pad(u))         util/pde_util.py:74-157 (heat / wave systems, both boundaries)
+ *   GGN      (sum_i J_i^T H_i J_i + alpha I) x  util/bnn_util.py:263-293,477-499 (MLP, fixed theta; struct mfx_ggn_net above)
  *   CALLBACK any Python callable                                                              */
 typedef struct mfx_operator {
   int32_t kind;  /* MFX_OP_* */
@@ -123,9 +158,9 @@ typedef struct mfx_operator {
   int32_t kernel_fn; /* MFX_KERNEL_*: which stationary kernel the Gram operator evaluates; any other value is MFX_ERR_INVALID */
   const void* lengthscale;
   const void* outputscale;
-  const void* noise;
+  const void* noise; /* GGN: the shift alpha (1) */
 
-  /* CALLBACK */
+  /* CALLBACK; GGN: ctx = const mfx_ggn_net* (host) */
   mfx_callback_fn callback;
   void* ctx;
 
@@ -155,7 +190,8 @@ typedef struct mfx_operator {
 /* Parameter-gradient outputs (device pointers, ACCUMULATED into, caller zero-fills).  NULL = skip.
  *   dense_a (n, n) row-major, leading dimension = n;  val (CSR: nnz stored values; STENCIL: the (st_ny, st_nx) coefficient field,
  *     val[i] += sigma sum_b L_b[blk + i] (S R_b.u)[i] with (sigma, blk) = (+1, 0) HEAT, (-1, 0) HEAT2, (+1, st_ny st_nx) WAVE);
- *   lengthscale (d if ard else 1), outputscale (1), noise (1);
+ *   lengthscale (d if ard else 1), outputscale (1), noise (1; GGN: the shift alpha, noise += sum_b L_b . R_b, the only field
+ *     that kind fills);
  *   x (n, d) row-major in the operator's dtype: the gradient with respect to the raw kernel inputs X of a kernel-Gram operator
  *     (the reference differentiates the inputs its lazy kernel closes over, arnoldi.py:21-23, util/gp_util.py:221-231).
  *     Every entry point that takes grads honours it (mfx_op_vjp_params, mfx_arnoldi_adjoint, mfx_lanczos_adjoint; the PCG backward
