@@ -26,12 +26,11 @@ Reference quirk Q1 is reproduced: the forward pass re-orthogonalises unless ``re
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from .operators import CallbackOp, DenseOp, RowShardedOp, _PtrRegistry, as_operator, differentiable_inputs
+from .operators import (CallbackOp, DenseOp, DriverCall, RowShardedOp, as_operator, differentiable_inputs, rebuild_params, reduce_grads_,
+                        stash_params)
 
 
 def hessenberg(
@@ -80,10 +79,7 @@ def hessenberg(
             Qb, H, r, c = _autodiff.batched(_autodiff.arnoldi_forward, V, op, int(krylov_depth), params, second_pass=second_pass)
             return (Qb, H, r, c) if batched else (Qb[0], H[0], r[0], c[0])
         cparams = op.constrain(*params)
-        if sharded:
-            Qkn, H, r, c = _ArnoldiShardedFn.apply(op, int(krylov_depth), second_pass, reortho, custom_vjp, V, *cparams)
-        else:
-            Qkn, H, r, c = _ArnoldiFn.apply(op, int(krylov_depth), second_pass, reortho, custom_vjp, V, *cparams)
+        Qkn, H, r, c = _ArnoldiFn.apply(op, int(krylov_depth), second_pass, reortho, custom_vjp, V, *cparams)
         Q = Qkn.transpose(-1, -2)  # reference layout (n, k); storage stays (k, n)
         if not batched:
             return Q[0], H[0], r[0], c[0]
@@ -102,13 +98,12 @@ def _complex_forward(op, k, second_pass, V, params):
     cdt, dev = V.dtype, V.device
     rdt = torch.float32 if cdt == torch.complex64 else torch.float64
     _lib.require_device(V)
-    keep = None
     if isinstance(op, DenseOp):  # native dense kernel on the (2n, 2n) real form [[Re, -Im], [Im, Re]] per entry
         (A,) = op.constrain(*params)
         A = A.to(cdt)
         M = torch.stack([torch.stack([A.real, -A.imag], -1), torch.stack([A.imag, A.real], -1)], 1).reshape(2 * n, 2 * n)
-        desc = op.descriptor((M.contiguous(),), rdt, 2 * n)
-        hold = M
+        M = M.contiguous()  # (alive until the call below has returned)
+        call = DriverCall(op, (M,), rdt, 2 * n)
     else:
         fn = op.fn if isinstance(op, CallbackOp) else op
 
@@ -116,63 +111,48 @@ def _complex_forward(op, k, second_pass, V, params):
             y = fn(torch.view_as_complex(x.view(n, 2)), *ps)
             return torch.view_as_real(y.to(cdt).contiguous()).reshape(2 * n)
 
-        reg = _PtrRegistry()
-        desc, keep, _ = CallbackOp(real_form).make(tuple(params), rdt, 2 * n, reg, want_grads=False)
-        hold = None
+        call = DriverCall(CallbackOp(real_form), tuple(params), rdt, 2 * n)
     Q = torch.empty((p, k, n), dtype=cdt, device=dev)
     H = torch.empty((p, k, k), dtype=cdt, device=dev)
     r = torch.empty((p, n), dtype=cdt, device=dev)
     c = torch.empty((p,), dtype=cdt, device=dev)
-    ws = _lib.scratch(int(lib.mfx_complex_workspace_bytes(C.byref(desc), n, k, p)), dev)
-    if keep is not None:
-        for t in (V, Q, r):
-            reg.add(torch.view_as_real(t))
-        reg.add_bytes(ws, rdt)
-    with _lib.busy(ws):
-        rc = lib.mfx_arnoldi_forward_complex(C.byref(desc), _lib.ptr(V), n, k, p, int(second_pass), _lib.ptr(Q), _lib.ptr(H),
-                                             _lib.ptr(r), _lib.ptr(c), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    if keep is not None and keep[1]:
-        raise keep[1][0]
-    _lib.check(rc)
-    del hold
+    ws = call.take(lib.mfx_complex_workspace_bytes, n, k, p, device=dev, visible=[torch.view_as_real(t) for t in (V, Q, r)])
+    call.run(lib.mfx_arnoldi_forward_complex, _lib.ptr(V), n, k, p, int(second_pass), _lib.ptr(Q), _lib.ptr(H), _lib.ptr(r),
+             _lib.ptr(c), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     return Q, H, r, c
 
 
 class _ArnoldiFn(torch.autograd.Function):
+    """``mfx_arnoldi_forward`` / ``mfx_arnoldi_adjoint``, and for a row-sharded operator their ``_sharded`` forms: V, Q, r, dv then hold
+    this rank's rows, with the gathered basis Qfull kept beside them; H and c are replicated; the parameter gradients are summed over
+    the row group before they are returned."""
+
     @staticmethod
     def forward(ctx, op, k, second_pass, reortho_bwd, differentiable, V, *cparams):
-        tensors = [q for q in cparams if torch.is_tensor(q)]
+        tensors = stash_params(ctx, cparams)
         _lib.require_device(V, *tensors)
         lib = _lib.get()
         V = V.contiguous()
-        p, n = V.shape
+        p, nrows = V.shape
+        sharded = isinstance(op, RowShardedOp)
+        n = op.comm.n if sharded else nrows
         dt, dev = V.dtype, V.device
-        Q = torch.empty((p, k, n), dtype=dt, device=dev)
+        Q = torch.empty((p, k, nrows), dtype=dt, device=dev)
         H = torch.empty((p, k, k), dtype=dt, device=dev)
-        r = torch.empty((p, n), dtype=dt, device=dev)
+        r = torch.empty((p, nrows), dtype=dt, device=dev)
         c = torch.empty((p,), dtype=dt, device=dev)
-        keep = None
-        if isinstance(op, CallbackOp):
-            reg = _PtrRegistry()
-            desc, keep, _ = op.make(cparams, dt, n, reg, want_grads=False)
+        call = DriverCall(op, cparams, dt, n)
+        if sharded:
+            Qfull = torch.empty((p, k, n), dtype=dt, device=dev)
+            ws = call.take(lib.mfx_sharded_workspace_bytes, n, k, p, device=dev, visible=(Q, Qfull))
+            entry, gathered = lib.mfx_arnoldi_forward_sharded, (Qfull,)
         else:
-            desc = op.descriptor(cparams, dt, n)
-        ws = _lib.workspace(desc, n, k, p, dev)
-        if keep is not None:
-            for t in (V, Q, r):
-                reg.add(t)
-            reg.add_bytes(ws, dt)
-        with _lib.busy(ws):
-            rc = lib.mfx_arnoldi_forward(C.byref(desc), _lib.ptr(V), n, k, p, int(second_pass), _lib.ptr(Q),
-                                         _lib.ptr(H), _lib.ptr(r), _lib.ptr(c), _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(dev))
-        if keep is not None and keep[1]:
-            raise keep[1][0]
-        _lib.check(rc)
+            ws = call.take(lib.mfx_workspace_bytes, n, k, p, device=dev, visible=(V, Q, r))
+            entry, gathered = lib.mfx_arnoldi_forward, ()
+        call.run(entry, _lib.ptr(V), n, k, p, int(second_pass), _lib.ptr(Q), *map(_lib.ptr, gathered), _lib.ptr(H), _lib.ptr(r),
+                 _lib.ptr(c), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         ctx.op, ctx.k, ctx.reortho, ctx.differentiable = op, k, reortho_bwd, differentiable
-        ctx.nparams = len(cparams)
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
-        ctx.save_for_backward(Q, H, r, c, *tensors)
+        ctx.save_for_backward(Q, H, r, c, *gathered, *tensors)
         ctx.set_materialize_grads(False)
         return Q, H, r, c
 
@@ -182,10 +162,12 @@ class _ArnoldiFn(torch.autograd.Function):
             raise RuntimeError("hessenberg(custom_vjp=False) is not differentiable in the MI355X build; "
                                "use custom_vjp=True (the adjoint system).")
         Q, H, r, c, *tensors = ctx.saved_tensors
-        it = iter(tensors)
-        cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)
         op, k, lib = ctx.op, ctx.k, _lib.get()
-        p, _, n = Q.shape
+        sharded = isinstance(op, RowShardedOp)
+        gathered = (tensors.pop(0),) if sharded else ()  # Qfull
+        cparams = rebuild_params(ctx, tensors)
+        p, _, nrows = Q.shape
+        n = op.comm.n if sharded else nrows
         dt, dev = Q.dtype, Q.device
         dQ = None if dQ is None else dQ.contiguous()
         dr = None if dr is None else dr.contiguous()
@@ -193,109 +175,17 @@ class _ArnoldiFn(torch.autograd.Function):
         dH = torch.zeros_like(H) if dH is None else dH.contiguous()
         # probes are constants in SLQ / GP training: without a cotangent to return, the driver skips the last operator application
         # and the vector kernels behind it, which produce nothing else (dv == NULL, include/mfx.h)
-        dv = torch.empty((p, n), dtype=dt, device=dev) if ctx.needs_input_grad[5] else None
-        Lam = torch.empty((p, k, n), dtype=dt, device=dev)
-        keep = None
-        if isinstance(op, CallbackOp):
-            reg = _PtrRegistry()
-            desc, keep, grads = op.make(cparams, dt, n, reg, want_grads=True)
-            gptr = None
-        else:
-            desc = op.descriptor(cparams, dt, n)
-            gstruct, grads = op.new_grads(*cparams)
-            gptr = C.byref(gstruct)
-        ws = _lib.workspace(desc, n, k, p, dev)
-        if keep is not None:
-            for t in (Q, r, Lam, dv, dQ, dr):
-                reg.add(t)
-            reg.add_bytes(ws, dt)
-        with _lib.busy(ws):
-            rc = lib.mfx_arnoldi_adjoint(C.byref(desc), n, k, p, _lib.ptr(Q), _lib.ptr(H), _lib.ptr(r), _lib.ptr(c),
-                                         _lib.ptr(dQ), _lib.ptr(dH), _lib.ptr(dr), _lib.ptr(dc),
-                                         _lib.REORTHO_FULL if ctx.reortho == "full" else _lib.REORTHO_NONE,
-                                         _lib.ptr(dv), _lib.ptr(Lam), gptr, _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(dev))
-        if keep is not None and keep[1]:
-            raise keep[1][0]
-        _lib.check(rc)
-        return (None, None, None, None, None, dv, *grads)
-
-
-class _ArnoldiShardedFn(torch.autograd.Function):
-    """_ArnoldiFn on row shards (``mfx_arnoldi_forward_sharded`` / ``mfx_arnoldi_adjoint_sharded``): V, Q, r, dv hold this
-    rank's rows; H and c are replicated; the parameter gradients are summed over the row group before they are returned."""
-
-    @staticmethod
-    def forward(ctx, sop, k, second_pass, reortho_bwd, differentiable, V, *cparams):
-        op, comm = sop.op, sop.comm
-        tensors = [q for q in cparams if torch.is_tensor(q)]
-        _lib.require_device(V, *tensors)
-        lib = _lib.get()
-        V = V.contiguous()
-        p, nrows = V.shape
-        n = comm.n
-        dt, dev = V.dtype, V.device
-        Q = torch.empty((p, k, nrows), dtype=dt, device=dev)
-        Qfull = torch.empty((p, k, n), dtype=dt, device=dev)
-        H = torch.empty((p, k, k), dtype=dt, device=dev)
-        r = torch.empty((p, nrows), dtype=dt, device=dev)
-        c = torch.empty((p,), dtype=dt, device=dev)
-        desc = op.descriptor(cparams, dt, n)
-        cm0 = _lib.Comm()
-        cm0.rank, cm0.world, cm0.nloc = comm.rank, comm.world, comm.nloc
-        ws = _lib.scratch(int(lib.mfx_sharded_workspace_bytes(C.byref(desc), C.byref(cm0), n, k, p)), dev)
-        cm, keep = comm.struct(ws, tensors=(Q, Qfull), plans=sop.plans)
-        with _lib.busy(ws):
-            rc = lib.mfx_arnoldi_forward_sharded(C.byref(desc), C.byref(cm), _lib.ptr(V), n, k, p, int(second_pass),
-                                                 _lib.ptr(Q), _lib.ptr(Qfull), _lib.ptr(H), _lib.ptr(r), _lib.ptr(c),
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        if keep[2]:
-            raise keep[2][0]
-        _lib.check(rc)
-        ctx.sop, ctx.k, ctx.reortho, ctx.differentiable = sop, k, reortho_bwd, differentiable
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
-        ctx.save_for_backward(Q, Qfull, H, r, c, *tensors)
-        ctx.set_materialize_grads(False)
-        return Q, H, r, c
-
-    @staticmethod
-    def backward(ctx, dQ, dH, dr, dc):
-        if not ctx.differentiable:
-            raise RuntimeError("hessenberg(custom_vjp=False) is not differentiable in the MI355X build; "
-                               "use custom_vjp=True (the adjoint system).")
-        Q, Qfull, H, r, c, *tensors = ctx.saved_tensors
-        it = iter(tensors)
-        cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)
-        op, comm, k, lib = ctx.sop.op, ctx.sop.comm, ctx.k, _lib.get()
-        p, _, nrows = Q.shape
-        n = comm.n
-        dt, dev = Q.dtype, Q.device
-        dQ = None if dQ is None else dQ.contiguous()
-        dr = None if dr is None else dr.contiguous()
-        dc = None if dc is None else dc.contiguous()
-        dH = torch.zeros_like(H) if dH is None else dH.contiguous()
-        dv = torch.empty((p, nrows), dtype=dt, device=dev) if ctx.needs_input_grad[5] else None  # see _ArnoldiFn.backward
+        dv = torch.empty((p, nrows), dtype=dt, device=dev) if ctx.needs_input_grad[5] else None
         Lam = torch.empty((p, k, nrows), dtype=dt, device=dev)
-        desc = op.descriptor(cparams, dt, n)
-        gstruct, grads = op.new_grads(*cparams)
-        cm0 = _lib.Comm()
-        cm0.rank, cm0.world, cm0.nloc = comm.rank, comm.world, comm.nloc
-        ws = _lib.scratch(int(lib.mfx_sharded_workspace_bytes(C.byref(desc), C.byref(cm0), n, k, p)), dev)
-        cm, keep = comm.struct(ws, tensors=(Lam,), plans=ctx.sop.plans)
-        with _lib.busy(ws):
-            rc = lib.mfx_arnoldi_adjoint_sharded(C.byref(desc), C.byref(cm), n, k, p, _lib.ptr(Q), _lib.ptr(Qfull), _lib.ptr(H),
-                                                 _lib.ptr(r), _lib.ptr(c), _lib.ptr(dQ), _lib.ptr(dH), _lib.ptr(dr), _lib.ptr(dc),
-                                                 _lib.REORTHO_FULL if ctx.reortho == "full" else _lib.REORTHO_NONE,
-                                                 _lib.ptr(dv), _lib.ptr(Lam), C.byref(gstruct), _lib.ptr(ws), ws.numel(),
-                                                 _lib.stream_ptr(dev))
-        if keep[2]:
-            raise keep[2][0]
-        _lib.check(rc)
-        if comm.world > 1 and grads:  # partial sums over this rank's rows -> the complete gradient, ONE small all-reduce
-            flat = torch.cat([g.reshape(-1) for g in grads])
-            comm.all_reduce_(flat)
-            off = 0
-            for g in grads:
-                g.copy_(flat[off : off + g.numel()].reshape(g.shape))
-                off += g.numel()
-        return (None, None, None, None, None, dv, *grads)
+        call = DriverCall(op, cparams, dt, n, want_grads=True)
+        if sharded:
+            ws = call.take(lib.mfx_sharded_workspace_bytes, n, k, p, device=dev, visible=(Lam,))
+        else:
+            ws = call.take(lib.mfx_workspace_bytes, n, k, p, device=dev, visible=(Q, r, Lam, dv, dQ, dr))
+        call.run(lib.mfx_arnoldi_adjoint_sharded if sharded else lib.mfx_arnoldi_adjoint, n, k, p, _lib.ptr(Q),
+                 *map(_lib.ptr, gathered), _lib.ptr(H), _lib.ptr(r), _lib.ptr(c), _lib.ptr(dQ), _lib.ptr(dH), _lib.ptr(dr), _lib.ptr(dc),
+                 _lib.REORTHO_FULL if ctx.reortho == "full" else _lib.REORTHO_NONE, _lib.ptr(dv), _lib.ptr(Lam), call.gptr,
+                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        if sharded:
+            reduce_grads_(op.comm, call.grads)
+        return (None, None, None, None, None, dv, *call.grads)

@@ -35,7 +35,7 @@ import torch
 
 from . import _lib
 from .low_rank import BoundPreconditioner
-from .operators import CallbackOp, RowShardedOp, _PtrRegistry, as_operator
+from .operators import CallbackOp, DriverCall, RowShardedOp, as_operator, rebuild_params, reduce_grads_, stash_params
 
 
 def cg_fixed_step(*args, **kwargs):
@@ -155,131 +155,74 @@ def _solve(A, b, P, cfg):
     return out
 
 
-def _run_sharded(sop, cfg, P, B, cparams):
-    """One mfx_pcg_solve_sharded call: B, x, r are this rank's rows; steps replicated."""
-    lib = _lib.get()
-    op, comm = sop.op, sop.comm
-    B = B.contiguous()
-    p, nrows = B.shape
-    n = comm.n
-    if nrows != comm.nrows:
-        raise ValueError(f"row-sharded operator: expected this rank's {comm.nrows} rows of the right-hand side, got {nrows}")
-    dt, dev = B.dtype, B.device
-    desc = op.descriptor(cparams, dt, n)
-    rank, lt, minv, shift = 0, None, None, None
-    if P is not None:
-        pre = P.pre
-        if pre.n != n or pre.lt.dtype != dt:
-            raise ValueError(f"preconditioner of size {pre.n} ({pre.lt.dtype}) used for a system of size {n} ({dt})")
-        rank = pre.rank
-        lt = pre.lt[:, comm.row0 : comm.row0 + comm.nrows].contiguous()  # this rank's columns of L^T
-        minv, shift = pre.minv(P.s)  # from the whole L: replicated
-    cm0 = _lib.Comm()
-    cm0.rank, cm0.world, cm0.nloc = comm.rank, comm.world, comm.nloc
-    ws = _lib.scratch(int(lib.mfx_pcg_sharded_workspace_bytes(C.byref(desc), C.byref(cm0), n, p, rank)), dev)
-    x = torch.empty_like(B)
-    r = torch.empty_like(B)
-    steps = torch.empty((p,), dtype=torch.int64, device=dev)
-    cm, keep = comm.struct(ws, tensors=(), plans=sop.plans)
-    with _lib.busy(ws):
-        rc = lib.mfx_pcg_solve_sharded(C.byref(desc), C.byref(cm), _lib.ptr(B), nrows, n, p, _lib.ptr(lt), rank, _lib.ptr(minv),
-                                       _lib.ptr(shift), cfg["maxiter"], cfg["miniter"], cfg["atol"], cfg["rtol"],
-                                       int(cfg["adaptive"]), _lib.ptr(x), _lib.ptr(r), _lib.ptr(steps), _lib.ptr(ws), ws.numel(),
-                                       _lib.stream_ptr(dev))
-    if keep[2]:
-        raise keep[2][0]
-    _lib.check(rc)
-    return x, r, steps
+def _precond(P, n, dtype, cols=None):
+    """-> (rank, lt, minv, shift) of the bound preconditioner ``P`` (None: none) for a system of size n; ``cols``: the columns of
+    L^T of a row shard."""
+    if P is None:
+        return 0, None, None, None
+    pre = P.pre
+    if pre.n != n or pre.lt.dtype != dtype:
+        raise ValueError(f"preconditioner of size {pre.n} ({pre.lt.dtype}) used for a system of size {n} ({dtype})")
+    lt = pre.lt if cols is None else pre.lt[:, cols].contiguous()  # this rank's columns of L^T
+    minv, shift = pre.minv(P.s)  # from the whole L: replicated
+    return pre.rank, lt, minv, shift
 
 
 def _run(op, cfg, P, B, cparams):
-    """One mfx_pcg_solve call on detached tensors -> (x, r, steps)."""
-    if isinstance(op, RowShardedOp):
-        return _run_sharded(op, cfg, P, B, cparams)
+    """One mfx_pcg_solve (row-sharded operator: mfx_pcg_solve_sharded, with B, x, r this rank's rows and steps replicated),
+    mfx_pcg_solve_reortho or mfx_mbcg_solve call on detached tensors -> (x, r, steps), (x, r, Q) or
+    (x, r, steps, tdiag, toff, rz0, depth, w0); the padded tridiagonals are (p, maxiter) each."""
     lib = _lib.get()
+    sharded = isinstance(op, RowShardedOp)
     B = B.contiguous()
-    p, n = B.shape
+    p, nrows = B.shape
+    n = op.comm.n if sharded else nrows
+    if sharded and nrows != op.comm.nrows:
+        raise ValueError(f"row-sharded operator: expected this rank's {op.comm.nrows} rows of the right-hand side, got {nrows}")
     dt, dev = B.dtype, B.device
-    keep = None
-    if isinstance(op, CallbackOp):
-        reg = _PtrRegistry()
-        desc, keep, _ = op.make(cparams, dt, n, reg, want_grads=False)
+    call = DriverCall(op, cparams, dt, n)
+    rank, lt, minv, shift = _precond(P, n, dt, slice(op.comm.row0, op.comm.row0 + op.comm.nrows) if sharded else None)
+    m, reortho, mbcg = cfg["maxiter"], cfg.get("reortho", False), cfg.get("mbcg", False)
+    if mbcg:
+        ws = call.take(lib.mfx_mbcg_workspace_bytes, n, p, rank, m, device=dev)
+    elif sharded:
+        ws = call.take(lib.mfx_pcg_sharded_workspace_bytes, n, p, rank, device=dev)
     else:
-        desc = op.descriptor(cparams, dt, n)
-    rank, lt, minv, shift = 0, None, None, None
-    if P is not None:
-        pre = P.pre
-        if pre.n != n or pre.lt.dtype != dt:
-            raise ValueError(f"preconditioner of size {pre.n} ({pre.lt.dtype}) used for a system of size {n} ({dt})")
-        rank, lt = pre.rank, pre.lt
-        minv, shift = pre.minv(P.s)
-    reortho = cfg.get("reortho", False)
-    ws = _lib.workspace_pcg(desc, n, p, max(rank, cfg["maxiter"]) if reortho else rank, dev)
+        ws = call.take(lib.mfx_pcg_workspace_bytes, n, p, max(rank, m) if reortho else rank, device=dev)
     x = torch.empty_like(B)
     r = torch.empty_like(B)
-    if keep is not None:
-        reg.add_bytes(ws, dt)
+    system = (_lib.ptr(B), nrows, n, p, _lib.ptr(lt), rank, _lib.ptr(minv), _lib.ptr(shift))
+    stop = (m, cfg["miniter"], cfg["atol"], cfg["rtol"], int(cfg["adaptive"]))
+    tail = (_lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     if reortho:
-        m = cfg["maxiter"]
         if m < 1:
             raise ValueError("pcg_fixed_step_reortho needs num_matvecs >= 1")
         Q = torch.zeros((p, m, n), dtype=dt, device=dev)
-        with _lib.busy(ws):
-            rc = lib.mfx_pcg_solve_reortho(C.byref(desc), _lib.ptr(B), n, n, p, _lib.ptr(lt), rank, _lib.ptr(minv),
-                                           _lib.ptr(shift), m, _lib.ptr(x), _lib.ptr(r), _lib.ptr(Q), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_ptr(dev))
-        if keep is not None and keep[1]:
-            raise keep[1][0]
-        _lib.check(rc)
+        call.run(lib.mfx_pcg_solve_reortho, *system, m, _lib.ptr(x), _lib.ptr(r), _lib.ptr(Q), *tail)
         return x, r, Q
-    if cfg.get("mbcg", False):
-        return _run_mbcg(lib, desc, cfg, B, (rank, lt, minv, shift), x, r, keep, reg if keep is not None else None)
     steps = torch.empty((p,), dtype=torch.int64, device=dev)
-    with _lib.busy(ws):
-        rc = lib.mfx_pcg_solve(C.byref(desc), _lib.ptr(B), n, n, p, _lib.ptr(lt), rank, _lib.ptr(minv), _lib.ptr(shift),
-                               cfg["maxiter"], cfg["miniter"], cfg["atol"], cfg["rtol"], int(cfg["adaptive"]),
-                               _lib.ptr(x), _lib.ptr(r), _lib.ptr(steps), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    if keep is not None and keep[1]:
-        raise keep[1][0]
-    _lib.check(rc)
+    if mbcg:
+        depth = torch.empty((p,), dtype=torch.int64, device=dev)
+        tdiag = torch.empty((p, m), dtype=dt, device=dev)
+        toff = torch.empty((p, m), dtype=dt, device=dev)
+        rz0 = torch.empty((p,), dtype=dt, device=dev)
+        w0 = torch.empty_like(B)
+        call.run(lib.mfx_mbcg_solve, *system, *stop, _lib.ptr(x), _lib.ptr(r), _lib.ptr(steps), _lib.ptr(w0), _lib.ptr(tdiag),
+                 _lib.ptr(toff), _lib.ptr(rz0), _lib.ptr(depth), *tail)
+        return x, r, steps, tdiag, toff, rz0, depth, w0
+    call.run(lib.mfx_pcg_solve_sharded if sharded else lib.mfx_pcg_solve, *system, *stop, _lib.ptr(x), _lib.ptr(r), _lib.ptr(steps),
+             *tail)
     return x, r, steps
-
-
-def _run_mbcg(lib, desc, cfg, B, precond, x, r, keep, reg):
-    """One mfx_mbcg_solve call -> (x, r, steps, tdiag, toff, rz0, depth, w0); the padded tridiagonals are (p, maxiter) each."""
-    p, n = B.shape
-    dt, dev = B.dtype, B.device
-    rank, lt, minv, shift = precond
-    m = cfg["maxiter"]
-    ws = _lib.scratch(int(lib.mfx_mbcg_workspace_bytes(C.byref(desc), n, p, rank, m)), dev)
-    if reg is not None:
-        reg.add_bytes(ws, dt)
-    steps = torch.empty((p,), dtype=torch.int64, device=dev)
-    depth = torch.empty((p,), dtype=torch.int64, device=dev)
-    tdiag = torch.empty((p, m), dtype=dt, device=dev)
-    toff = torch.empty((p, m), dtype=dt, device=dev)
-    rz0 = torch.empty((p,), dtype=dt, device=dev)
-    w0 = torch.empty_like(B)
-    with _lib.busy(ws):
-        rc = lib.mfx_mbcg_solve(C.byref(desc), _lib.ptr(B), n, n, p, _lib.ptr(lt), rank, _lib.ptr(minv), _lib.ptr(shift), m,
-                                cfg["miniter"], cfg["atol"], cfg["rtol"], int(cfg["adaptive"]), _lib.ptr(x), _lib.ptr(r),
-                                _lib.ptr(steps), _lib.ptr(w0), _lib.ptr(tdiag), _lib.ptr(toff), _lib.ptr(rz0), _lib.ptr(depth),
-                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    if keep is not None and keep[1]:
-        raise keep[1][0]
-    _lib.check(rc)
-    return x, r, steps, tdiag, toff, rz0, depth, w0
 
 
 class _PcgFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, op, cfg, P, B, *cparams):
-        tensors = [q for q in cparams if torch.is_tensor(q)]
+        tensors = stash_params(ctx, cparams)
         _lib.require_device(B, *tensors)
         x, *rest = _run(op, cfg, P, B, cparams)
         ctx.op, ctx.P = op, P
         ctx.cfg = {k: v for k, v in cfg.items() if k != "mbcg"}  # the transpose solve needs no coefficients
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
         ctx.save_for_backward(x, *tensors)
         ctx.mark_non_differentiable(*rest)
         return (x, *rest)
@@ -287,29 +230,11 @@ class _PcgFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx, *_unused):
         x, *tensors = ctx.saved_tensors
-        it = iter(tensors)
-        cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)
+        cparams = rebuild_params(ctx, tensors)
         op = ctx.op
         lam, _r, _s = _run(op, ctx.cfg, ctx.P, dx, cparams)  # symmetric=True: the transpose solve is the same solve
-        p, n = x.shape
-        if isinstance(op, RowShardedOp):  # this rank's rows of -lambda against ALL entries of x; partial sums -> one all-reduce
-            nat, comm = op.op, op.comm
-            desc = nat.descriptor(cparams, x.dtype, comm.n)
-            desc.row0, desc.nrows = comm.row0, comm.nrows
-            gstruct, grads = nat.new_grads(*cparams)
-            ws = _lib.workspace(desc, comm.n, 1, p, x.device)
-            L = (-lam).contiguous()
-            xfull = comm.gather_rows(x)
-            _lib.check(_lib.get().mfx_op_vjp_params(C.byref(desc), _lib.ptr(L), comm.nrows, _lib.ptr(xfull), comm.n, p,
-                                                    C.byref(gstruct), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
-            if comm.world > 1 and grads:
-                flat = torch.cat([g.reshape(-1) for g in grads])
-                comm.all_reduce_(flat)
-                off = 0
-                for g in grads:
-                    g.copy_(flat[off : off + g.numel()].reshape(g.shape))
-                    off += g.numel()
-        elif isinstance(op, CallbackOp):
+        p, nrows = x.shape
+        if isinstance(op, CallbackOp):
             grads = []
             diff_idx = [i for i, q in enumerate(cparams) if torch.is_tensor(q) and q.is_floating_point()]
             acc = {i: torch.zeros_like(cparams[i]) for i in diff_idx}
@@ -325,10 +250,17 @@ class _PcgFn(torch.autograd.Function):
                                 acc[i].add_(g)
             grads = [acc.get(i) for i in range(len(cparams))]
         else:
-            desc = op.descriptor(cparams, x.dtype, n)
-            gstruct, grads = op.new_grads(*cparams)
+            sharded = isinstance(op, RowShardedOp)
+            nat, n = (op.op, op.comm.n) if sharded else (op, nrows)
+            desc = nat.descriptor(cparams, x.dtype, n)
+            if sharded:  # this rank's rows of -lambda against ALL entries of x; partial sums -> one all-reduce
+                desc.row0, desc.nrows = op.comm.row0, op.comm.nrows
+            gstruct, grads = nat.new_grads(*cparams)
             ws = _lib.workspace(desc, n, 1, p, x.device)
             L = (-lam).contiguous()
-            _lib.check(_lib.get().mfx_op_vjp_params(C.byref(desc), _lib.ptr(L), n, _lib.ptr(x), n, p, C.byref(gstruct),
+            R = op.comm.gather_rows(x) if sharded else x
+            _lib.check(_lib.get().mfx_op_vjp_params(C.byref(desc), _lib.ptr(L), nrows, _lib.ptr(R), n, p, C.byref(gstruct),
                                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+            if sharded:
+                reduce_grads_(op.comm, grads)
         return (None, None, None, lam, *grads)

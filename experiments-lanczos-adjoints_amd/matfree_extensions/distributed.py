@@ -225,6 +225,13 @@ class RowComm:
             full[:, lo:hi] = buf.to(full.device, non_blocking=False)
 
     # ---- mfx_comm ---------------------------------------------------------------------------------
+    def size_query(self):
+        """-> the ``mfx_comm`` of the workspace size queries (``mfx_*sharded_workspace_bytes``): they read the layout only, so it
+        needs neither callbacks nor a workspace.  (NativeRowComm inherits it: the sizes do not depend on who runs the collectives.)"""
+        cm = _lib.Comm()
+        cm.rank, cm.world, cm.nloc = self.rank, self.world, self.nloc
+        return cm
+
     def struct(self, ws: torch.Tensor, tensors=(), plans=None):
         """-> (mfx_comm, keepalive).  ``ws`` is the uint8 workspace tensor the collective callbacks' pointers lie in;
         ``tensors``: further tensors the exchange callback's pointers may lie in (basis, gathered basis, adjoint states);
@@ -294,8 +301,7 @@ class RowComm:
 
         cb_r, cb_g = _lib.ALLREDUCE_T(allreduce), _lib.ALLGATHER_T(allgather)
         cb_x = _lib.EXCHANGE_T(exchange) if plans is not None else _lib.EXCHANGE_T()
-        cm = _lib.Comm()
-        cm.rank, cm.world, cm.nloc = self.rank, self.world, self.nloc
+        cm = self.size_query()
         cm.allreduce_sum, cm.allgather, cm.exchange = cb_r, cb_g, cb_x
         return cm, (cb_r, cb_g, failure, cb_x)
 

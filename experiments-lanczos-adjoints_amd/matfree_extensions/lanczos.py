@@ -21,13 +21,13 @@ eigen-problem and its VJP (lanczos.py:48-59) run on the device too (``mfx_tridia
 
 from __future__ import annotations
 
-import ctypes as C
 import warnings
 
 import torch
 
 from . import _lib, arnoldi
-from .operators import CallbackOp, RowShardedOp, _PtrRegistry, as_operator, differentiable_inputs, with_inputs
+from .operators import (CallbackOp, DriverCall, RowShardedOp, as_operator, differentiable_inputs, rebuild_params, reduce_grads_,
+                        stash_params, with_inputs)
 
 
 def _vec_norm(V, matvec):
@@ -84,14 +84,11 @@ def _tridiag_reortho_none(matvec, krylov_depth, /, *, custom_vjp):
         if k < 1 or k > n:
             raise ValueError(f"Parameter depth {k} is outside the expected range")
         wants_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (V, *params, *differentiable_inputs(op)))
-        if sharded:  # vectors are row shards, alpha / beta replicated (mfx_lanczos_*_sharded)
-            cparams = op.constrain(*params)
-            xs, alpha, beta = _LanczosShardedFn.apply(op, k, custom_vjp, V, *cparams)
-        elif not custom_vjp and wants_grad:  # autodiff through the loop (the reference's baseline), see _autodiff.py
+        if not sharded and not custom_vjp and wants_grad:  # autodiff through the loop (the reference's baseline), see _autodiff.py
             from . import _autodiff
 
             xs, alpha, beta = _autodiff.batched(_autodiff.lanczos_forward, V, op, k, params)
-        else:
+        else:  # (a row-sharded operator: vectors are row shards, alpha / beta replicated)
             cparams = op.constrain(*params)
             xs, alpha, beta = _LanczosFn.apply(op, k, custom_vjp, V, *cparams)
         out = (xs[:, :-1], (alpha, beta[:, :-1])), (xs[:, -1], beta[:, -1])
@@ -103,115 +100,31 @@ def _tridiag_reortho_none(matvec, krylov_depth, /, *, custom_vjp):
 
 
 class _LanczosFn(torch.autograd.Function):
+    """``mfx_lanczos_forward`` / ``mfx_lanczos_adjoint``, and for a row-sharded operator their ``_sharded`` forms: V, xs, dv then hold
+    this rank's rows; alpha, beta are replicated; the parameter gradients are summed over the row group before they are returned."""
+
     @staticmethod
     def forward(ctx, op, k, differentiable, V, *cparams):
-        tensors = [q for q in cparams if torch.is_tensor(q)]
-        _lib.require_device(V, *tensors)
-        lib = _lib.get()
-        V = V.contiguous()
-        p, n = V.shape
-        dt, dev = V.dtype, V.device
-        xs = torch.empty((p, k + 1, n), dtype=dt, device=dev)
-        alpha = torch.empty((p, k), dtype=dt, device=dev)
-        beta = torch.empty((p, k), dtype=dt, device=dev)
-        vnorm = torch.empty((p,), dtype=dt, device=dev)
-        keep = None
-        if isinstance(op, CallbackOp):
-            reg = _PtrRegistry()
-            desc, keep, _ = op.make(cparams, dt, n, reg, want_grads=False)
-        else:
-            desc = op.descriptor(cparams, dt, n)
-        ws = _lib.workspace(desc, n, k, p, dev)
-        if keep is not None:
-            for t in (V, xs):
-                reg.add(t)
-            reg.add_bytes(ws, dt)
-        with _lib.busy(ws):
-            rc = lib.mfx_lanczos_forward(C.byref(desc), _lib.ptr(V), n, k, p, _lib.ptr(xs), _lib.ptr(alpha),
-                                         _lib.ptr(beta), _lib.ptr(vnorm), _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(dev))
-        if keep is not None and keep[1]:
-            raise keep[1][0]
-        _lib.check(rc)
-        ctx.op, ctx.k, ctx.differentiable = op, k, differentiable
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
-        ctx.save_for_backward(xs, alpha, beta, vnorm, *tensors)
-        ctx.set_materialize_grads(False)
-        return xs, alpha, beta
-
-    @staticmethod
-    def backward(ctx, dxs, dalpha, dbeta):
-        if not ctx.differentiable:
-            raise RuntimeError("tridiag(custom_vjp=False) is not differentiable in the MI355X build; "
-                               "use custom_vjp=True (the adjoint system).")
-        xs, alpha, beta, vnorm, *tensors = ctx.saved_tensors
-        it = iter(tensors)
-        cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)
-        op, k, lib = ctx.op, ctx.k, _lib.get()
-        p, _, n = xs.shape
-        dt, dev = xs.dtype, xs.device
-        dxs = None if dxs is None else dxs.contiguous()
-        dalpha = torch.zeros_like(alpha) if dalpha is None else dalpha.contiguous()
-        dbeta = torch.zeros_like(beta) if dbeta is None else dbeta.contiguous()
-        # no cotangent wanted for the start vector: the driver skips what only produces it (dv == NULL, include/mfx.h)
-        dv = torch.empty((p, n), dtype=dt, device=dev) if ctx.needs_input_grad[3] else None
-        Lam = torch.empty((p, k, n), dtype=dt, device=dev)
-        keep = None
-        if isinstance(op, CallbackOp):
-            reg = _PtrRegistry()
-            desc, keep, grads = op.make(cparams, dt, n, reg, want_grads=True)
-            gptr = None
-        else:
-            desc = op.descriptor(cparams, dt, n)
-            gstruct, grads = op.new_grads(*cparams)
-            gptr = C.byref(gstruct)
-        ws = _lib.workspace(desc, n, k, p, dev)
-        if keep is not None:
-            for t in (xs, Lam, dv, dxs):
-                reg.add(t)
-            reg.add_bytes(ws, dt)
-        with _lib.busy(ws):
-            rc = lib.mfx_lanczos_adjoint(C.byref(desc), n, k, p, _lib.ptr(xs), _lib.ptr(alpha), _lib.ptr(beta),
-                                         _lib.ptr(vnorm), _lib.ptr(dxs), _lib.ptr(dalpha), _lib.ptr(dbeta),
-                                         _lib.ptr(dv), _lib.ptr(Lam), gptr, _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(dev))
-        if keep is not None and keep[1]:
-            raise keep[1][0]
-        _lib.check(rc)
-        return (None, None, None, dv, *grads)
-
-
-class _LanczosShardedFn(torch.autograd.Function):
-    """_LanczosFn on row shards (``mfx_lanczos_forward_sharded`` / ``mfx_lanczos_adjoint_sharded``): V, xs, dv hold this rank's
-    rows; alpha, beta are replicated; the parameter gradients are summed over the row group before they are returned."""
-
-    @staticmethod
-    def forward(ctx, sop, k, differentiable, V, *cparams):
-        op, comm = sop.op, sop.comm
-        tensors = [q for q in cparams if torch.is_tensor(q)]
+        tensors = stash_params(ctx, cparams)
         _lib.require_device(V, *tensors)
         lib = _lib.get()
         V = V.contiguous()
         p, nrows = V.shape
-        n = comm.n
+        sharded = isinstance(op, RowShardedOp)
+        n = op.comm.n if sharded else nrows
         dt, dev = V.dtype, V.device
         xs = torch.empty((p, k + 1, nrows), dtype=dt, device=dev)
         alpha = torch.empty((p, k), dtype=dt, device=dev)
         beta = torch.empty((p, k), dtype=dt, device=dev)
         vnorm = torch.empty((p,), dtype=dt, device=dev)
-        desc = op.descriptor(cparams, dt, n)
-        cm0 = _lib.Comm()
-        cm0.rank, cm0.world, cm0.nloc = comm.rank, comm.world, comm.nloc
-        ws = _lib.scratch(int(lib.mfx_sharded_workspace_bytes(C.byref(desc), C.byref(cm0), n, k, p)), dev)
-        cm, keep = comm.struct(ws, tensors=(xs,), plans=sop.plans)
-        with _lib.busy(ws):
-            rc = lib.mfx_lanczos_forward_sharded(C.byref(desc), C.byref(cm), _lib.ptr(V), n, k, p, _lib.ptr(xs), _lib.ptr(alpha),
-                                                 _lib.ptr(beta), _lib.ptr(vnorm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        if keep[2]:
-            raise keep[2][0]
-        _lib.check(rc)
-        ctx.sop, ctx.k, ctx.differentiable = sop, k, differentiable
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in cparams]
+        call = DriverCall(op, cparams, dt, n)
+        if sharded:
+            ws = call.take(lib.mfx_sharded_workspace_bytes, n, k, p, device=dev, visible=(xs,))
+        else:
+            ws = call.take(lib.mfx_workspace_bytes, n, k, p, device=dev, visible=(V, xs))
+        call.run(lib.mfx_lanczos_forward_sharded if sharded else lib.mfx_lanczos_forward, _lib.ptr(V), n, k, p, _lib.ptr(xs),
+                 _lib.ptr(alpha), _lib.ptr(beta), _lib.ptr(vnorm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        ctx.op, ctx.k, ctx.differentiable = op, k, differentiable
         ctx.save_for_backward(xs, alpha, beta, vnorm, *tensors)
         ctx.set_materialize_grads(False)
         return xs, alpha, beta
@@ -222,40 +135,31 @@ class _LanczosShardedFn(torch.autograd.Function):
             raise RuntimeError("tridiag(custom_vjp=False) is not differentiable in the MI355X build; "
                                "use custom_vjp=True (the adjoint system).")
         xs, alpha, beta, vnorm, *tensors = ctx.saved_tensors
-        it = iter(tensors)
-        cparams = tuple(next(it) if q is None else q for q in ctx.nontensor)
-        op, comm, k, lib = ctx.sop.op, ctx.sop.comm, ctx.k, _lib.get()
+        cparams = rebuild_params(ctx, tensors)
+        op, k, lib = ctx.op, ctx.k, _lib.get()
         p, _, nrows = xs.shape
-        n = comm.n
+        sharded = isinstance(op, RowShardedOp)
+        n = op.comm.n if sharded else nrows
         dt, dev = xs.dtype, xs.device
         dxs = None if dxs is None else dxs.contiguous()
         dalpha = torch.zeros_like(alpha) if dalpha is None else dalpha.contiguous()
         dbeta = torch.zeros_like(beta) if dbeta is None else dbeta.contiguous()
-        dv = torch.empty((p, nrows), dtype=dt, device=dev) if ctx.needs_input_grad[3] else None  # see _LanczosFn.backward
+        # no cotangent wanted for the start vector: the driver skips what only produces it (dv == NULL, include/mfx.h)
+        dv = torch.empty((p, nrows), dtype=dt, device=dev) if ctx.needs_input_grad[3] else None
         Lam = torch.empty((p, k, nrows), dtype=dt, device=dev)
-        Lamfull = torch.empty((p, k, n), dtype=dt, device=dev)
-        desc = op.descriptor(cparams, dt, n)
-        gstruct, grads = op.new_grads(*cparams)
-        cm0 = _lib.Comm()
-        cm0.rank, cm0.world, cm0.nloc = comm.rank, comm.world, comm.nloc
-        ws = _lib.scratch(int(lib.mfx_sharded_workspace_bytes(C.byref(desc), C.byref(cm0), n, k, p)), dev)
-        cm, keep = comm.struct(ws, tensors=(Lam, Lamfull), plans=ctx.sop.plans)
-        with _lib.busy(ws):
-            rc = lib.mfx_lanczos_adjoint_sharded(C.byref(desc), C.byref(cm), n, k, p, _lib.ptr(xs), _lib.ptr(alpha), _lib.ptr(beta),
-                                                 _lib.ptr(vnorm), _lib.ptr(dxs), _lib.ptr(dalpha), _lib.ptr(dbeta), _lib.ptr(dv),
-                                                 _lib.ptr(Lam), _lib.ptr(Lamfull), C.byref(gstruct), _lib.ptr(ws), ws.numel(),
-                                                 _lib.stream_ptr(dev))
-        if keep[2]:
-            raise keep[2][0]
-        _lib.check(rc)
-        if comm.world > 1 and grads:  # partial sums over this rank's rows -> the complete gradient, ONE small all-reduce
-            flat = torch.cat([g.reshape(-1) for g in grads])
-            comm.all_reduce_(flat)
-            off = 0
-            for g in grads:
-                g.copy_(flat[off : off + g.numel()].reshape(g.shape))
-                off += g.numel()
-        return (None, None, None, dv, *grads)
+        call = DriverCall(op, cparams, dt, n, want_grads=True)
+        if sharded:
+            Lamfull = torch.empty((p, k, n), dtype=dt, device=dev)
+            ws = call.take(lib.mfx_sharded_workspace_bytes, n, k, p, device=dev, visible=(Lam, Lamfull))
+            entry, gathered = lib.mfx_lanczos_adjoint_sharded, (_lib.ptr(Lamfull),)
+        else:
+            ws = call.take(lib.mfx_workspace_bytes, n, k, p, device=dev, visible=(xs, Lam, dv, dxs))
+            entry, gathered = lib.mfx_lanczos_adjoint, ()
+        call.run(entry, n, k, p, _lib.ptr(xs), _lib.ptr(alpha), _lib.ptr(beta), _lib.ptr(vnorm), _lib.ptr(dxs), _lib.ptr(dalpha),
+                 _lib.ptr(dbeta), _lib.ptr(dv), _lib.ptr(Lam), *gathered, call.gptr, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        if sharded:
+            reduce_grads_(op.comm, call.grads)
+        return (None, None, None, dv, *call.grads)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -264,20 +168,7 @@ class _LanczosShardedFn(torch.autograd.Function):
 class _QuadformFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, matfun, diag, off):
-        _lib.require_device(diag, off)
-        lib = _lib.get()
-        diag, off = diag.contiguous(), off.contiguous()
-        p, k = diag.shape
-        dt, dev = diag.dtype, diag.device
-        # beyond depth 120 the eigensolver accumulates its rotations in the fp64 output itself (include/mfx.h): fp32 problems are cast
-        et = torch.float64 if k > 120 else dt
-        diag_e, off_e = diag.to(et), off.to(et)
-        evals = torch.empty((p, k), dtype=et, device=dev)
-        evecs = torch.empty((p, k, k), dtype=et, device=dev)
-        _lib.check(lib.mfx_tridiag_eigh(_lib.ptr(diag_e), _lib.ptr(off_e) if k > 1 else None, max(k - 1, 1), p, k,
-                                        _lib.dtype_code(et), _lib.ptr(evals), _lib.ptr(evecs),
-                                        _lib.stream_ptr(dev)))
-        evals, evecs = evals.to(dt), evecs.to(dt)
+        evals, evecs = _tridiag_eigh(diag, off)
         with torch.enable_grad():
             lam = evals.detach().requires_grad_(True)
             fx = matfun(lam)  # vmap(matfun)(eigvals), lanczos.py:58
@@ -386,7 +277,8 @@ def _tridiag_eigh(diag, off):
     diag, off = diag.detach().contiguous(), off.detach().contiguous()
     p, k = diag.shape
     dt, dev = diag.dtype, diag.device
-    et = torch.float64 if k > 120 else dt  # as _QuadformFn: beyond depth 120 the eigensolver wants fp64 buffers
+    # beyond depth 120 the eigensolver accumulates its rotations in the fp64 output itself (include/mfx.h): fp32 problems are cast
+    et = torch.float64 if k > 120 else dt
     diag_e, off_e = diag.to(et), off.to(et)
     evals = torch.empty((p, k), dtype=et, device=dev)
     evecs = torch.empty((p, k, k), dtype=et, device=dev)
@@ -529,15 +421,13 @@ class _ReuseFn(torch.autograd.Function):
             w1 = scale[:, None] ** 2 * torch.einsum("pin,pi->pn", basis, sol)  # lanczos.py:117
         ctx.op = op
         ctx.nparams = nparams
-        ctx.save_for_backward(w1, U, *[q for q in parameters if torch.is_tensor(q)], *differentiable_inputs(op))
-        ctx.nontensor = [None if torch.is_tensor(q) else q for q in parameters] + [None] * len(differentiable_inputs(op))
+        ctx.save_for_backward(w1, U, *stash_params(ctx, (*parameters, *differentiable_inputs(op))))
         return scale**2 * value
 
     @staticmethod
     def backward(ctx, gout):
         w1, w2, *tensors = ctx.saved_tensors
-        it = iter(tensors)
-        params = tuple(next(it) if q is None else q for q in ctx.nontensor)
+        params = rebuild_params(ctx, tensors)
         warnings.warn("Todo: implement gradient wrt v correctly", stacklevel=1)  # lanczos.py:131-133
         with torch.enable_grad():
             live = [q.detach().requires_grad_(True) if torch.is_tensor(q) and q.is_floating_point() else q for q in params]

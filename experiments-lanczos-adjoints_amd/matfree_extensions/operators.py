@@ -954,6 +954,81 @@ class CallbackOp:
         return desc, (cb, failure), accum
 
 
+class DriverCall:
+    """One libmfx driver call on behalf of an autograd Function, for a native, callback or row-sharded operator:
+
+        call = DriverCall(op, cparams, dtype, n, want_grads)   # .desc; .gptr, .grads aligned with cparams; .comm (or None)
+        ws = call.take(lib.mfx_..._workspace_bytes, *dims, device=dev, visible=(tensors the call hands out pointers into))
+        call.run(lib.mfx_x_sharded if call.comm else lib.mfx_x, <the arguments after the descriptor and the comm>)
+
+    It holds the two rules that are easy to get wrong: every tensor a callback may be handed is registered, and a Python exception
+    captured inside the call wins over the return code."""
+
+    def __init__(self, op, cparams, dtype, n, want_grads=False):
+        self.dtype, self.reg, self.comm, self.plans, self.failure = dtype, None, None, None, ()
+        self.gptr, self.grads = None, ()
+        if isinstance(op, RowShardedOp):  # vectors are row shards; the descriptor is the whole operator's (n = comm.n)
+            op, self.comm, self.plans = op.op, op.comm, op.plans
+        if isinstance(op, CallbackOp):  # the trampoline accumulates the parameter gradients itself: no mfx_op_grads
+            self.reg = _PtrRegistry()
+            self.desc, (self._cb, self.failure), self.grads = op.make(cparams, dtype, n, self.reg, want_grads)
+        else:
+            self.desc = op.descriptor(cparams, dtype, n)
+            if want_grads:
+                self._gstruct, self.grads = op.new_grads(*cparams)
+                self.gptr = C.byref(self._gstruct)
+
+    def take(self, query, *dims, device, visible=()):
+        """The workspace of the call, ``query(desc[, comm], *dims)`` bytes from ``_lib._take``, taken ONCE; ``visible``: the tensors a
+        callback operator or the exchange of a row-sharded one may receive pointers into, besides the workspace itself."""
+        lead = [C.byref(self.desc)] + ([C.byref(self.comm.size_query())] if self.comm is not None else [])
+        self.ws = ws = _lib.scratch(int(query(*lead, *dims)), device)
+        if self.reg is not None:
+            for t in visible:
+                self.reg.add(t)
+            self.reg.add_bytes(ws, self.dtype)
+        if self.comm is not None:
+            self._cm, self._keep = self.comm.struct(ws, tensors=visible, plans=self.plans)
+            lead[1], self.failure = C.byref(self._cm), self._keep[2]
+        self.lead = lead
+        return ws
+
+    def run(self, entry, *args):
+        """``entry(desc[, comm], *args)`` with the workspace marked busy for the call and nothing else; then the Python exception the
+        callback trampoline or a collective captured, as the original object, in preference to the status; then the status."""
+        with _lib.busy(self.ws):
+            rc = entry(*self.lead, *args)
+        if self.failure:
+            raise self.failure[0]
+        _lib.check(rc)
+
+
+def reduce_grads_(comm, grads):
+    """Row-sharded backward: partial sums over this rank's rows -> the complete gradients, in place, by ONE small all-reduce."""
+    if comm.world > 1 and grads:
+        flat = torch.cat([g.reshape(-1) for g in grads])
+        comm.all_reduce_(flat)
+        off = 0
+        for g in grads:
+            g.copy_(flat[off : off + g.numel()].reshape(g.shape))
+            off += g.numel()
+
+
+_TENSOR = object()  # the place of a tensor in ctx.nontensor (None is a parameter value like any other)
+
+
+def stash_params(ctx, cparams):
+    """Forward: the non-tensor parameters stay on ``ctx``; -> the tensors among them, for ``ctx.save_for_backward``."""
+    ctx.nontensor = [_TENSOR if torch.is_tensor(q) else q for q in cparams]
+    return [q for q in cparams if torch.is_tensor(q)]
+
+
+def rebuild_params(ctx, tensors):
+    """Backward: the parameter tuple of ``stash_params`` again, around the saved tensors."""
+    it = iter(tensors)
+    return tuple(next(it) if q is _TENSOR else q for q in ctx.nontensor)
+
+
 KernelGramOp = RbfGramOp  # the operator covers the reference's three stationary kernels
 
 

@@ -643,6 +643,107 @@ def test_error_paths_on_device():
         arnoldi.hessenberg(DenseOp(), 3, reortho="full")(v.to(torch.float16), A.to(torch.float16))
 
 
+def test_python_exception_wins_at_every_driver_site():
+    """The rule test_error_paths_on_device pins at the Arnoldi forward, at every site that hands a Python matvec to a libmfx driver:
+    the exception the matvec raised surfaces as itself (not as the status the callback returned), no workspace stays marked busy,
+    and the same call with a healthy matvec then succeeds.  n = 16, fp64, diagonal plus rank 2; the matvec raises on its SECOND
+    invocation, so every driver is past its first step (the backward cases: healthy forward, second invocation of the backward).
+    Healthy results against dense torch on the CPU (tests/_torch_forward.py and autograd through it; torch.linalg.solve for the
+    solvers after n steps; the Arnoldi relation for the complex forward) at this file's fp64 tolerances: 1e-9 forward, 1e-7
+    gradients, 1e-8 for an n-step CG solve against the direct one (as test_cg_fixed_step_matches_oracle)."""
+    import _torch_forward as tf
+    from matfree_extensions import cg
+
+    n, k = 16, 4
+    A = orc.spd_diag_plus_lowrank(n, 2, seed=0)
+    rng = np.random.default_rng(5)
+    v, b = rng.standard_normal(n), rng.standard_normal(n)
+    At, Ac, vc = T(A), torch.tensor(A), torch.tensor(v)
+    vz = torch.tensor(v + 1j * rng.standard_normal(n), device=DEV)
+
+    def matvec(fail_at):
+        state = {"armed": True, "calls": 0}
+
+        def mv(x, P=None):  # symmetric parametrisation: the three-term adjoint applies A, not A^T
+            state["calls"] += state["armed"]
+            if state["armed"] and state["calls"] == fail_at:
+                raise ZeroDivisionError("matvec failed on purpose")
+            return (At if P is None else 0.5 * (P + P.T)).to(x.dtype) @ x
+
+        return mv, state
+
+    def flat(tree):
+        return [tree] if torch.is_tensor(tree) else [t for s in tree for t in flat(s)]
+
+    def sym(x, P):
+        return 0.5 * (P + P.T) @ x
+
+    want_l = flat(tf.tridiag_none(sym, k, vc, Ac))
+    want_a = flat(tf.arnoldi_forward(sym, k, vc, Ac))
+    w_l = [torch.tensor(rng.standard_normal(tuple(t.shape))) for t in want_l]
+    w_a = [torch.tensor(rng.standard_normal(tuple(t.shape))) for t in want_a]
+
+    def grads(forward, weights, vt, Pt):
+        return list(torch.autograd.grad(sum((o * w.to(o.device)).sum() for o, w in zip(flat(forward(vt, Pt)), weights)), (vt, Pt)))
+
+    vg, Pg = vc.clone().requires_grad_(True), Ac.clone().requires_grad_(True)
+    want_lg = grads(lambda x, P: tf.tridiag_none(sym, k, x, P), w_l, vg, Pg)
+    want_ag = grads(lambda x, P: tf.arnoldi_forward(sym, k, x, P), w_a, vg, Pg)
+    want_x = [torch.linalg.solve(Ac, torch.tensor(b))]
+
+    def backward_of(alg, weights):
+        def run(mv, state):
+            state["armed"] = False
+            vt, Pt = T(v, grad=True), T(A, grad=True)
+            loss = sum((o * w.to(DEV)).sum() for o, w in zip(flat(alg(mv)(vt, Pt)), weights))
+            state["armed"] = True
+            return list(torch.autograd.grad(loss, (vt, Pt)))
+
+        return run
+
+    def complex_forward(mv, _state):
+        Q, H, r, c = arnoldi.hessenberg(mv, k, reortho="full")(vz)
+        assert close(torch.view_as_real(Q.mH @ Q), N(torch.view_as_real(torch.eye(k, dtype=vz.dtype, device=DEV))), 1e-9)
+        assert close(torch.view_as_real(Q[:, 0]), N(torch.view_as_real(c * vz)), 1e-9)
+        last = torch.zeros((n, k), dtype=vz.dtype, device=DEV)
+        last[:, -1] = r
+        return [torch.view_as_real(Q @ H + last)], [torch.view_as_real(At.to(vz.dtype) @ Q).cpu()]  # A Q = Q H + r e_k^T
+
+    def lanczos_none(mv):
+        return lanczos.tridiag(mv, k, reortho="none")
+
+    def hessenberg(mv):
+        return arnoldi.hessenberg(mv, k, reortho="full")
+
+    cases = [
+        ("lanczos forward", lambda mv, _s: flat(lanczos_none(mv)(T(v), At)), want_l, 1e-9),
+        ("lanczos backward", backward_of(lanczos_none, w_l), want_lg, 1e-7),
+        ("arnoldi forward", lambda mv, _s: flat(hessenberg(mv)(T(v), At)), want_a, 1e-9),
+        ("arnoldi backward", backward_of(hessenberg, w_a), want_ag, 1e-7),
+        ("complex arnoldi forward", complex_forward, None, 1e-9),
+        ("pcg_fixed_step", lambda mv, _s: [cg.pcg_fixed_step(n)(mv, T(b), None)[0]], want_x, 1e-8),
+        ("pcg_fixed_step_reortho", lambda mv, _s: [cg.pcg_fixed_step_reortho(n)(mv, T(b), None)[0]], want_x, 1e-8),
+        ("mbcg_fixed_step", lambda mv, _s: [cg.mbcg_fixed_step(n)(mv, T(b), None)[0]], want_x, 1e-8),
+    ]
+    for name, run, want, tol in cases:
+        mv, state = matvec(2)
+        with pytest.raises(ZeroDivisionError, match="failed on purpose"):
+            run(mv, state)
+        assert state["calls"] == 2, name  # it was this driver's second application that raised
+        assert not _lib._ws_busy, name
+        got = run(*matvec(None))
+        if want is None:
+            got, want = got
+        assert not _lib._ws_busy, name
+        assert len(got) == len(want), name
+        for g, w in zip(got, want):
+            print(name, tuple(w.shape), "max abs err", float((g.detach().cpu() - w.detach()).abs().max()), "scale", float(w.abs().max()))
+            if tol == 1e-8:
+                assert np.allclose(N(g), N(w), rtol=tol, atol=tol), name
+            else:
+                assert close(g, N(w), tol), name
+
+
 @pytest.mark.parametrize("dtype,vtol,gtol", [(torch.float64, 1e-10, 1e-7), (torch.float32, 2e-5, 2e-3)])
 @pytest.mark.parametrize("k", [121, 150, 255])
 def test_slq_beyond_depth_120(k, dtype, vtol, gtol):
