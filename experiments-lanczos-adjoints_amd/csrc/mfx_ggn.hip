@@ -19,6 +19,13 @@
 // No atomics and a fixed summation order: bit-identical from run to run; the arithmetic of a probe does not involve its group,
 // so its bits do not depend on how many probes share the call.  The shift gradient (mfx_op_grads.noise += sum_b L_b . R_b) is a
 // two-stage dot product with fp64 partial sums in the workspace.
+//
+// The two halves of that pass are also entry points of their own, the network Jacobian at the samples of a tape as a pair of linear
+// maps (mfx_mlp_jac_apply, mfx_mlp_jac_t_apply: what the linearised-Laplace predictive needs at the test points):
+//
+//   k_jac_tiles     out[b][i][:] = J_i v_b: the forward tangent of k_ggn_tiles, written per sample; no workspace, no sum
+//   k_jac_t_tiles   the backward accumulation started at g_L = U[b][i][:], per-workgroup partial sums as above
+//   k_jac_t_reduce  y = sum over workgroups, in index order
 #include "mfx_internal.h"
 
 namespace mfx {
@@ -220,6 +227,161 @@ __global__ __launch_bounds__(256) void k_ggn_reduce(const T* __restrict__ part, 
   y[b * ldy + i] = acc + alpha[0] * x[b * ldx + i];
 }
 
+// out[b][i][:] = J_i v_b for every probe b and sample i < N (out: (p, N, c) contiguous): the forward tangent of k_ggn_tiles with the
+// same geometry -- a tile of 32 samples and a group of probes per workgroup, every tape chunk staged once per group -- ending in a
+// store of t_L instead of the H product.  Samples past N in the last tile write nothing.
+template <typename T>
+__global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_tiles(GgnArgs<T> a, const T* __restrict__ x, int64_t ldx, int64_t p,
+                                                                       T* __restrict__ out) {
+  constexpr int G = GgnGroup<T>::value, TS = kGgnTS, W = kGgnW;
+  __shared__ __attribute__((aligned(16))) GgnLds<T> sm;
+  const int j = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.y * G + g;
+  const bool live = b < p;  // wave-uniform; a wave without a probe still stages and meets the barriers
+  const T* __restrict__ v = x + (live ? b : 0) * ldx;
+  const int L = a.L, c = a.w[L];
+  T s[TS];  // this unit's tangents for the samples of the tile
+
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const int64_t i0 = tile * TS;
+    const int nv = a.N - i0 < TS ? (int)(a.N - i0) : TS;
+    for (int l = 1; l <= L; ++l) {
+      const int wi = a.w[l - 1], wo = a.w[l];
+      const bool on = live && j < wo;
+      const T* __restrict__ vW = v + a.off[l] + wo;
+      const T* __restrict__ Wl = a.theta + a.off[l] + wo;
+      const T vb = on ? v[a.off[l] + j] : T(0);
+#pragma unroll
+      for (int i = 0; i < TS; ++i) s[i] = vb;
+      for (int k0 = 0; k0 < wi; k0 += W) {
+        __syncthreads();  // the chunk before this one has been consumed
+        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        __syncthreads();
+        if (on) {
+          const int kc = wi - k0 < W ? wi - k0 : W;
+          if (l == 1) {
+#pragma unroll 2
+            for (int kk = 0; kk < kc; ++kk) {
+              const T vw = vW[(int64_t)(k0 + kk) * wo + j];
+#pragma unroll
+              for (int i = 0; i < TS; ++i) s[i] += sm.aT[kk][i] * vw;
+            }
+          } else {  // wi <= 64: one chunk, kk is the unit of layer l - 1
+#pragma unroll 2
+            for (int kk = 0; kk < kc; ++kk) {
+              const T vw = vW[kk * wo + j], wt = Wl[kk * wo + j];
+#pragma unroll
+              for (int i = 0; i < TS; ++i) s[i] += sm.aT[kk][i] * vw + sm.tb[g][kk][i] * wt;
+            }
+          }
+        }
+      }
+      __syncthreads();  // every wave is done with t_{l-1} and with the last chunk
+      if (l < L) {      // the slopes of the tile, staged once for the whole group
+        ggn_stage<T>(sm, a.dact[l], wo, 0, i0, nv);
+        __syncthreads();
+        if (on) {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = sm.aT[j][i] * s[i];
+        }
+      } else if (on) {  // j < c: lane j writes logit j, consecutive lanes consecutive addresses
+        T* __restrict__ o = out + ((int64_t)b * a.N + i0) * c + j;
+#pragma unroll
+        for (int i = 0; i < TS; ++i) {
+          if (i < nv) o[(int64_t)i * c] = s[i];
+        }
+      }
+    }
+    __syncthreads();  // the next tile stages into aT and writes tb
+  }
+}
+
+// part[workgroup][b][:] = sum over the workgroup's samples of J_i^T u_bi, u (p, N, c) contiguous: the backward accumulation of
+// k_ggn_tiles started at g_L = u_bi (0 past the end of the tape), the same geometry and the same partial sums.
+template <typename T>
+__global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_t_tiles(GgnArgs<T> a, const T* __restrict__ u, int64_t p,
+                                                                         T* __restrict__ part) {
+  constexpr int G = GgnGroup<T>::value, TS = kGgnTS, W = kGgnW;
+  __shared__ __attribute__((aligned(16))) GgnLds<T> sm;
+  const int j = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.y * G + g;
+  const bool live = b < p;  // wave-uniform; a wave without a probe still stages and meets the barriers
+  T* __restrict__ out = part + ((int64_t)blockIdx.x * p + (live ? b : 0)) * a.P;
+  const int L = a.L, c = a.w[L];
+  T s[TS];  // this unit's cotangents for the samples of the tile
+
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const bool first = tile == (int64_t)blockIdx.x;
+    const int64_t i0 = tile * TS;
+    const int nv = a.N - i0 < TS ? (int)(a.N - i0) : TS;
+    {
+      const bool on = live && j < c;
+      const T* __restrict__ ub = u + ((int64_t)(live ? b : 0) * a.N + i0) * c + j;
+#pragma unroll
+      for (int i = 0; i < TS; ++i) s[i] = (on && i < nv) ? ub[(int64_t)i * c] : T(0);
+    }
+    for (int l = L; l >= 1; --l) {
+      const int wi = a.w[l - 1], wo = a.w[l];
+      const bool on = live && j < wo;
+      if (on) {
+        T sb = T(0);
+#pragma unroll
+        for (int i = 0; i < TS; ++i) sb += s[i];
+        ggn_accumulate<T>(out, a.off[l] + j, sb, first);
+      }
+      for (int k0 = 0; k0 < wi; k0 += W) {
+        __syncthreads();
+        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        __syncthreads();
+        if (on) {
+          const int kc = wi - k0 < W ? wi - k0 : W;
+          const int64_t base = a.off[l] + wo + (int64_t)k0 * wo + j;
+#pragma unroll 2
+          for (int kk = 0; kk < kc; ++kk) {
+            T acc = T(0);
+#pragma unroll
+            for (int i = 0; i < TS; ++i) acc += sm.aT[kk][i] * s[i];
+            ggn_accumulate<T>(out, base + (int64_t)kk * wo, acc, first);
+          }
+        }
+      }
+      if (l > 1) {
+        __syncthreads();  // tb is free (the cotangents of the layer above have been read)
+        if (on) {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
+        }
+        ggn_stage<T>(sm, a.dact[l - 1], wi, 0, i0, nv);  // aT is free as well: the slopes of layer l - 1, staged once for the group
+        __syncthreads();
+        if (live && j < wi) {
+          const T* __restrict__ Wrow = a.theta + a.off[l] + wo + (int64_t)j * wo;
+#pragma unroll
+          for (int i = 0; i < TS; ++i) s[i] = T(0);
+          for (int m = 0; m < wo; ++m) {
+            const T wt = Wrow[m];
+#pragma unroll
+            for (int i = 0; i < TS; ++i) s[i] += sm.tb[g][m][i] * wt;
+          }
+#pragma unroll
+          for (int i = 0; i < TS; ++i) s[i] = sm.aT[j][i] * s[i];
+        }
+      }
+    }
+    __syncthreads();  // the next tile stages into aT and writes tb
+  }
+}
+
+// y_b[i] = sum_blk part[blk][b][i], the workgroups in index order
+template <typename T>
+__global__ __launch_bounds__(256) void k_jac_t_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, T* __restrict__ y,
+                                                      int64_t ldy) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, p = gridDim.y;
+  if (i >= P) return;
+  T acc = T(0);
+  for (int64_t blk = 0; blk < nblk; ++blk) acc += part[(blk * p + b) * P + i];
+  y[b * ldy + i] = acc;
+}
+
 // partial[blockIdx.x] = this workgroup's share of sum_b L_b . R_b (fp64 sums, fixed order)
 template <typename T>
 __global__ __launch_bounds__(256) void k_ggn_dot(const T* __restrict__ L, int64_t ldl, const T* __restrict__ R, int64_t ldr, int64_t batch,
@@ -261,34 +423,46 @@ static int64_t ggn_dot_blocks(int64_t n) {
   return blocks < kGgnDotBlocks ? blocks : kGgnDotBlocks;
 }
 
-static int ggn_check(const mfx_operator* op) {
-  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
-  MFX_REQUIRE(net, MFX_ERR_INVALID, "GGN operator: ctx (the mfx_ggn_net) is NULL");
-  MFX_REQUIRE(net->nlayers >= 1 && net->nlayers <= MFX_GGN_MAX_LAYERS, MFX_ERR_INVALID, "GGN operator: nlayers = %d is outside 1..%d",
+// the checks of a net that the operator and the Jacobian maps share; `who` opens the message
+static int ggn_check_net(const mfx_ggn_net* net, const char* who) {
+  MFX_REQUIRE(net->nlayers >= 1 && net->nlayers <= MFX_GGN_MAX_LAYERS, MFX_ERR_INVALID, "%s: nlayers = %d is outside 1..%d", who,
               net->nlayers, MFX_GGN_MAX_LAYERS);
-  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "GGN operator: unknown loss %d",
-              net->loss);
-  MFX_REQUIRE(net->nsamples >= 1, MFX_ERR_INVALID, "GGN operator: nsamples = %lld must be at least 1", (long long)net->nsamples);
+  MFX_REQUIRE(net->nsamples >= 1, MFX_ERR_INVALID, "%s: nsamples = %lld must be at least 1", who, (long long)net->nsamples);
   const int L = net->nlayers;
   for (int l = 0; l <= L; ++l) {
-    MFX_REQUIRE(net->width[l] >= 1, MFX_ERR_INVALID, "GGN operator: width[%d] = %d must be at least 1", l, net->width[l]);
+    MFX_REQUIRE(net->width[l] >= 1, MFX_ERR_INVALID, "%s: width[%d] = %d must be at least 1", who, l, net->width[l]);
   }
-  MFX_REQUIRE(net->theta, MFX_ERR_INVALID, "GGN operator: theta is NULL");
-  MFX_REQUIRE(op->noise, MFX_ERR_INVALID, "GGN operator: noise (the shift alpha) is NULL");
+  MFX_REQUIRE(net->theta, MFX_ERR_INVALID, "%s: theta is NULL", who);
   for (int l = 0; l < L; ++l) {
-    MFX_REQUIRE(net->act[l], MFX_ERR_INVALID, "GGN operator: act[%d] is NULL", l);
-    MFX_REQUIRE(l == 0 || net->dact[l], MFX_ERR_INVALID, "GGN operator: dact[%d] is NULL", l);
+    MFX_REQUIRE(net->act[l], MFX_ERR_INVALID, "%s: act[%d] is NULL", who, l);
+    MFX_REQUIRE(l == 0 || net->dact[l], MFX_ERR_INVALID, "%s: dact[%d] is NULL", who, l);
   }
+  return MFX_OK;
+}
+
+static int ggn_check_limits(const mfx_ggn_net* net, const char* who) {
+  MFX_REQUIRE(net->width[0] <= kGgnMaxIn, MFX_ERR_UNSUPPORTED, "%s: width[0] = %d exceeds the input limit %d", who, net->width[0],
+              kGgnMaxIn);
+  for (int l = 1; l <= net->nlayers; ++l) {
+    MFX_REQUIRE(net->width[l] <= kGgnW, MFX_ERR_UNSUPPORTED, "%s: width[%d] = %d exceeds the layer limit %d", who, l, net->width[l],
+                kGgnW);
+  }
+  return MFX_OK;
+}
+
+static int ggn_check(const mfx_operator* op) {
+  static const char* who = "GGN operator";
+  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
+  MFX_REQUIRE(net, MFX_ERR_INVALID, "GGN operator: ctx (the mfx_ggn_net) is NULL");
+  MFX_TRY(ggn_check_net(net, who));
+  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "GGN operator: unknown loss %d",
+              net->loss);
+  MFX_REQUIRE(op->noise, MFX_ERR_INVALID, "GGN operator: noise (the shift alpha) is NULL");
   MFX_REQUIRE(net->loss != MFX_GGN_CROSS_ENTROPY || net->prob, MFX_ERR_INVALID, "GGN operator: prob is NULL (cross-entropy)");
   const int64_t P = ggn_params(net);
   MFX_REQUIRE(op->n == P, MFX_ERR_INVALID, "GGN operator: n = %lld, but the widths give P = %lld parameters", (long long)op->n,
               (long long)P);
-  MFX_REQUIRE(net->width[0] <= kGgnMaxIn, MFX_ERR_UNSUPPORTED, "GGN operator: width[0] = %d exceeds the input limit %d", net->width[0],
-              kGgnMaxIn);
-  for (int l = 1; l <= L; ++l) {
-    MFX_REQUIRE(net->width[l] <= kGgnW, MFX_ERR_UNSUPPORTED, "GGN operator: width[%d] = %d exceeds the layer limit %d", l,
-                net->width[l], kGgnW);
-  }
+  MFX_TRY(ggn_check_limits(net, who));
   MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "GGN operator: no row block (nrows > 0): every output row sums over all samples");
   return MFX_OK;
 }
@@ -308,16 +482,13 @@ static int64_t ggn_workspace_bytes(const mfx_operator* op, int64_t, int64_t p_ap
   return align_up(apply > dot ? apply : dot, 256);
 }
 
+// the kernel arguments of a checked net
 template <typename T>
-static int ggn_apply(const mfx_operator* op, int, const void* xv, int64_t ldx, const void*, int64_t, void* y, int64_t ldy, int64_t p,
-                     void* ws, int64_t ws_bytes, hipStream_t stream) {  // symmetric: the mode is ignored
-  const T* x = (const T*)xv;
-  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
+static GgnArgs<T> ggn_args(const mfx_ggn_net* net) {
   GgnArgs<T> a{};
   a.L = net->nlayers;
   a.loss = net->loss;
   a.N = net->nsamples;
-  a.P = op->n;
   a.ntiles = (a.N + kGgnTS - 1) / kGgnTS;
   int64_t off = 0;
   for (int l = 0; l <= a.L; ++l) {
@@ -331,8 +502,18 @@ static int ggn_apply(const mfx_operator* op, int, const void* xv, int64_t ldx, c
       a.dact[l] = (const T*)net->dact[l];
     }
   }
+  a.P = off;
   a.theta = (const T*)net->theta;
   a.prob = (const T*)net->prob;
+  return a;
+}
+
+template <typename T>
+static int ggn_apply(const mfx_operator* op, int, const void* xv, int64_t ldx, const void*, int64_t, void* y, int64_t ldy, int64_t p,
+                     void* ws, int64_t ws_bytes, hipStream_t stream) {  // symmetric: the mode is ignored
+  const T* x = (const T*)xv;
+  const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
+  const GgnArgs<T> a = ggn_args<T>(net);
   const int64_t nblk = ggn_blocks(a.N);
   const int64_t need = nblk * p * a.P * (int64_t)sizeof(T);
   MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "GGN operator: workspace too small: need %lld bytes", (long long)need);
@@ -369,4 +550,78 @@ static const OpKind kGgnKind = {ggn_check, ggn_check_grads, ggn_workspace_bytes,
                                 ggn_graph_key};
 const OpKind* ggn_kind() { return &kGgnKind; }  // for the table of kinds in mfx_ops.hip
 
+// ---- the Jacobian maps of the net (mfx_mlp_jac_*): rectangular, so not an operator kind ----
+static const char* const kJacWho = "MLP Jacobian";
+constexpr int kJacMaxBlocks = 1024;  // workgroups along the samples of J V (no partial sums: bounded only to keep the tile loop short)
+
+static int jac_check(const mfx_ggn_net* net, int dtype, int64_t p) {
+  MFX_REQUIRE(net, MFX_ERR_INVALID, "MLP Jacobian: net is NULL");
+  MFX_TRY(ggn_check_net(net, kJacWho));
+  MFX_TRY(ggn_check_limits(net, kJacWho));
+  MFX_REQUIRE(dtype == MFX_F32 || dtype == MFX_F64, MFX_ERR_UNSUPPORTED, "MLP Jacobian: unsupported dtype %d", dtype);
+  MFX_REQUIRE(p >= 1, MFX_ERR_INVALID, "MLP Jacobian: p = %lld must be at least 1", (long long)p);
+  MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "MLP Jacobian: p too large (at most 65535 vectors per call)");
+  return MFX_OK;
+}
+
+static int64_t jac_t_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {
+  return ggn_blocks(net->nsamples) * p * ggn_params(net) * (int64_t)dtype_size(dtype);
+}
+
+template <typename T>
+static int jac_apply_t(const mfx_ggn_net* net, const T* V, int64_t ldv, int64_t p, T* out, hipStream_t stream) {
+  const GgnArgs<T> a = ggn_args<T>(net);
+  constexpr int G = GgnGroup<T>::value;
+  const int64_t nblk = a.ntiles < kJacMaxBlocks ? a.ntiles : kJacMaxBlocks;
+  k_jac_tiles<T><<<dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G, 0, stream>>>(a, V, ldv, p, out);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+template <typename T>
+static int jac_t_apply_t(const mfx_ggn_net* net, const T* U, int64_t p, T* Y, int64_t ldy, T* ws, hipStream_t stream) {
+  const GgnArgs<T> a = ggn_args<T>(net);
+  constexpr int G = GgnGroup<T>::value;
+  const int64_t nblk = ggn_blocks(a.N);
+  k_jac_t_tiles<T><<<dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G, 0, stream>>>(a, U, p, ws);
+  MFX_CHECK_LAUNCH();
+  k_jac_t_reduce<T><<<dim3((unsigned)((a.P + 255) / 256), (unsigned)p), 256, 0, stream>>>(ws, nblk, a.P, Y, ldy);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
 }  // namespace mfx
+
+using namespace mfx;
+
+extern "C" {
+
+int64_t mfx_mlp_jac_workspace_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {
+  if (jac_check(net, dtype, p) != MFX_OK) return -1;
+  return align_up(jac_t_bytes(net, dtype, p), 256);
+}
+
+int mfx_mlp_jac_apply(const mfx_ggn_net* net, int dtype, const void* V, int64_t ldv, int64_t p, void* out, void* stream) {
+  MFX_TRY(jac_check(net, dtype, p));
+  MFX_REQUIRE(V && out, MFX_ERR_INVALID, "MLP Jacobian: V or out is NULL");
+  MFX_REQUIRE(ldv >= ggn_params(net), MFX_ERR_INVALID, "MLP Jacobian: ldv = %lld is less than the P = %lld parameters", (long long)ldv,
+              (long long)ggn_params(net));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == MFX_F32) return jac_apply_t<float>(net, (const float*)V, ldv, p, (float*)out, s);
+  return jac_apply_t<double>(net, (const double*)V, ldv, p, (double*)out, s);
+}
+
+int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_t p, void* Y, int64_t ldy, void* ws, int64_t ws_bytes,
+                        void* stream) {
+  MFX_TRY(jac_check(net, dtype, p));
+  MFX_REQUIRE(U && Y, MFX_ERR_INVALID, "MLP Jacobian: U or Y is NULL");
+  MFX_REQUIRE(ldy >= ggn_params(net), MFX_ERR_INVALID, "MLP Jacobian: ldy = %lld is less than the P = %lld parameters", (long long)ldy,
+              (long long)ggn_params(net));
+  const int64_t need = jac_t_bytes(net, dtype, p);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "MLP Jacobian: workspace too small: need %lld bytes", (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == MFX_F32) return jac_t_apply_t<float>(net, (const float*)U, p, (float*)Y, ldy, (float*)ws, s);
+  return jac_t_apply_t<double>(net, (const double*)U, p, (double*)Y, ldy, (double*)ws, s);
+}
+
+}  // extern "C"

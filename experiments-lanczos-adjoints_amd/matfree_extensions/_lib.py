@@ -135,7 +135,7 @@ class OpGrads(C.Structure):
 
 # every symbol include/mfx.h declares: (name, restype, argtypes)
 _P, _I64, _I = C.c_void_p, C.c_int64, C.c_int
-_OPP, _GRP, _CMP = C.POINTER(Operator), C.POINTER(OpGrads), C.POINTER(Comm)
+_OPP, _GRP, _CMP, _NETP = C.POINTER(Operator), C.POINTER(OpGrads), C.POINTER(Comm), C.POINTER(GgnNet)
 SYMBOLS = {
     "mfx_last_error": (C.c_char_p, []),
     "mfx_version": (_I, []),
@@ -206,6 +206,9 @@ SYMBOLS = {
     "mfx_gram_cross_vjp_dense": (_I, [_OPP, _P, _I64, _P, _I64, _GRP, _P, _P, _I64, _P]),
     "mfx_gram_block_workspace_bytes": (_I64, [_OPP, _I64, _I64]),
     "mfx_gram_block": (_I, [_OPP, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "mfx_mlp_jac_workspace_bytes": (_I64, [_NETP, _I, _I64]),
+    "mfx_mlp_jac_apply": (_I, [_NETP, _I, _P, _I64, _I64, _P, _P]),
+    "mfx_mlp_jac_t_apply": (_I, [_NETP, _I, _P, _I64, _P, _I64, _P, _I64, _P]),
     "mfx_timing_enable": (_I, [_I]),
     "mfx_timing_reset": (_I, []),
     "mfx_timing_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

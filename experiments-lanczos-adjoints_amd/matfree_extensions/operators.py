@@ -17,6 +17,9 @@ whole Krylov loop, the transposed matvec and the parameter-gradient sweep run as
   GgnMlpOp(x_train, theta, widths)  params = (alpha,)             util/bnn_util.py:263-293,477-499 (GGN of an MLP + alpha I, theta fixed)
   CallbackOp(fn)                    any Python ``fn(v, *params)`` (torch ops); per-step host control
 
+``MlpJacobian(x, theta, widths)`` is not an operator (it is rectangular): the Jacobian of the same MLP at the points x as the pair of
+linear maps ``apply`` (J V) and ``t_apply`` (J^T U), for the linearised-Laplace predictive (util/bnn_util.py:206-215, 630-683).
+
 ``op.bind(*params)`` freezes the parameters into a zero-argument-parameter matvec (what the GP code
 hands to ``krylov_logdet_slq``, util/gp_util.py:555-557) while keeping them differentiable.
 """
@@ -618,6 +621,69 @@ class StencilOp(NativeOp):
         return s, (g,)
 
 
+_MLP_FIXED = ("holds theta and {x} fixed: a gradient with respect to them needs third derivatives of the network, which the reference "
+              "never takes; pass detached tensors")
+
+
+def _mlp_problem(who, x, theta, widths, activation, xname):
+    """The checks GgnMlpOp and MlpJacobian share -> (widths, number of parameters, x as (N, d_in))."""
+    if activation not in ("tanh", "relu"):
+        raise ValueError("activation must be 'tanh' or 'relu'")
+    if theta.requires_grad or x.requires_grad:
+        raise NotImplementedError(f"{who} " + _MLP_FIXED.format(x=xname))
+    widths = tuple(int(w) for w in widths)
+    nl = len(widths) - 1
+    if not 1 <= nl <= _lib.GGN_MAX_LAYERS or min(widths) < 1:
+        raise ValueError(f"{who}: widths {widths} must name 1..{_lib.GGN_MAX_LAYERS} layers of at least one unit")
+    n = sum((wi + 1) * wo for wi, wo in zip(widths[:-1], widths[1:]))
+    if theta.dim() != 1 or theta.numel() != n:
+        raise ValueError(f"{who}: widths {widths} have {n} parameters, theta has shape {tuple(theta.shape)}")
+    x2 = x.reshape(x.shape[0], -1)
+    if x2.shape[0] < 1 or x2.shape[1] != widths[0] or x2.dtype != theta.dtype or x2.device != theta.device:
+        raise ValueError(f"{who}: {xname} {tuple(x.shape)} ({x2.dtype}, {x2.device}) does not match widths[0] = "
+                         f"{widths[0]} and theta ({theta.dtype}, {theta.device})")
+    return widths, n, x2
+
+
+def _mlp_tape(theta, x, widths, activation, softmax):
+    """{"act": [a_0 = x, ..., a_{L-1}], "dact": [None, phi'(z_1), ..., phi'(z_{L-1})], "logits", "prob" (None without softmax)}"""
+    with torch.no_grad():
+        a, off = x.contiguous(), 0
+        act, dact = [a], [None]
+        nl = len(widths) - 1
+        for l in range(1, nl + 1):
+            wi, wo = widths[l - 1], widths[l]
+            z = a @ theta[off + wo : off + wo + wi * wo].reshape(wi, wo) + theta[off : off + wo]
+            off += (wi + 1) * wo
+            if l < nl:
+                if activation == "tanh":
+                    a = torch.tanh(z)
+                    d = 1 - a * a
+                else:
+                    a = torch.relu(z)
+                    d = (z > 0).to(z.dtype)
+                act.append(a.contiguous())
+                dact.append(d.contiguous())
+        prob = torch.softmax(z, dim=-1).contiguous() if softmax else None
+    return {"act": act, "dact": dact, "logits": z, "prob": prob}
+
+
+def _mlp_net(widths, theta, tape, loss_code):
+    """struct mfx_ggn_net over a tape (a host struct of device pointers: it must not outlive the tensors)"""
+    nl = len(widths) - 1
+    net = _lib.GgnNet()
+    net.nlayers, net.loss, net.nsamples = nl, loss_code, tape["act"][0].shape[0]
+    net.width = (C.c_int32 * (_lib.GGN_MAX_LAYERS + 1))(*widths)
+    net.theta = theta.data_ptr()
+    for l in range(nl):
+        net.act[l] = tape["act"][l].data_ptr()
+        if l >= 1:
+            net.dact[l] = tape["dact"][l].data_ptr()
+    if tape["prob"] is not None:
+        net.prob = tape["prob"].data_ptr()
+    return net
+
+
 class GgnMlpOp(NativeOp):
     """The generalised Gauss-Newton matrix of an MLP plus a shift, matrix-free (the reference's ggn_vp_parallel inside
     callibration_loss, util/bnn_util.py:263-293, 477-499):
@@ -635,60 +701,21 @@ class GgnMlpOp(NativeOp):
     _LOSSES = {"cross_entropy": _lib.GGN_CROSS_ENTROPY, "mse": _lib.GGN_MSE}
 
     def __init__(self, x_train, theta, widths, *, activation="tanh", loss="cross_entropy"):
-        if activation not in ("tanh", "relu"):
-            raise ValueError("activation must be 'tanh' or 'relu'")
         if loss not in self._LOSSES:
             raise ValueError(f"loss must be one of {sorted(self._LOSSES)}")
-        if theta.requires_grad or x_train.requires_grad:
-            raise NotImplementedError("GgnMlpOp holds theta and x_train fixed: a gradient with respect to them needs third derivatives of "
-                                      "the network, which the reference never takes; pass detached tensors")
-        self.widths = tuple(int(w) for w in widths)
-        nl = len(self.widths) - 1
-        if not 1 <= nl <= _lib.GGN_MAX_LAYERS or min(self.widths) < 1:
-            raise ValueError(f"GgnMlpOp: widths {self.widths} must name 1..{_lib.GGN_MAX_LAYERS} layers of at least one unit")
-        self.n = sum((wi + 1) * wo for wi, wo in zip(self.widths[:-1], self.widths[1:]))
-        if theta.dim() != 1 or theta.numel() != self.n:
-            raise ValueError(f"GgnMlpOp: widths {self.widths} have {self.n} parameters, theta has shape {tuple(theta.shape)}")
-        x = x_train.reshape(x_train.shape[0], -1)
-        if x.shape[0] < 1 or x.shape[1] != self.widths[0] or x.dtype != theta.dtype or x.device != theta.device:
-            raise ValueError(f"GgnMlpOp: x_train {tuple(x_train.shape)} ({x.dtype}, {x.device}) does not match widths[0] = "
-                             f"{self.widths[0]} and theta ({theta.dtype}, {theta.device})")
+        self.widths, self.n, x = _mlp_problem("GgnMlpOp", x_train, theta, widths, activation, "x_train")
         self.activation, self.loss = activation, loss
         self.theta = theta.detach().contiguous()
         self.tape = self._build_tape(x)
-        net = _lib.GgnNet()
-        net.nlayers, net.loss, net.nsamples = nl, self._LOSSES[loss], x.shape[0]
-        net.width = (C.c_int32 * (_lib.GGN_MAX_LAYERS + 1))(*self.widths)
-        net.theta = self.theta.data_ptr()
-        for l in range(nl):
-            net.act[l] = self.tape["act"][l].data_ptr()
-            if l >= 1:
-                net.dact[l] = self.tape["dact"][l].data_ptr()
-        if loss == "cross_entropy":
-            net.prob = self.tape["prob"].data_ptr()
-        self.net = net  # the descriptor's ctx points here: lives as long as the operator
+        self.net = _mlp_net(self.widths, self.theta, self.tape, self._LOSSES[loss])  # the descriptor's ctx points here
 
     def _build_tape(self, x):
         """{"act": [a_0 = x, ..., a_{L-1}], "dact": [None, phi'(z_1), ..., phi'(z_{L-1})], "logits", "prob" (None for mse)}"""
-        with torch.no_grad():
-            a, off = x.contiguous(), 0
-            act, dact = [a], [None]
-            nl = len(self.widths) - 1
-            for l in range(1, nl + 1):
-                wi, wo = self.widths[l - 1], self.widths[l]
-                z = a @ self.theta[off + wo : off + wo + wi * wo].reshape(wi, wo) + self.theta[off : off + wo]
-                off += (wi + 1) * wo
-                if l < nl:
-                    if self.activation == "tanh":
-                        a = torch.tanh(z)
-                        d = 1 - a * a
-                    else:
-                        a = torch.relu(z)
-                        d = (z > 0).to(z.dtype)
-                    act.append(a.contiguous())
-                    dact.append(d.contiguous())
-            prob = torch.softmax(z, dim=-1).contiguous() if self.loss == "cross_entropy" else None
-        return {"act": act, "dact": dact, "logits": z, "prob": prob}
+        return _mlp_tape(self.theta, x, self.widths, self.activation, self.loss == "cross_entropy")
+
+    def jacobian(self):
+        """The network Jacobian at the operator's own samples, over its own tape: the tensors are shared, nothing is recomputed."""
+        return MlpJacobian._over(self.widths, self.activation, self.theta, self.tape)
 
     def constrain(self, alpha):
         return (alpha.reshape(1),)
@@ -709,6 +736,103 @@ class GgnMlpOp(NativeOp):
         s = _lib.OpGrads()
         s.noise = g.data_ptr()
         return s, (g,)
+
+
+class MlpJacobian:
+    """The Jacobian J = d f(theta; x_i) / d theta of the MLP of ``GgnMlpOp`` at the points x, (N c) x P, as a pair of linear maps over a
+    tape built once (include/mfx.h, next to struct mfx_ggn_net; csrc/mfx_ggn.hip):
+
+      jac.apply(V)     J V:    (p, P) -> (p, N, c),  (P,) -> (N, c)        mfx_mlp_jac_apply
+      jac.t_apply(U)   J^T U:  (p, N, c) -> (p, P),  (N, c) -> (P,)        mfx_mlp_jac_t_apply
+
+    ``jac.logits`` (N, c) is the mean prediction f(theta; x), ``jac.n_params`` = P.  theta and x are FIXED, as for GgnMlpOp; both maps
+    are differentiable in their argument (they are linear: the backward of one is the other).  ``jac.rows(i0, i1)`` is the Jacobian
+    at the points i0 .. i1 - 1 over row slices of the same tape."""
+
+    def __init__(self, x, theta, widths, *, activation="tanh"):
+        widths, _, x2 = _mlp_problem("MlpJacobian", x, theta, widths, activation, "x")
+        theta = theta.detach().contiguous()
+        self._set(widths, activation, theta, _mlp_tape(theta, x2, widths, activation, False))
+
+    def _set(self, widths, activation, theta, tape):
+        self.widths, self.activation, self.theta, self.tape = widths, activation, theta, tape
+        self.n_params = sum((wi + 1) * wo for wi, wo in zip(widths[:-1], widths[1:]))
+        self.n_samples, self.n_out = tape["act"][0].shape[0], widths[-1]
+        self.logits = tape["logits"]
+        self.net = _mlp_net(widths, theta, {**tape, "prob": None}, 0)  # the maps read neither the loss nor the softmax
+
+    @classmethod
+    def _over(cls, widths, activation, theta, tape):
+        new = cls.__new__(cls)
+        new._set(widths, activation, theta, tape)
+        return new
+
+    def rows(self, i0, i1):
+        """The Jacobian at the points i0 .. i1 - 1: row slices of the tape tensors (views), nothing rebuilt."""
+        if not 0 <= i0 < i1 <= self.n_samples:
+            raise ValueError(f"MlpJacobian.rows: [{i0}, {i1}) is not a range of the {self.n_samples} points")
+        cut = lambda t: None if t is None else t[i0:i1]  # noqa: E731  (rows of a contiguous matrix: contiguous)
+        tape = {"act": [cut(t) for t in self.tape["act"]], "dact": [cut(t) for t in self.tape["dact"]],
+                "logits": cut(self.tape["logits"]), "prob": cut(self.tape["prob"])}
+        return MlpJacobian._over(self.widths, self.activation, self.theta, tape)
+
+    def apply(self, V):
+        return _JacFn.apply(self, False, V)
+
+    def t_apply(self, U):
+        return _JacFn.apply(self, True, U)
+
+    # ---- the two calls, outside autograd ----
+    def _check(self, what, t):
+        _lib.require_device(t, self.theta)
+        if t.dtype != self.theta.dtype:
+            raise TypeError(f"MlpJacobian: {what} must have the dtype of theta and the tape ({self.theta.dtype}), got {t.dtype}")
+        if t.device != self.theta.device:
+            raise ValueError(f"MlpJacobian: {what} is on {t.device}, theta and the tape on {self.theta.device}")
+
+    def _forward(self, V):
+        self._check("V", V)
+        batched = V.dim() == 2
+        V2 = (V if batched else V[None]).contiguous()
+        if V2.dim() != 2 or V2.shape[1] != self.n_params or V2.shape[0] < 1:
+            raise ValueError(f"MlpJacobian.apply: V {tuple(V.shape)} must be (p, {self.n_params}) or ({self.n_params},)")
+        p = V2.shape[0]
+        out = torch.empty((p, self.n_samples, self.n_out), dtype=V2.dtype, device=V2.device)
+        with torch.cuda.device(V2.device):
+            _lib.check(_lib.get().mfx_mlp_jac_apply(C.byref(self.net), _lib.dtype_code(V2.dtype), _lib.ptr(V2), self.n_params, p,
+                                                    _lib.ptr(out), _lib.stream_ptr(V2.device)))
+        return out if batched else out[0]
+
+    def _transpose(self, U):
+        self._check("U", U)
+        batched = U.dim() == 3
+        U3 = (U if batched else U[None]).contiguous()
+        if U3.dim() != 3 or tuple(U3.shape[1:]) != (self.n_samples, self.n_out) or U3.shape[0] < 1:
+            raise ValueError(f"MlpJacobian.t_apply: U {tuple(U.shape)} must be (p, {self.n_samples}, {self.n_out}) or "
+                             f"({self.n_samples}, {self.n_out})")
+        p, lib, code = U3.shape[0], _lib.get(), _lib.dtype_code(U3.dtype)
+        need = int(lib.mfx_mlp_jac_workspace_bytes(C.byref(self.net), code, p))
+        if need < 0:  # the query refuses what the call would: the call names the reason and the code
+            _lib.check(lib.mfx_mlp_jac_t_apply(C.byref(self.net), code, _lib.ptr(U3), p, None, self.n_params, None, 0, None))
+        ws = _lib.scratch(need, U3.device)
+        Y = torch.empty((p, self.n_params), dtype=U3.dtype, device=U3.device)
+        with _lib.busy(ws):
+            _lib.check(lib.mfx_mlp_jac_t_apply(C.byref(self.net), code, _lib.ptr(U3), p, _lib.ptr(Y), self.n_params, _lib.ptr(ws),
+                                               ws.numel(), _lib.stream_ptr(U3.device)))
+        return Y if batched else Y[0]
+
+
+class _JacFn(torch.autograd.Function):
+    """J V (transpose False) or J^T U (True); both are linear in their argument, so the backward of one is the other."""
+
+    @staticmethod
+    def forward(ctx, jac, transpose, t):
+        ctx.jac, ctx.transpose = jac, transpose
+        return jac._transpose(t) if transpose else jac._forward(t)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return None, None, _JacFn.apply(ctx.jac, not ctx.transpose, dy)
 
 
 def softplus(x, beta=1.0, threshold=20.0):

@@ -6,8 +6,13 @@ the k x k tridiagonal matrix (torch, k <= ~100).
 Calibration (:21-40, 43-61, 120-203, 218-228, 477-518): the reference's MLP on a flat parameter vector, the dense GGN baseline
 (``ggn_full``, torch.func), the matrix-free GGN operator (``ggn_operator`` -> ``operators.GgnMlpOp``, one fused HIP pass over a tape
 per matvec), the log-determinant solvers and the calibration losses.  The reference differentiates those losses in ``log_alpha``
-alone, with theta and the data fixed; so does this module: a theta that requires grad is refused.  Conv nets, ViTs,
-``hutchinson_diagonal`` / ``bnn_baselines`` and data loaders are not here.
+alone, with theta and the data fixed; so does this module: a theta that requires grad is refused.
+
+Predictive (:206-215, 549-683): N(f(x*; theta), J* (GGN + alpha I)^-1 J*^T) at test points -- the dense baseline ``predictive_cov``,
+the matrix-free ``predictive_cov_operator`` (``operators.MlpJacobian`` for J* and J*^T, a batched CG on the bound GGN operator in
+between), ``logpdf_cholesky`` / ``logpdf_eigh``, ``predictive_posterior_loglikelihood`` and ``predictive_logit_sampler``.
+
+Conv nets, ViTs, ``hutchinson_diagonal`` / ``bnn_baselines`` and data loaders are not here.
 """
 
 from __future__ import annotations
@@ -16,8 +21,8 @@ import math
 
 import torch
 
-from .. import hutchinson, lanczos
-from ..operators import DenseOp, GgnMlpOp
+from .. import cg, hutchinson, lanczos
+from ..operators import DenseOp, GgnMlpOp, MlpJacobian
 
 
 def _normal(key, shape, like):
@@ -295,3 +300,157 @@ def callibration_loss(model_apply, unflatten, hyperparam_unconstrain, n_params, 
         return -(log_prior - logdet)
 
     return loss_fn
+
+
+# ------------------------------------------------------------------------------------------------
+# the predictive distribution at test points (util/bnn_util.py:206-215, 549-683)
+# ------------------------------------------------------------------------------------------------
+_REFERENCE_CG_STEPS = 20  # krylov_solve_cg_fixed_step_reortho(20), hard-coded at util/bnn_util.py:643, 668
+
+
+def _cov_matrix(cov, mean):
+    """``cov`` applied to the identity in ONE batched call (the reference: jacfwd / jacfwd_map of cov at the mean, column by
+    column): row b of the result of the call is cov e_b, the b-th column of the matrix."""
+    n = mean.shape[0]
+    return cov(torch.eye(n, dtype=mean.dtype, device=mean.device)).T
+
+
+def logpdf_cholesky():
+    """util/bnn_util.py:549-574: ``logpdf(y, mean=, cov=)`` -> (value, {}) of N(mean, C) by a Cholesky factorisation; ``cov`` is a
+    callable that applies C to a batch of vectors, (p, n) -> (p, n)."""
+
+    def logpdf(y, /, *, mean, cov):
+        cholesky = torch.linalg.cholesky(_cov_matrix(cov, mean))
+        logdet = torch.log(torch.diagonal(cholesky)).sum()
+        tmp = torch.linalg.solve_triangular(cholesky, (y - mean)[:, None], upper=False)[:, 0]
+        mahalanobis = torch.dot(tmp, tmp)
+        (n,) = mean.shape
+        return -logdet - 0.5 * mahalanobis - n / 2 * math.log(2 * math.pi), {}
+
+    return logpdf
+
+
+def _eigh(cov_matrix):
+    """jnp.linalg.eigh symmetrises its input by default; torch reads one triangle, so the mean of both is taken here"""
+    return torch.linalg.eigh(0.5 * (cov_matrix + cov_matrix.T))
+
+
+def logpdf_eigh():
+    """util/bnn_util.py:599-627: the same by a symmetric eigendecomposition, with the reference's rules as written: an eigenvalue
+    below 1e-6 counts as 1 in the log-determinant and as 0 (not 1 / w) in the Mahalanobis norm."""
+
+    def logpdf(y, /, *, mean, cov):
+        w, v = _eigh(_cov_matrix(cov, mean))
+        small = w < 1e-6
+        logdet = torch.log(torch.where(small, torch.ones_like(w), w)).sum() / 2
+        inv_eigvals = torch.where(small, torch.zeros_like(w), 1 / torch.where(small, torch.ones_like(w), w))
+        factor = (v * torch.sqrt(inv_eigvals)[None, :]) @ v.T
+        tmp = factor @ (y - mean)
+        mahalanobis = torch.dot(tmp, tmp)
+        (n,) = mean.shape
+        return -logdet - 0.5 * mahalanobis - n / 2 * math.log(2 * math.pi), {}
+
+    return logpdf
+
+
+def predictive_cov(*, ggn_fun, model_fun, param_unflatten, hyperparam_unconstrain):
+    """util/bnn_util.py:206-215, the dense baseline: the inverse of the full GGN (``ggn_full``) and the test Jacobian by
+    torch.func.jacrev; ``evaluate(a, variables, x_train, y_train, x_test)`` -> (N*, c, c), J_i (GGN + alpha I)^-1 J_i^T per point."""
+
+    def evaluate(a, variables, x_train, y_train, x_test):
+        alpha = hyperparam_unconstrain(a)
+        covariance = torch.linalg.inv(ggn_fun(alpha, variables, x_train, y_train))
+        J_test = torch.func.jacrev(lambda v: model_fun(param_unflatten(v), x_test))(variables)  # (N*, c, P)
+        return torch.einsum("nci,ij,ndj->ncd", J_test, covariance, J_test)
+
+    return evaluate
+
+
+def predictive_cov_operator(ggn_op, jac, *, solve=None, chunk=32):
+    """The same per-point covariances without a matrix: ``ggn_op`` is a ``GgnMlpOp`` over the training set (anything with
+    ``bind(alpha)``), ``jac`` an ``operators.MlpJacobian`` over the test points (anything with ``rows`` / ``apply`` / ``t_apply`` /
+    ``n_samples`` / ``n_out``), ``solve(A, B) -> (X, info)`` a batched solver of ``cg.*`` (default: ``cg.cg_fixed_step_reortho(20)``,
+    what the reference hard-codes).  ``evaluate(alpha)`` -> (N*, c, c).  Per chunk of B <= ``chunk`` test points: R = J_c^T I
+    (B c unit cotangents -> (B c, P)), S = solve(ggn_op.bind(alpha), R), C = J_c S, of which the B diagonal c x c blocks are kept.
+    Memory per chunk: three (B c, P) matrices and the solver's own."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"predictive_cov_operator: chunk must be >= 1, got {chunk}")
+    solve = cg.cg_fixed_step_reortho(_REFERENCE_CG_STEPS) if solve is None else solve
+
+    def evaluate(alpha):
+        bound = ggn_op.bind(alpha)
+        n, c = jac.n_samples, jac.n_out
+        blocks = []
+        for i0 in range(0, n, chunk):
+            part = jac.rows(i0, min(i0 + chunk, n))
+            B = part.n_samples
+            eye = torch.eye(B * c, dtype=part.logits.dtype, device=part.logits.device)
+            R = part.t_apply(eye.reshape(B * c, B, c))
+            S, _info = solve(bound, R)
+            C = part.apply(S).reshape(B, c, B, c)  # C[a, j, a', k] = (J_a' A^-1 J_a^T)[k, j]
+            idx = torch.arange(B, device=C.device)
+            blocks.append(C[idx, :, idx, :].transpose(-1, -2))
+        return torch.cat(blocks)
+
+    return evaluate
+
+
+def _mlp_jacobian(model_apply):
+    """(params_vec, x_test) -> MlpJacobian for ``model_mlp``'s apply, which names the widths and the activation"""
+
+    def jacobian(params_vec, x_test):
+        d_in = x_test.reshape(x_test.shape[0], -1).shape[1]
+        return MlpJacobian(x_test, params_vec, model_apply.widths(d_in), activation=model_apply.activation)
+
+    return jacobian
+
+
+def _joint_cov_vp(jac, ggn_fun, solve):
+    """v -> J* solve(ggn_fun, J*^T v) on batches (p, N* c) of flattened logit vectors: the joint (N* c)^2 predictive covariance"""
+    n, c = jac.n_samples, jac.n_out
+
+    def cov_vp(V):
+        R = jac.t_apply(V.reshape(V.shape[0], n, c))
+        S, _info = solve(ggn_fun, R)
+        return jac.apply(S).reshape(V.shape[0], n * c)
+
+    return cov_vp
+
+
+def predictive_posterior_loglikelihood(*, model_apply, unflatten, logpdf, ggn_fun, solve=None, jacobian=None):
+    """util/bnn_util.py:630-652: ``eval_logprob(params_vec, x_test, y_test)`` -> ``logpdf(y, mean=f(x*), cov=J* solve(ggn_fun, J*^T .))``
+    over the flattened logits.  ``model_apply`` is ``model_mlp``'s apply (it names the widths and the activation; ``unflatten`` is
+    unused: theta stays flat); ``ggn_fun`` a bound operator (``ggn_operator(...).bind(alpha)``) or any callable v -> A v;
+    ``solve`` defaults to the reference's ``cg.cg_fixed_step_reortho(20)``.  ``jacobian=`` fixes what stands for J* instead
+    (``lambda params_vec, x_test: object with logits / apply / t_apply`` -- the tests put a dense Jacobian there)."""
+    solve = cg.cg_fixed_step_reortho(_REFERENCE_CG_STEPS) if solve is None else solve
+    jacobian = _mlp_jacobian(model_apply) if jacobian is None else jacobian
+
+    def eval_logprob(params_vec, x_test, y_test):
+        jac = jacobian(params_vec, x_test)
+        return logpdf(y_test.reshape(-1), mean=jac.logits.reshape(-1), cov=_joint_cov_vp(jac, ggn_fun, solve))
+
+    return eval_logprob
+
+
+def predictive_logit_sampler(*, model_apply, unflatten, num_samples, ggn_fun, solve=None, jacobian=None):
+    """util/bnn_util.py:655-683: ``eval_test_set(params_vec, x_test, y_test, key)`` -> (num_samples, *y_test.shape) logit samples
+    mean + F eps with F = V diag(sqrt(1 / w)) V^T from the eigendecomposition of the joint covariance.  A quirk of the reference,
+    reproduced: the root is taken of 1 / w (0 where w < 1e-6), so F is the inverse square root of the covariance, not its square
+    root.  ``key``: an integer seed, or the (num_samples, N* c) draws ``eps`` themselves.  The other arguments as in
+    ``predictive_posterior_loglikelihood``."""
+    solve = cg.cg_fixed_step_reortho(_REFERENCE_CG_STEPS) if solve is None else solve
+    jacobian = _mlp_jacobian(model_apply) if jacobian is None else jacobian
+
+    def eval_test_set(params_vec, x_test, y_test, key):
+        jac = jacobian(params_vec, x_test)
+        mean = jac.logits.reshape(-1)
+        w, v = _eigh(_cov_matrix(_joint_cov_vp(jac, ggn_fun, solve), mean))
+        small = w < 1e-6
+        inv_eigvals = torch.where(small, torch.zeros_like(w), 1 / torch.where(small, torch.ones_like(w), w))
+        cov_sqrt = (v * torch.sqrt(inv_eigvals)[None, :]) @ v.T
+        eps = _normal(key, (num_samples, mean.shape[0]), mean)
+        return (mean[None, :] + eps @ cov_sqrt.T).reshape(num_samples, *y_test.shape)
+
+    return eval_test_set

@@ -28,7 +28,8 @@ extern "C" {
 
 #define MFX_VERSION 201 /* 201: + mfx_comm_rccl_count.  MFX_OP_STENCIL and the st_* fields at the end of mfx_operator are additive (no
                            bump, as for mfx_op_grads.x): callers that zero-fill the descriptor never select them.  MFX_OP_GGN is
-                           additive too: its data travels through the existing `ctx` pointer, no struct grows */
+                           additive too: its data travels through the existing `ctx` pointer, no struct grows.  So are the three
+                           mfx_mlp_jac_* entry points: new symbols, no struct or existing signature changes */
 
 enum { MFX_F32 = 0, MFX_F64 = 1 };
 enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4, MFX_OP_GGN = 5 };
@@ -115,6 +116,28 @@ typedef struct mfx_ggn_net {
   const void* dact[MFX_GGN_MAX_LAYERS];  /* dact[l] = phi'(z_l), (N, width[l]), l = 1..L-1; dact[0] unused */
   const void* prob;                      /* (N, c) softmax; NULL for MSE */
 } mfx_ggn_net;
+
+/* The Jacobian of the same MLP at the N samples of a tape, J = d f(theta; x_i) / d theta stacked over i ((N c) x P), as a pair of
+ * linear maps: what the linearised-Laplace predictive N(f(x*), J* (GGN + alpha I)^-1 J*^T) needs at the test points
+ * (util/bnn_util.py:206-215, 630-683).  They take the net directly -- J is rectangular, so it is not an operator kind -- and read
+ * neither `loss` nor `prob` (any loss value and a NULL prob are accepted).  theta layout, tape and limits as above.
+ *   mfx_mlp_jac_apply     out[b][i][:] = J_i v_b,  out (p, N, c) contiguous, V (p, P) with leading dimension ldv:
+ *                           t_0 = 0;  s_l = V_W_l^T a_{l-1} + v_b_l + W_l^T t_{l-1};  t_l = dact_l o s_l (l < L);  out = t_L = s_L
+ *                         No workspace and no sum over the samples.
+ *   mfx_mlp_jac_t_apply   y_b = sum_i J_i^T u_bi,  U (p, N, c) contiguous, Y (p, P) with leading dimension ldy:
+ *                           g_L = u_bi;  y_b_l += g_l;  y_W_l += a_{l-1} g_l^T;  g_{l-1} = dact_{l-1} o (W_l g_l)
+ *                         The sum over samples as for the operator: per-workgroup partial sums in the workspace (written before
+ *                         they are read), then one pass that adds them in index order; no atomics, bit-identical from run to run,
+ *                         and the bits of a vector's result do not depend on how many vectors share the call.
+ *   mfx_mlp_jac_workspace_bytes   bytes mfx_mlp_jac_t_apply needs for p vectors (host arithmetic); -1 for arguments it would refuse.
+ * The two maps are each other's transpose: <U, J V> = <J^T U, V>.
+ * Refused before any launch.  MFX_ERR_INVALID: net, theta, act[l] (l < L), dact[l] (1 <= l < L), V, U, out or Y NULL; nlayers
+ * outside 1..MFX_GGN_MAX_LAYERS; a width < 1; nsamples < 1; p < 1; ldv or ldy less than P.  MFX_ERR_UNSUPPORTED: width[0] > 65536 or
+ * width[l] > 64 for l >= 1; a dtype other than MFX_F32 / MFX_F64; p > 65535.  MFX_ERR_WORKSPACE: ws NULL or ws_bytes too small. */
+int64_t mfx_mlp_jac_workspace_bytes(const mfx_ggn_net* net, int dtype, int64_t p);
+int mfx_mlp_jac_apply(const mfx_ggn_net* net, int dtype, const void* V, int64_t ldv, int64_t p, void* out, void* stream);
+int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_t p, void* Y, int64_t ldy, void* ws, int64_t ws_bytes,
+                        void* stream);
 
 /* Operator descriptor: a POD of borrowed pointers, valid for the duration of one call.
  * Replaces the reference's `matvec(v, *params)` closures:
