@@ -139,8 +139,9 @@ struct RbfMatvecArgs {
   const int* rangeflag;
   int64_t ldpart, row0, rend;
 };
-// launcher of the fat-wave matvec kernel (mfx_rbf_fat.hip): RBF, d <= 16, chunks of nb * 32 vectors (nb = 1, 2);
+// launcher of the fat-wave matvec kernels (mfx_rbf_fat.hip): RBF, d <= 16, chunks of nb * 32 vectors (nb = 1, 2);
+// wide16: k_rbf_fat_apply16 (v_mfma_f32_16x16x32_f16) where it is built -- d <= 8 and nb = 2 --, k_rbf_fat_apply for every other shape;
 // grid = (ceil(rows / 512), chunks, splits)
-int rbf_fat_launch(int dpad, int nb, bool vec4, dim3 grid, hipStream_t stream, const RbfMatvecArgs& a);
+int rbf_fat_launch(int dpad, int nb, bool vec4, bool wide16, dim3 grid, hipStream_t stream, const RbfMatvecArgs& a);
 
 }  // namespace mfx

@@ -428,9 +428,315 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply(const float* __restric
 #undef MFX_WN
 #undef MFX_WD
 
-int rbf_fat_launch(int dpad, int nb, bool vec4, dim3 grid, hipStream_t stream, const RbfMatvecArgs& a) {
+// ================================================================================================================================
+// The same sweep on v_mfma_f32_16x16x32_f16: RBF, d <= 8 (3 (d + 2) <= 32: the whole distance product is ONE k-step), chunks of 64
+// vectors.  Same flops per cycle as 32x32x16, but the dense 16x16x32 stream holds a higher clock (tools/unit16_bench.hip; the
+// parameter-gradient GEMM made the same move).
+//
+// Unit of work = 16 rows x 32 columns (a column block jb of the tile) x 64 probes: 2 distance MFMAs, 8 kernel entries per lane
+// (8 v_exp, 4 v_cvt_pk, 4 v_fma_mixlo + 4 v_fma_mixhi), 12 contraction MFMAs = 4 probe groups of 16 x {hi hi, hi lo, lo hi}.  An
+// MFMA holds the vector issue for 8 of its 16 cycles.  kFat16Tab is the model's table T0: one v_exp behind each of slots 0-7, two
+// short instructions behind each of slots 8-13.  At the nominal costs (v_exp 8, the others 4) that is 8 issue
+// cycles per slot; tools/slot_cost_bench.hip prices v_fma_mixlo/hi at 8, by which slots 10-13 carry 16.  The alternative with ONE
+// mix per slot (exps two per slot behind 0-3, hi pairs behind 4-5, the lo halves behind 6-13) was measured on the kernel and is
+// slower: 5.49 against 5.38 ms per launch (profiles/r13a_matvec_16x16x32/kernel_ab.log), so T0 stays.  The table fixes the ORDER of
+// the chain between the MFMAs, not every position: the compiler sinks the four v_cvt_pk behind slot 9 (they are not pinned).
+// A tile = 16 units u = 8 jb + it (it: the wave's eight 16-row tiles).  During unit u the wave contracts K_u, runs the whole split
+// chain of K_{u+1} and computes the distances of K_{u+2}; the pipeline runs across tiles like k_rbf_fat_apply's.
+//
+// Everything the accuracy rests on is k_rbf_fat_apply's: the tile images of k_pack_tiles (bit for bit), two LDS buffers and one
+// barrier per tile, the chain folds, the alternating block signs (32-row block it >> 1 negated when odd; odd column blocks are
+// packed negated), the column split, the range guard, row blocks and the epilogue.  What differs is the order of the sums inside a
+// tile: one k-step of 32 columns where the 32x32x16 form has two of 16, and one k-step of the distance product instead of two.
+//
+// How the images map onto the 16x16x32 fragments (lane = 16 g + c, g = 0..3):
+//   * a 16-B pack of the probe image holds, for image row (jb, s, h) and one probe, the columns 16 s + 8 (e >> 2) + 4 h + (e & 3),
+//     e = 0..7.  The contraction's B fragment of lane (g, probe c) is the pack of row 4 jb + g, i.e. (s, h) = (g >> 1, g & 1).
+//   * so lane g must hold the kernel entries of exactly those columns: distance MFMA c2 (c2 = 0, 1) takes as its 16 A rows the
+//     columns 16 (m >> 3) + 8 c2 + (m & 7), m = 0..15 ({0..7, 16..23}, then {8..15, 24..31}); its results land on lane (g, row c) in
+//     registers r = 0..3 as columns 16 (g >> 1) + 8 c2 + 4 (g & 1) + r: entry e = 4 c2 + r of the pack order, no lane movement.
+//   * accumulator (it, pg): lane (g, c) holds rows 16 it + 4 g + r, r = 0..3, of probe 16 pg + c: one float4 of the output.
+struct Fat16Tab {
+  int e[8], h[4], m[8];
+};
+// slot (0..13 of the unit BEFORE) behind which each micro-step of a unit's chain runs: exps behind slots 0-7, the four hi pairs
+// behind 8 and 9, the lo halves behind 10-13; no step follows its producer within one slot
+constexpr Fat16Tab kFat16Tab = {{0, 1, 2, 3, 4, 5, 6, 7}, {8, 8, 9, 9}, {10, 11, 10, 11, 12, 13, 12, 13}};
+
+template <int DPAD, bool VEC4>
+__global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restrict__ xs, const float* __restrict__ sq, int64_t n,
+                                                            const float* __restrict__ outputscale, const float* __restrict__ noise,
+                                                            const float* __restrict__ vscale, const float* __restrict__ x,
+                                                            int64_t ldx, float* __restrict__ y, int64_t ldy, int64_t p,
+                                                            const uintx4* __restrict__ pkv, const uintx4* __restrict__ pka,
+                                                            float* __restrict__ part, const int* __restrict__ rangeflag,
+                                                            int64_t ldpart, int64_t row0, int64_t rend) {
+  if (rangeflag && *rangeflag != 0) return;  // f16 range guard: the fp32-distance launch queued behind this one does the work
+  using S = FatSmem<DPAD, 2>;
+  constexpr int KD = S::KD, AROW = S::AROW;
+  static_assert(S::NKD == 2 && 3 * KD <= 32, "the distance product is one k-step of 32");
+  constexpr Fat16Tab T = kFat16Tab;
+  extern __shared__ __attribute__((aligned(16))) char fat_smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lg = lane >> 4;
+  const int64_t i_wave = row0 + (int64_t)blockIdx.x * 512 + wid * 128;
+  const int64_t b0 = (int64_t)blockIdx.y * 64;
+  const int64_t ntile_all = (n + 63) / 64;
+  const int64_t t_first = ntile_all * blockIdx.z / gridDim.z;
+  const int ntl = (int)(ntile_all * (blockIdx.z + 1) / gridDim.z - t_first);
+
+  // (as in k_rbf_fat_apply: keeps the contraction MFMAs in their AGPR form)
+  float agpr_seed = 0.f;
+  asm volatile("; accumulators in AGPRs" : "+a"(agpr_seed));
+
+  auto issue_tile_dma = [&](int tl) {
+    const char* asrc = reinterpret_cast<const char*>(pka) + (t_first + tl) * (int64_t)S::kABytes;
+    const char* vsrc = reinterpret_cast<const char*>(pkv) + ((int64_t)blockIdx.y * ntile_all + t_first + tl) * S::kVBytes;
+    char* dst = fat_smem + (tl & 1) * S::kTile;
+#pragma unroll
+    for (int c = 0; c < (S::kABytes / 1024 + 3) / 4; ++c) {
+      const int piece = wid + 4 * c;
+      if (piece < S::kABytes / 1024) glds16(asrc + piece * 1024 + lane * 16, dst + piece * 1024);
+    }
+#pragma unroll
+    for (int c = 0; c < S::kVBytes / 4096; ++c) glds16(vsrc + (wid + 4 * c) * 1024 + lane * 16, dst + S::kABytes + (wid + 4 * c) * 1024);
+  };
+  if (0 < ntl) issue_tile_dma(0);
+  if (1 < ntl) issue_tile_dma(1);
+
+  // row operand of the distance product, resident: [Bh | Bl | Bh | 0] of [x_i, 1, |x_i|^2] along k = 8 g + e, negated for odd 32-row blocks
+  half8 bi[8];
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    int64_t i = i_wave + it * 16 + l15;
+    if (i >= rend) i = rend - 1;
+    if (i < row0) i = row0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int slot = lg * 8 + e;
+      const int comp = slot / KD, kk = slot % KD;
+      float v = 0.f;
+      if (comp < 3) v = (kk < DPAD) ? xs[i * DPAD + kk] : (kk == DPAD ? 1.f : sq[i]);
+      float hi, lo;
+      split_hi_lo(v, hi, lo);
+      const float w = comp == 1 ? lo : hi;
+      bi[it][e] = (_Float16)(((it >> 1) & 1) ? -w : w);
+    }
+  }
+  floatx4 acc[8][4], mst[8][4];
+#pragma unroll
+  for (int it = 0; it < 8; ++it)
+#pragma unroll
+    for (int pg = 0; pg < 4; ++pg)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[it][pg][r] = 0.f;
+        mst[it][pg][r] = 0.f;
+      }
+  acc[0][0][0] = agpr_seed;
+
+  // ---- fragment reads ---------------------------------------------------------------------------------------------------------
+  auto read_a = [&](half8& a, int buf, int jb, int c2) {  // A rows of distance MFMA c2 of column block jb
+    const _Float16* img = reinterpret_cast<const _Float16*>(fat_smem + buf * S::kTile);
+    a = *reinterpret_cast<const half8*>(img + (jb * 32 + 16 * (l15 >> 3) + 8 * c2 + (l15 & 7)) * AROW + lg * 8);
+  };
+  auto read_v = [&](half8& v, int buf, int jb, int f) {  // probe fragment f = 2 pg + (lo ? 1 : 0) of column block jb
+    v = *reinterpret_cast<const half8*>(fat_smem + buf * S::kTile + S::kABytes + (f & 1) * (8 * S::kVRow) + (jb * 4 + lg) * S::kVRow +
+                                        ((f >> 1) * 16 + l15) * 16);
+  };
+  // ---- the distance MFMA: asm, because its four results must land in VGPRs (v_exp cannot read an accumulation register) while the
+  //      function's intrinsic MFMAs are in AGPR form.  The compiler sees no MFMA here and pads nothing:
+  //      * operands: the row operand is written once before the sweep; the column operand arrives by ds_read_b128, whose s_waitcnt is
+  //        data flow and kept.  The leading s_nop 1 covers a register copy of either that the allocator might put in front of the
+  //        statement (VALU write -> MFMA A/B read).
+  //      * result: a v_mfma_f32_16x16x32_f16 is an 8-pass MFMA; a VALU instruction may read its VGPR result 12 wait states after
+  //        issue at the earliest.  The first reader of distance MFMA c2 (slot 8 + 2 c2 of unit u) is the v_exp behind slot 4 c2 of unit
+  //        u + 1: six (c2 = 0) or eight (c2 = 1) MFMAs of this wave -- which owns the SIMD's matrix pipe, 16 cycles each -- and the
+  //        chain's VALU instructions behind them (one per slot 0-7, two per slot 8-13) lie between: >= 12 instructions by the
+  //        MFMAs and the table alone, and >= 96 cycles.  The prologue has no such schedule and pads by hand. ------------------------------------------------------------------------------------------
+  auto dist16 = [&](floatx4& kd, const half8& a, const half8& b) {
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(kd) : "v"(a), "v"(b));
+  };
+  // ---- one micro-step of the split chain of a unit (entries w[c2][r], e = 4 c2 + r): t = 0 exp2 of entry i; 1 hi pair i; 2 lo half
+  //      of entry i (v_fma_mixlo / mixhi straight into its half of the packed lo register, as k_rbf_fat_apply) -------------------------
+  auto chain = [&](floatx4 (&w)[2], half8& ah, half8& al, unsigned (&lp)[4], const int t, const int i, const bool neg) {
+    if (t == 0) {
+      w[i >> 2][i & 3] = __builtin_amdgcn_exp2f(neg ? -w[i >> 2][i & 3] : w[i >> 2][i & 3]);
+    } else if (t == 1) {
+      const half2v h = {(_Float16)w[i >> 1][(2 * i) & 3], (_Float16)w[i >> 1][(2 * i + 1) & 3]};  // one v_cvt_pk_f16_f32
+      ah[2 * i] = h[0];
+      ah[2 * i + 1] = h[1];
+    } else {
+      const int pr = i >> 1;
+      const half2v h = {ah[2 * pr], ah[2 * pr + 1]};
+      const unsigned hb = __builtin_bit_cast(unsigned, h);
+      if ((i & 1) == 0) {
+        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lp[pr]) : "v"(hb), "v"(w[i >> 2][i & 3]));
+      } else {
+        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lp[pr]) : "v"(hb), "v"(w[i >> 2][i & 3]));
+        const half2v l = __builtin_bit_cast(half2v, lp[pr]);
+        al[2 * pr] = l[0];
+        al[2 * pr + 1] = l[1];
+      }
+    }
+  };
+  auto chain_slot = [&](const int slot, floatx4 (&w)[2], half8& ah, half8& al, unsigned (&lp)[4], const bool neg) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (T.e[i] == slot) chain(w, ah, al, lp, 0, i, neg);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (T.h[i] == slot) chain(w, ah, al, lp, 1, i, neg);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (T.m[i] == slot) chain(w, ah, al, lp, 2, i, neg);
+  };
+
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): my pieces of tiles 0 and 1
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+
+  // ---- pipeline state.  Units are numbered along the sweep: 16 tile + 8 jb + it; everything below is indexed by the unit's number
+  //      mod 2 or mod 4 (16 is a multiple of both: every index is static, nothing is moved). -------------------------------------------
+  floatx4 wr[4][2];     // distances -> kernel entries of a unit: ring of four (contracting u, splitting u + 1, distances of u + 2)
+  half8 ah[2], al[2];   // A fragments (hi, lo) of the unit being contracted and of the next
+  unsigned lp[4];       // packed lo pairs between their mixlo and mixhi step
+  half8 vf[2][8];       // probe fragments [column block][2 pg + lo]
+  half8 aj[2][2];       // column operand [column block][distance MFMA]
+  // prologue (once per sweep): the distances of units 0 and 1 and the whole chain of unit 0, by hand
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2) read_a(aj[0][c2], 0, 0, c2);
+#pragma unroll
+  for (int f = 0; f < 8; ++f) read_v(vf[0][f], 0, 0, f);
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2) dist16(wr[0][c2], aj[0][c2], bi[0]);
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2) dist16(wr[1][c2], aj[0][c2], bi[1]);
+  // no MFMA follows here: the 12 wait states (and more) between the last distance MFMA and the first v_exp, by hand
+  asm volatile("s_nop 15\n\ts_nop 15" : "+v"(wr[0][0]), "+v"(wr[0][1]), "+v"(wr[1][0]), "+v"(wr[1][1]));
+#pragma unroll
+  for (int slot = 0; slot < 14; ++slot) chain_slot(slot, wr[0], ah[0], al[0], lp, false);
+
+  const float sc = outputscale[0];
+  for (int tl = 0; tl < ntl; ++tl) {
+    const int buf = tl & 1;
+    if (tl > 0 && (tl % kChainTiles) == 0) {  // chain fold: masters += accumulators, accumulators restart from zero
+#pragma unroll
+      for (int it = 0; it < 8; ++it)
+#pragma unroll
+        for (int pg = 0; pg < 4; ++pg)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            mst[it][pg][r] += acc[it][pg][r];
+            acc[it][pg][r] = 0.f;
+          }
+    }
+    auto unit = [&](auto uc) {
+      constexpr int u = decltype(uc)::value;
+      constexpr int jb = u >> 3, it = u & 7;
+      constexpr int u1 = (u + 1) & 15, u2 = (u + 2) & 15;  // the unit being split and the one whose distances are computed (may lie in the next tile)
+      constexpr bool neg_n = (((u1 >> 3) + ((u1 & 7) >> 1)) & 1) != 0;
+      // the fragments of column block jb ^ 1 roll in during column block jb: this tile's block 1, or the NEXT tile's block 0 (behind the barrier)
+      const int nbuf = jb == 1 ? buf ^ 1 : buf;
+      if (u == 9 && tl + 2 < ntl) issue_tile_dma(tl + 2);  // (this tile's buffer has been dead since the barrier behind unit 7)
+#pragma unroll
+      for (int slot = 0; slot < 14; ++slot) {
+        __builtin_amdgcn_sched_barrier(0);
+        // slots: hi hi of the four probe groups (0-3), hi lo (4-7), distance 0 (8), lo hi 0 (9), distance 1 (10), lo hi 1-3 (11-13): four
+        // other accumulators between two MFMAs on the same one, and the lo fragment -- finished last -- is read last
+        if (slot == 8 || slot == 10) {
+          const int c2 = (slot - 8) / 2;
+          dist16(wr[(u + 2) & 3][c2], aj[(u2 >> 3) & 1][c2], bi[u2 & 7]);
+        } else {
+          const int m = slot < 8 ? slot : (slot == 9 ? 8 : slot - 2);
+          const int w = m / 4, pg = m % 4;
+          acc[it][pg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w == 2 ? al[u & 1] : ah[u & 1], w == 1 ? vf[jb][pg * 2 + 1] : vf[jb][pg * 2],
+                                                               acc[it][pg], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        chain_slot(slot, wr[(u + 1) & 3], ah[(u + 1) & 1], al[(u + 1) & 1], lp, neg_n);
+        // fragment reads: one probe fragment of the next column block per unit; its column operand in unit it = 3 (first needed by the
+        // distances issued in unit it = 6)
+        if (slot == 2) read_v(vf[jb ^ 1][it], nbuf, jb ^ 1, it);
+        if (it == 3 && (slot == 4 || slot == 5)) read_a(aj[jb ^ 1][slot - 4], nbuf, jb ^ 1, slot - 4);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (u == 7) {
+        // tile tl + 1 (requested a tile ago) has landed for everybody, and everybody is done with this tile's buffer: its last reads
+        // -- probe fragment 7 of column block 1 -- were issued behind slot 2 of this unit.  Every read of the next tile comes later.
+        __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
+    };
+    unit(std::integral_constant<int, 0>{});
+    unit(std::integral_constant<int, 1>{});
+    unit(std::integral_constant<int, 2>{});
+    unit(std::integral_constant<int, 3>{});
+    unit(std::integral_constant<int, 4>{});
+    unit(std::integral_constant<int, 5>{});
+    unit(std::integral_constant<int, 6>{});
+    unit(std::integral_constant<int, 7>{});
+    unit(std::integral_constant<int, 8>{});
+    unit(std::integral_constant<int, 9>{});
+    unit(std::integral_constant<int, 10>{});
+    unit(std::integral_constant<int, 11>{});
+    unit(std::integral_constant<int, 12>{});
+    unit(std::integral_constant<int, 13>{});
+    unit(std::integral_constant<int, 14>{});
+    unit(std::integral_constant<int, 15>{});
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // no LDS-DMA of mine is left in flight
+#pragma unroll
+  for (int it = 0; it < 8; ++it)
+#pragma unroll
+    for (int pg = 0; pg < 4; ++pg)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[it][pg][r] += mst[it][pg][r];
+  const float nz = gridDim.z > 1 ? 0.f : noise[0];
+  float* yout = gridDim.z > 1 ? part + (int64_t)blockIdx.z * p * ldpart : y;
+  const int64_t ldo = gridDim.z > 1 ? ldpart : ldy;
+#pragma unroll
+  for (int pg = 0; pg < 4; ++pg) {
+    const int64_t b = b0 + pg * 16 + l15;
+    if (b >= p) continue;
+    const float sb = sc * vscale[2 * b + 1] * (1.f / 32768.f);
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int64_t i = i_wave + it * 16 + 4 * lg;
+      if (VEC4 && i + 3 < rend) {
+        const float4 xv = *reinterpret_cast<const float4*>(x + b * ldx + i);
+        float4 o;
+        o.x = fmaf(sb, acc[it][pg][0], nz * xv.x);
+        o.y = fmaf(sb, acc[it][pg][1], nz * xv.y);
+        o.z = fmaf(sb, acc[it][pg][2], nz * xv.z);
+        o.w = fmaf(sb, acc[it][pg][3], nz * xv.w);
+        *reinterpret_cast<float4*>(yout + b * ldo + (i - row0)) = o;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (i + e < rend) yout[b * ldo + (i - row0) + e] = fmaf(sb, acc[it][pg][e], nz * x[b * ldx + i + e]);
+      }
+    }
+  }
+}
+
+int rbf_fat_launch(int dpad, int nb, bool vec4, bool wide16, dim3 grid, hipStream_t stream, const RbfMatvecArgs& a) {
   const char* not_built = "fat-wave Gram matvec supports d <= 16 and chunks of 32 or 64 vectors";
   MFX_REQUIRE(nb == 1 || nb == 2, MFX_ERR_UNSUPPORTED, "%s", not_built);
+  if (wide16 && nb == 2 && dpad <= 8) {  // the 16x16x32 form: d <= 8, 64-wide chunks
+    return with_mfma_dpad<8>(dpad, not_built, [&](auto dc) -> int {
+      return with_bool(vec4, [&](auto v4) -> int {
+        constexpr int DPAD = decltype(dc)::value;
+        k_rbf_fat_apply16<DPAD, decltype(v4)::value><<<grid, 256, FatSmem<DPAD, 2>::kTotal, stream>>>(
+            a.xs, a.sq, a.n, a.outputscale, a.noise, a.vscale, a.x, a.ldx, a.y, a.ldy, a.p, static_cast<const uintx4*>(a.pkv),
+            static_cast<const uintx4*>(a.pka), a.part, a.rangeflag, a.ldpart, a.row0, a.rend);
+        MFX_CHECK_LAUNCH();
+        return MFX_OK;
+      });
+    });
+  }
   return with_mfma_dpad<16>(dpad, not_built, [&](auto dc) -> int {
     return with_bool(nb == 2, [&](auto two) -> int {
       return with_bool(vec4, [&](auto v4) -> int {

@@ -1016,17 +1016,21 @@ __global__ __launch_bounds__(256) void k_pack_tiles(const float* __restrict__ xs
   }
 }
 
-// Which kernel runs the chunks (of 64 vectors, or one of at most 32) of an RBF operator with d <= 8 (BASELINE config 4's matvec,
-// config 2's): the fat-wave kernel (mfx_rbf_fat.hip: one wave per SIMD; at 64 vectors 82 % matrix-pipe share, -16 % cycles
-// against h3).  MFX_RBF_FAT=0 runs the same-program
-// kernel k_rbf_mfma_apply_h3 (two waves per SIMD) instead -- the one A/B switch kept, because it reproduces the comparison of
-// DESIGN.md §3.2 and the bit-identity test of the two kernels; h3 also takes every other shape.
-static bool rbf_fat() {
+// Which kernel runs the chunks (of 64 vectors, or one of at most 32) of an RBF operator with d <= 16 (BASELINE config 4's matvec,
+// config 2's): the fat-wave kernels (mfx_rbf_fat.hip: one wave per SIMD; the 32x32x16 form at 64 vectors: 82 % matrix-pipe share,
+// -16 % cycles against h3; the 16x16x32 form: DESIGN.md §3.2).  The one A/B switch kept, MFX_RBF_FAT:
+//   0  the same-program kernel k_rbf_mfma_apply_h3 (two waves per SIMD) for every shape -- reproduces the comparison of DESIGN.md
+//      §3.2 and the bit-identity test of the two kernels; h3 also takes every other shape;
+//   1  k_rbf_fat_apply (v_mfma_f32_32x32x16_f16) for every shape the fat-wave form takes;
+//   2  as 1, but d <= 8 with 64-wide chunks on k_rbf_fat_apply16 (v_mfma_f32_16x16x32_f16).
+constexpr int kRbfFatDefault = 2;
+static int rbf_fat() {
   static const int v = [] {
     const char* e = getenv("MFX_RBF_FAT");
-    return e ? atoi(e) : 1;
+    const int m = e ? atoi(e) : kRbfFatDefault;
+    return m == 0 || m == 1 ? m : 2;
   }();
-  return v != 0;
+  return v;
 }
 
 // vectors per chunk of the pre-packed matvec: 64 from 33 vectors on; DPAD = 32 is built with one probe block per chunk only (the
@@ -1135,9 +1139,9 @@ static int launch_apply_h3k(const mfx_operator* op, const float* xs, const float
       k_pack_tiles<DPAD, NB, KIND><<<dim3((unsigned)pl.ntile, chunks + 1), 256, 0, stream>>>(
           xs, sq, n, vscale, amax_part, (int)vl.gx, x, ldx, p, static_cast<uintx4*>(pk), reinterpret_cast<uintx4*>(pkb + pl.off_a), rangeflag);
       MFX_CHECK_LAUNCH();
-      bool fat = false;  // fat waves (mfx_rbf_fat.hip): four waves of 128 rows, one per SIMD
+      int fat = 0;  // fat waves (mfx_rbf_fat.hip): four waves of 128 rows, one per SIMD
       if constexpr (KIND == MFX_KERNEL_RBF && DPAD <= 16) fat = rbf_fat();
-      if (fat) MFX_TRY(rbf_fat_launch(DPAD, NB, vec4, grid_pk, stream, a));
+      if (fat) MFX_TRY(rbf_fat_launch(DPAD, NB, vec4, fat == 2, grid_pk, stream, a));
       else MFX_TRY((launch_h3<DPAD, NB, KIND, true>(vec4, grid_pk, stream, a)));
       // f16 range guard: the launch below returns at once unless k_pack_tiles raised the flag, in which case the one above did
     }

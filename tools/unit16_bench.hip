@@ -11,6 +11,9 @@
 // Variants (bit mask VAR): 1 chain on; 2 the three products of an accumulator back to back (else product-major: 4 different
 // accumulators between two MFMAs on the same one); 4 LDS fragment reads on; 8 LDS-DMA of the tile images + barrier per tile;
 // 16 the 32x32x16 reference loop of tools/shape_bench.hip (SHAPE 0) instead.
+// The like-for-like row: the 32x32x16 loop (k32) has the fragment reads of k_rbf_fat_apply in every form; with DMA = 1 it also has
+// the kernel's LDS-DMA (21 pieces of 1 KiB per 64-column tile = 8 blocks, requested in block 5) and its one barrier per tile
+// (behind block 4).  That row, not the bare chain row, is what the full 16x16x32 row (VAR 1 + 4 + 8) compares with.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -199,10 +202,11 @@ __device__ __forceinline__ void chain_op(float (&w)[16], half8 (&ah)[2], half8 (
     }
   }
 }
-template <int CHAIN, int ORDER = 0>
-__global__ __launch_bounds__(256, 1) void k32(const _Float16* __restrict__ rnd, float* out, long long* cyc, int blocks) {
+template <int CHAIN, int ORDER = 0, int DMA = 0>
+__global__ __launch_bounds__(256, 1) void k32(const _Float16* __restrict__ rnd, const _Float16* __restrict__ img, float* out, long long* cyc, int blocks) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   for (int i = tid; i < 65536 / 2; i += 256) {
     const _Float16 v = rnd[(blockIdx.x * 977 + i) % (1 << 20)];
     const int piece = (i / 512) % 12;
@@ -237,6 +241,15 @@ __global__ __launch_bounds__(256, 1) void k32(const _Float16* __restrict__ rnd, 
     const char* vb = base + (b4 & 3) * 12288;
     auto body = [&](auto bc) {
       constexpr int b = decltype(bc)::value;
+      if (DMA && b == 1 && (b4 & 1)) {
+        // block 5 of the tile: request the tile after next -- 5 + 16 pieces of 1 KiB, piece w, w + 4, ... by wave w -- into one of two
+        // buffers BEHIND the 48 KiB the fragment reads use (the model's reads keep their data; the kernel's buffer is dead by then)
+        const char* src = reinterpret_cast<const char*>(img) + ((size_t)(((b4 >> 1) * 131 + blockIdx.x * 17) & 63)) * 20480;
+        char* dst = smem + 49152 + ((b4 >> 1) & 1) * 21504;
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+          if (wid + 4 * c < 21) glds16(src + ((wid + 4 * c) % 20) * 1024 + lane * 16, dst + (wid + 4 * c) * 1024);
+      }
 #pragma unroll
       for (int slot = 0; slot < 14; ++slot) {
         __builtin_amdgcn_sched_barrier(0);
@@ -271,6 +284,11 @@ __global__ __launch_bounds__(256, 1) void k32(const _Float16* __restrict__ rnd, 
         if ((b & 3) == 1 && slot < 2) aj[slot] = *reinterpret_cast<const half8*>(vb + (9 + slot) * 1024);
       }
       __builtin_amdgcn_sched_barrier(0);
+      if (DMA && b == 0 && (b4 & 1)) {  // behind block 4 of the tile, as the kernel
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
       ahc[0] = ahn[0]; ahc[1] = ahn[1];
       alc[0] = aln[0]; alc[1] = aln[1];
 #pragma unroll
@@ -282,6 +300,7 @@ __global__ __launch_bounds__(256, 1) void k32(const _Float16* __restrict__ rnd, 
     body(std::integral_constant<int, 3>{});
   }
   const long long t1 = __builtin_readcyclecounter();
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   if (tid == 0) cyc[blockIdx.x] = t1 - t0;
   float s = 0;
   for (int q = 0; q < 8; ++q)
@@ -327,11 +346,13 @@ void run16(const char* name, const _Float16* rnd, float* d) {
   hipFuncSetAttribute(reinterpret_cast<const void*>(k16<VAR>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
   time_it(name, [&](long long* cyc, int div) { k16<VAR><<<256, 256, 40960>>>(rnd, g_img, d, cyc, tiles / div); }, tiles * 8);
 }
-template <int CHAIN, int ORDER = 0>
+template <int CHAIN, int ORDER = 0, int DMA = 0>
 void run32(const char* name, const _Float16* rnd, float* d) {
+  extern _Float16* g_img;
   const int blocks = 400000;
-  hipFuncSetAttribute(reinterpret_cast<const void*>(k32<CHAIN, ORDER>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-  time_it(name, [&](long long* cyc, int div) { k32<CHAIN, ORDER><<<256, 256, 65536>>>(rnd, d, cyc, blocks / div); }, blocks);
+  constexpr int kSmem = DMA ? 49152 + 2 * 21504 : 65536;
+  hipFuncSetAttribute(reinterpret_cast<const void*>(k32<CHAIN, ORDER, DMA>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
+  time_it(name, [&](long long* cyc, int div) { k32<CHAIN, ORDER, DMA><<<256, 256, kSmem>>>(rnd, g_img, d, cyc, blocks / div); }, blocks);
 }
 
 int main() {
@@ -355,7 +376,8 @@ int main() {
     hipMemcpy(g_img, hi, m * 2, hipMemcpyHostToDevice);
   }
   for (int rep = 0; rep < 2; ++rep) {
-    run32<1>("32x32x16 + chain (shape_bench SHAPE 0)", rnd, d);
+    run32<1>("32x32x16 + chain + LDS reads (shape_bench SHAPE 0)", rnd, d);
+    run32<1, 0, 1>("32x32x16 + chain + LDS reads + DMA/barrier  [like for like]", rnd, d);
     run32<0>("32x32x16 MFMAs only", rnd, d);
     run32<1, 1>("32x32x16 + chain, six in a row per accumulator", rnd, d);
     run32<1, 2>("32x32x16 + chain, product-major", rnd, d);
