@@ -26,6 +26,11 @@
 //   k_jac_tiles     out[b][i][:] = J_i v_b: the forward tangent of k_ggn_tiles, written per sample; no workspace, no sum
 //   k_jac_t_tiles   the backward accumulation started at g_L = U[b][i][:], per-workgroup partial sums as above
 //   k_jac_t_reduce  y = sum over workgroups, in index order
+//
+// The exact diagonal sum_i diag(J_i^T H_i J_i) (mfx_ggn_diag: the diagonal-Laplace baseline) is a fourth pass over the same tape:
+//
+//   k_ggn_diag_tiles   the backward sweep once per class, squared where it is produced; the waves of a workgroup share the classes
+//                      instead of holding probes; partial sums as above, added by k_jac_t_reduce
 #include "mfx_internal.h"
 
 namespace mfx {
@@ -382,6 +387,157 @@ __global__ __launch_bounds__(256) void k_jac_t_reduce(const T* __restrict__ part
   y[b * ldy + i] = acc;
 }
 
+// ---- the exact diagonal sum_i diag(J_i^T H_i J_i) (mfx_ggn_diag); include/mfx.h has the formulas ----
+// The steps of k_ggn_diag_tiles that the kernels above spell out in place are helpers here: the staging of a squared tape chunk, one
+// layer of the backward sweep, and the fixed-order sum over the waves of a workgroup.
+
+// D = max(m1 - m2^2, 0), the product rounded on its own: contracted to fma(-m2, m2, m1) it is not 0 where m1 = round(m2 * m2) (c = 1),
+// and hipcc contracts across statements (and through __fmul_rn) unless the expression says otherwise
+template <typename T>
+__device__ __forceinline__ T ggn_variance(T m1, T m2) {
+#pragma clang fp contract(off)
+  const T d = m1 - m2 * m2;
+  return d > T(0) ? d : T(0);  // a variance under p: round-off below 0 is cut off
+}
+
+// aT[kk][i] = M[i0 + i][k0 + kk]^2 for the nv samples of the tile and the units of the chunk, 0 elsewhere: ggn_stage with a square
+template <typename T>
+__device__ __forceinline__ void ggn_stage_sq(GgnLds<T>& sm, const T* __restrict__ M, int width, int k0, int64_t i0, int nv) {
+  for (int e = threadIdx.x; e < kGgnW * kGgnTS; e += blockDim.x) {
+    const int kk = e & (kGgnW - 1), i = e / kGgnW;
+    const int k = k0 + kk;
+    const T m = (i < nv && k < width) ? M[(i0 + i) * width + k] : T(0);
+    sm.aT[kk][i] = m * m;
+  }
+}
+
+// One layer down, for the cotangents s of wave g (lane j = unit j of layer l on entry, of layer l - 1 on return):
+// s <- dact_{l-1} o (W_l s).  The cotangents pass through the wave's own tb, the slopes of layer l - 1 are staged once for the
+// workgroup (0 past the end of the tape).  Every wave of the workgroup calls it, with the same l: it holds two barriers.
+template <typename T>
+__device__ __forceinline__ void ggn_down(GgnLds<T>& sm, const GgnArgs<T>& a, int l, int g, int j, int64_t i0, int nv, T (&s)[kGgnTS]) {
+  constexpr int TS = kGgnTS;
+  const int wi = a.w[l - 1], wo = a.w[l];
+  __syncthreads();  // tb and aT are free
+  if (j < wo) {
+#pragma unroll
+    for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
+  }
+  ggn_stage<T>(sm, a.dact[l - 1], wi, 0, i0, nv);
+  __syncthreads();
+  if (j < wi) {
+    const T* __restrict__ Wrow = a.theta + a.off[l] + wo + (int64_t)j * wo;
+#pragma unroll
+    for (int i = 0; i < TS; ++i) s[i] = T(0);
+    for (int m = 0; m < wo; ++m) {
+      const T wt = Wrow[m];
+#pragma unroll
+      for (int i = 0; i < TS; ++i) s[i] += sm.tb[g][m][i] * wt;
+    }
+#pragma unroll
+    for (int i = 0; i < TS; ++i) s[i] = sm.aT[j][i] * s[i];
+  }
+}
+
+// v[i] <- sum over the waves h = 0, 1, ... of the workgroup of lane j's v[i], in that order: every wave ends with the same bits
+template <typename T>
+__device__ __forceinline__ void ggn_sum_waves(GgnLds<T>& sm, int g, int j, T (&v)[kGgnTS]) {
+  constexpr int G = GgnGroup<T>::value, TS = kGgnTS;
+  __syncthreads();  // tb is free
+#pragma unroll
+  for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = v[i];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < TS; ++i) {
+    T acc = sm.tb[0][j][i];
+#pragma unroll
+    for (int h = 1; h < G; ++h) acc += sm.tb[h][j][i];
+    v[i] = acc;
+  }
+}
+
+// part[workgroup][:] = sum over the workgroup's samples of diag(J_i^T H_i J_i).  The geometry of k_ggn_tiles: tiles of 32 samples,
+// lane j = unit j of the layer at hand, the waves of the workgroup (4 in fp32, 2 in fp64) in the place of its probes.  Row o of J_i
+// is the backward sweep started at g_L = e_o; the classes are dealt to the waves round robin (wave g takes o = g, g + G, ...).
+// Layer-outer: for the layer l whose entries are being produced every class is swept from L down to l again, so that only the two
+// moments of that layer live in registers (m1 = sum_o p_o g^2, m2 = sum_o p_o g, 2 x 32 values) -- L (L - 1) / 2 layer steps per
+// class instead of L - 1, at widths <= 64.  Then the moments are added over the waves in wave order, D = max(m1 - m2^2, 0) (m1 for
+// MSE), and y_b_l += D, y_W_l += a_{l-1}^2 D^T with the squared inputs staged chunk by chunk; the rows of a chunk are dealt to the
+// waves, which all hold the same D.
+template <typename T>
+__global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_diag_tiles(GgnArgs<T> a, T* __restrict__ part) {
+  constexpr int G = GgnGroup<T>::value, TS = kGgnTS, W = kGgnW;
+  __shared__ __attribute__((aligned(16))) GgnLds<T> sm;
+  __shared__ T po[G][TS];  // per wave: p_o of the class it is sweeping, for the samples of the tile
+  const int j = threadIdx.x & 63, g = threadIdx.x >> 6;
+  T* __restrict__ out = part + (int64_t)blockIdx.x * a.P;
+  const int L = a.L, c = a.w[L];
+  const bool ce = a.loss == MFX_GGN_CROSS_ENTROPY;
+  T s[TS];   // this unit's cotangents of the class at hand
+  T m1[TS];  // sum_o p_o g^2 over this wave's classes, then over all; then D
+  T m2[TS];  // sum_o p_o g (cross-entropy)
+
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const bool first = tile == (int64_t)blockIdx.x;
+    const int64_t i0 = tile * TS;
+    const int nv = a.N - i0 < TS ? (int)(a.N - i0) : TS;
+    for (int l = L; l >= 1; --l) {
+      const int wi = a.w[l - 1], wo = a.w[l];
+#pragma unroll
+      for (int i = 0; i < TS; ++i) m1[i] = m2[i] = T(0);
+      for (int o0 = 0; o0 < c; o0 += G) {  // every wave makes every round, with or without a class: ggn_down holds barriers
+        const int o = o0 + g;
+        const bool has = o < c;  // wave-uniform
+        if (j < TS) {  // p_o of the tile's samples (1 for MSE); 0 past the end of the tape: such samples contribute nothing
+          const bool in = has && j < nv;
+          po[g][j] = in ? (ce ? a.prob[(i0 + j) * c + o] : T(1)) : T(0);
+        }
+        const T e = (has && j == o) ? T(1) : T(0);
+#pragma unroll
+        for (int i = 0; i < TS; ++i) s[i] = e;
+        for (int lp = L; lp > l; --lp) ggn_down<T>(sm, a, lp, g, j, i0, nv, s);
+        __syncthreads();  // po of this round is written (a wave reads its own row, after its own reads of the round before)
+        if (has && j < wo) {
+#pragma unroll
+          for (int i = 0; i < TS; ++i) {
+            const T ps = po[g][i] * s[i];
+            m2[i] += ps;
+            m1[i] += ps * s[i];
+          }
+        }
+      }
+      ggn_sum_waves<T>(sm, g, j, m1);
+      if (ce) {
+        ggn_sum_waves<T>(sm, g, j, m2);
+#pragma unroll
+        for (int i = 0; i < TS; ++i) m1[i] = ggn_variance(m1[i], m2[i]);
+      }
+      if (g == 0 && j < wo) {
+        T sb = T(0);
+#pragma unroll
+        for (int i = 0; i < TS; ++i) sb += m1[i];
+        ggn_accumulate<T>(out, a.off[l] + j, sb, first);
+      }
+      for (int k0 = 0; k0 < wi; k0 += W) {
+        __syncthreads();  // the chunk before this one (or the sums over the waves) has been consumed
+        ggn_stage_sq<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        __syncthreads();
+        if (j < wo) {
+          const int kc = wi - k0 < W ? wi - k0 : W;
+          const int64_t base = a.off[l] + wo + (int64_t)k0 * wo + j;
+          for (int kk = g; kk < kc; kk += G) {
+            T acc = T(0);
+#pragma unroll
+            for (int i = 0; i < TS; ++i) acc += sm.aT[kk][i] * m1[i];
+            ggn_accumulate<T>(out, base + (int64_t)kk * wo, acc, first);
+          }
+        }
+      }
+    }
+    __syncthreads();  // the next tile stages into aT and writes tb
+  }
+}
+
 // partial[blockIdx.x] = this workgroup's share of sum_b L_b . R_b (fp64 sums, fixed order)
 template <typename T>
 __global__ __launch_bounds__(256) void k_ggn_dot(const T* __restrict__ L, int64_t ldl, const T* __restrict__ R, int64_t ldr, int64_t batch,
@@ -590,11 +746,54 @@ static int jac_t_apply_t(const mfx_ggn_net* net, const T* U, int64_t p, T* Y, in
   return MFX_OK;
 }
 
+// ---- the exact diagonal of the GGN (mfx_ggn_diag): one value per parameter, so not an operator application ----
+static const char* const kDiagWho = "GGN diagonal";
+
+static int diag_check(const mfx_ggn_net* net, int dtype) {
+  MFX_REQUIRE(net, MFX_ERR_INVALID, "GGN diagonal: net is NULL");
+  MFX_TRY(ggn_check_net(net, kDiagWho));
+  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "GGN diagonal: unknown loss %d", net->loss);
+  MFX_REQUIRE(net->loss != MFX_GGN_CROSS_ENTROPY || net->prob, MFX_ERR_INVALID, "GGN diagonal: prob is NULL (cross-entropy)");
+  MFX_TRY(ggn_check_limits(net, kDiagWho));
+  MFX_REQUIRE(dtype == MFX_F32 || dtype == MFX_F64, MFX_ERR_UNSUPPORTED, "GGN diagonal: unsupported dtype %d", dtype);
+  return MFX_OK;
+}
+
+static int64_t diag_bytes(const mfx_ggn_net* net, int dtype) {  // part[workgroup][P]
+  return ggn_blocks(net->nsamples) * ggn_params(net) * (int64_t)dtype_size(dtype);
+}
+
+template <typename T>
+static int diag_t(const mfx_ggn_net* net, T* diag, T* ws, hipStream_t stream) {
+  const GgnArgs<T> a = ggn_args<T>(net);
+  const int64_t nblk = ggn_blocks(a.N);
+  k_ggn_diag_tiles<T><<<dim3((unsigned)nblk), 64 * GgnGroup<T>::value, 0, stream>>>(a, ws);
+  MFX_CHECK_LAUNCH();
+  k_jac_t_reduce<T><<<dim3((unsigned)((a.P + 255) / 256), 1), 256, 0, stream>>>(ws, nblk, a.P, diag, a.P);  // one "vector"
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
 }  // namespace mfx
 
 using namespace mfx;
 
 extern "C" {
+
+int64_t mfx_ggn_diag_workspace_bytes(const mfx_ggn_net* net, int dtype) {
+  if (diag_check(net, dtype) != MFX_OK) return -1;
+  return align_up(diag_bytes(net, dtype), 256);
+}
+
+int mfx_ggn_diag(const mfx_ggn_net* net, int dtype, void* diag, void* ws, int64_t ws_bytes, void* stream) {
+  MFX_TRY(diag_check(net, dtype));
+  MFX_REQUIRE(diag, MFX_ERR_INVALID, "GGN diagonal: diag is NULL");
+  const int64_t need = diag_bytes(net, dtype);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "GGN diagonal: workspace too small: need %lld bytes", (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == MFX_F32) return diag_t<float>(net, (float*)diag, (float*)ws, s);
+  return diag_t<double>(net, (double*)diag, (double*)ws, s);
+}
 
 int64_t mfx_mlp_jac_workspace_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {
   if (jac_check(net, dtype, p) != MFX_OK) return -1;

@@ -209,6 +209,8 @@ SYMBOLS = {
     "mfx_mlp_jac_workspace_bytes": (_I64, [_NETP, _I, _I64]),
     "mfx_mlp_jac_apply": (_I, [_NETP, _I, _P, _I64, _I64, _P, _P]),
     "mfx_mlp_jac_t_apply": (_I, [_NETP, _I, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "mfx_ggn_diag_workspace_bytes": (_I64, [_NETP, _I]),
+    "mfx_ggn_diag": (_I, [_NETP, _I, _P, _P, _I64, _P]),
     "mfx_timing_enable": (_I, [_I]),
     "mfx_timing_reset": (_I, []),
     "mfx_timing_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -717,6 +717,22 @@ class GgnMlpOp(NativeOp):
         """The network Jacobian at the operator's own samples, over its own tape: the tensors are shared, nothing is recomputed."""
         return MlpJacobian._over(self.widths, self.activation, self.theta, self.tape)
 
+    def diagonal(self, alpha=None):
+        """The exact diagonal sum_i diag(J_i^T H_i J_i) over the operator's own tape, (P,), in one fused HIP pass (mfx_ggn_diag: c
+        backward sweeps per sample, squared where they are produced; the reference's exact_diagonal takes N c^2 gradients).  Entrywise
+        >= 0.  ``alpha`` (a tensor or a number) is added with a torch add, so the result is differentiable in it; the diagonal
+        itself is a constant."""
+        _lib.require_device(self.theta)
+        lib, code, dev = _lib.get(), _lib.dtype_code(self.theta.dtype), self.theta.device
+        need = int(lib.mfx_ggn_diag_workspace_bytes(C.byref(self.net), code))
+        if need < 0:  # the query refuses what the call would: the call names the reason and the code
+            _lib.check(lib.mfx_ggn_diag(C.byref(self.net), code, None, None, 0, None))
+        ws = _lib.scratch(need, dev)
+        diag = torch.empty(self.n, dtype=self.theta.dtype, device=dev)
+        with _lib.busy(ws):
+            _lib.check(lib.mfx_ggn_diag(C.byref(self.net), code, _lib.ptr(diag), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return diag if alpha is None else diag + alpha
+
     def constrain(self, alpha):
         return (alpha.reshape(1),)
 

@@ -12,7 +12,10 @@ Predictive (:206-215, 549-683): N(f(x*; theta), J* (GGN + alpha I)^-1 J*^T) at t
 the matrix-free ``predictive_cov_operator`` (``operators.MlpJacobian`` for J* and J*^T, a batched CG on the bound GGN operator in
 between), ``logpdf_cholesky`` / ``logpdf_eigh``, ``predictive_posterior_loglikelihood`` and ``predictive_logit_sampler``.
 
-Conv nets, ViTs, ``hutchinson_diagonal`` / ``bnn_baselines`` and data loaders are not here.
+Diagonal baseline (:349-358, 433-474): ``ggn_diag`` (dense) and ``callibration_loss_diagonal`` on the Hutchinson or the exact diagonal
+of the GGN; ``hutchinson_diagonal``, ``exact_diagonal`` and ``last_layer_ggn`` are in ``util/bnn_baselines.py``.
+
+Conv nets, ViTs and data loaders are not here.
 """
 
 from __future__ import annotations
@@ -205,6 +208,16 @@ def ggn_full(*, loss_single, model_fun, param_unflatten):
     return ggn_fun
 
 
+def ggn_diag(*, loss_single, model_fun, param_unflatten):
+    """util/bnn_util.py:349-358, the dense diagonal baseline: diag(diag(ggn_full)), the shift included as in the reference"""
+    ggn_fun_full = ggn_full(loss_single=loss_single, model_fun=model_fun, param_unflatten=param_unflatten)
+
+    def ggn_fun(alpha, variables, x_train, y_train):
+        return torch.diag(torch.diagonal(ggn_fun_full(alpha, variables, x_train, y_train)))
+
+    return ggn_fun
+
+
 def ggn_operator(theta, x_train, widths, *, activation="tanh", loss="cross_entropy"):
     """The matrix-free counterpart of ``ggn_full`` for an MLP: ``op(v, alpha)`` = (sum_i J_i^T H_i J_i + alpha I) v as one fused HIP
     pass over a tape built once here (theta and x_train fixed; with one-hot labels the labels do not enter either Hessian)."""
@@ -296,6 +309,50 @@ def callibration_loss(model_apply, unflatten, hyperparam_unconstrain, n_params, 
         bound = op.bind(alpha) if operator is None else operator(op, alpha)
         logdet_fun = solver_logdet_slq_implicit(lanczos_rank=10, slq_num_samples=10, slq_num_batches=1, N=n_params, x_like=params_vec)
         logdet = logdet_fun(bound, key)
+        log_prior = torch.log(alpha) * n_params - alpha * torch.dot(params_vec, params_vec)
+        return -(log_prior - logdet)
+
+    return loss_fn
+
+
+def callibration_loss_diagonal(model_apply, unflatten, hyperparam_unconstrain, hutchinson_samples, num_levels, n_params, *,
+                               loss="cross_entropy", exact=False, key=0, operator=None):
+    """util/bnn_util.py:433-474, the diagonal-Laplace counterpart of ``callibration_loss``:
+
+        -(log(alpha) n_params - alpha |theta|^2 - sum log(diag + alpha)),     entries of diag below 1e-4 set to 0
+
+    with diag the diagonal of the GGN WITHOUT the shift: ``bnn_baselines.hutchinson_diagonal`` ("serial", ``hutchinson_samples``
+    probes on each of ``num_levels`` levels; ``key`` an integer seed -- the reference fixes PRNGKey(0) -- or the draws themselves,
+    (num_levels, hutchinson_samples, n_params)) over the operator bound to the shift 0, or, ``exact=True``, ``op.diagonal()`` (what
+    the reference keeps commented out: N c^2 gradients there, one kernel here).  ``loss(log_alpha, params_vec, img, label)`` is
+    differentiable in ``log_alpha`` only, through the explicit ``+ alpha``: the diagonal is a constant.  ``model_apply``,
+    ``unflatten`` and the cache of the operator as in ``callibration_loss`` (the diagonal is kept with the operator: it does not
+    depend on alpha); ``operator=`` fixes what the probes are applied to (``lambda tape_op, zero: batched matvec``)."""
+    from .bnn_baselines import hutchinson_diagonal  # (bnn_baselines imports this module)
+
+    cache = {}
+
+    def loss_fn(log_alpha, params_vec, img, label):
+        if params_vec.requires_grad or img.requires_grad:
+            raise NotImplementedError("callibration_loss_diagonal differentiates log_alpha only: theta and the data are fixed (their "
+                                      "gradients need third derivatives of the network, which the reference never takes)")
+        alpha = hyperparam_unconstrain(log_alpha)
+        if cache.get("theta") is not params_vec or cache.get("img") is not img:
+            d_in = img.reshape(img.shape[0], -1).shape[1]
+            cache["theta"], cache["img"] = params_vec, img
+            op = ggn_operator(params_vec, img, model_apply.widths(d_in), activation=model_apply.activation, loss=loss)
+            with torch.no_grad():
+                if exact:
+                    diag = op.diagonal()
+                else:
+                    zero = torch.zeros((), dtype=params_vec.dtype, device=params_vec.device)  # the shift stays out of the estimate
+                    bound = op.bind(zero) if operator is None else operator(op, zero)
+                    diag = hutchinson_diagonal(bound, params_vec, hutchinson_samples, key, num_levels=num_levels,
+                                               computation_type="serial")
+            cache["op"], cache["diag"] = op, diag
+        diag = cache["diag"]
+        diag = torch.where(diag < 1e-4, torch.zeros_like(diag), diag)
+        logdet = torch.log(diag + alpha).sum()
         log_prior = torch.log(alpha) * n_params - alpha * torch.dot(params_vec, params_vec)
         return -(log_prior - logdet)
 

@@ -29,7 +29,8 @@ extern "C" {
 #define MFX_VERSION 201 /* 201: + mfx_comm_rccl_count.  MFX_OP_STENCIL and the st_* fields at the end of mfx_operator are additive (no
                            bump, as for mfx_op_grads.x): callers that zero-fill the descriptor never select them.  MFX_OP_GGN is
                            additive too: its data travels through the existing `ctx` pointer, no struct grows.  So are the three
-                           mfx_mlp_jac_* entry points: new symbols, no struct or existing signature changes */
+                           mfx_mlp_jac_* entry points: new symbols, no struct or existing signature changes.  So are
+                           mfx_ggn_diag and mfx_ggn_diag_workspace_bytes: new symbols again, no bump */
 
 enum { MFX_F32 = 0, MFX_F64 = 1 };
 enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4, MFX_OP_GGN = 5 };
@@ -138,6 +139,27 @@ int64_t mfx_mlp_jac_workspace_bytes(const mfx_ggn_net* net, int dtype, int64_t p
 int mfx_mlp_jac_apply(const mfx_ggn_net* net, int dtype, const void* V, int64_t ldv, int64_t p, void* out, void* stream);
 int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_t p, void* Y, int64_t ldy, void* ws, int64_t ws_bytes,
                         void* stream);
+
+/* The exact diagonal of the same GGN without the shift, diag = sum_i diag(J_i^T H_i J_i) (P values in the theta layout): the
+ * diagonal-Laplace baseline the full-GGN calibration is compared against (util/bnn_baselines.py:10-82 exact_diagonal, which takes
+ * N c^2 gradients; util/bnn_util.py:433-474 callibration_loss_diagonal).  It takes the net directly and reads `loss`, and `prob` for
+ * cross-entropy only.  For sample i and class o let g_L = e_o and, going down, g_{l-1} = dact_{l-1} o (W_l g_l): row o of J_i has
+ * the entry g_{l,m} at bias (l, m) and a_{l-1,k} g_{l,m} at kernel (l, k, m).  With
+ *   D_il[m] = max(sum_o p_o g_{l,m}^2 - (sum_o p_o g_{l,m})^2, 0)   (MFX_GGN_CROSS_ENTROPY, H = diag(p) - p p^T)
+ *   D_il[m] = sum_o g_{l,m}^2                                       (MFX_GGN_MSE, H = I)
+ *   diag[bias (l, m)] = sum_i D_il[m]          diag[kernel (l, k, m)] = sum_i a_{i,l-1,k}^2 D_il[m]
+ * The clamp is part of the contract: D is a variance under p, which round-off can push below 0 where the softmax is saturated;
+ * the result is >= 0 entrywise (and exactly 0 for c = 1 with cross-entropy).  `diag` is written, not accumulated, and carries no
+ * shift: the caller adds alpha.  Asynchronous on `stream`.  The sum over samples as for the operator: per-workgroup partial sums
+ * in the workspace (written before they are read), then one pass that adds them in index order; no atomics, bit-identical from
+ * run to run, independent of what the workspace held.
+ *   mfx_ggn_diag_workspace_bytes   min(ceil(N / 32), 64) P values, rounded up to 256 bytes (host arithmetic); -1 for a net or a
+ *                                  dtype the call would refuse.
+ * Refused before any launch.  MFX_ERR_INVALID: net, diag, theta, act[l] (l < L), dact[l] (1 <= l < L) or prob (cross-entropy)
+ * NULL; an unknown loss; nlayers outside 1..MFX_GGN_MAX_LAYERS; a width < 1; nsamples < 1.  MFX_ERR_UNSUPPORTED: width[0] > 65536
+ * or width[l] > 64 for l >= 1; a dtype other than MFX_F32 / MFX_F64.  MFX_ERR_WORKSPACE: ws NULL or ws_bytes too small. */
+int64_t mfx_ggn_diag_workspace_bytes(const mfx_ggn_net* net, int dtype);
+int mfx_ggn_diag(const mfx_ggn_net* net, int dtype, void* diag, void* ws, int64_t ws_bytes, void* stream);
 
 /* Operator descriptor: a POD of borrowed pointers, valid for the duration of one call.
  * Replaces the reference's `matvec(v, *params)` closures:
