@@ -1619,10 +1619,11 @@ static const OpKind kCallbackKind = {callback_check, nullptr, nullptr, {op_apply
                                      "row sharding needs a native operator", false, nullptr};
 
 // ---- the table and the generic functions every driver goes through -----------------------------------
-const OpKind *stencil_kind(), *ggn_kind();  // mfx_stencil.hip, mfx_ggn.hip
+const OpKind *stencil_kind(), *ggn_kind(), *precond_kind();  // mfx_stencil.hip, mfx_ggn.hip, mfx_lowrank.hip
 
 const OpKind* op_kind(const mfx_operator* op) {
-  static const OpKind* const kinds[] = {&kDenseKind, &kCsrKind, &kGramKind, &kCallbackKind, stencil_kind(), ggn_kind()};  // by MFX_OP_*
+  static const OpKind* const kinds[] = {&kDenseKind, &kCsrKind, &kGramKind, &kCallbackKind, stencil_kind(), ggn_kind(),
+                                       precond_kind()};  // by MFX_OP_*
   return op->kind >= 0 && op->kind < (int)(sizeof(kinds) / sizeof(kinds[0])) ? kinds[op->kind] : nullptr;
 }
 

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFX_LIBRARY_PATH") or os.path.join(_HERE, "libmfx.so")  # override: A/B builds
 
 MFX_F32, MFX_F64 = 0, 1
-OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL, OP_GGN = 0, 1, 2, 3, 4, 5
+OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL, OP_GGN, OP_PRECOND = 0, 1, 2, 3, 4, 5, 6
 STENCIL_HEAT, STENCIL_HEAT2, STENCIL_WAVE = 0, 1, 2
 BOUNDARY_DIRICHLET, BOUNDARY_NEUMANN = 0, 1
 GGN_CROSS_ENTROPY, GGN_MSE = 0, 1
@@ -77,6 +77,18 @@ class Operator(C.Structure):
         ("st_form", C.c_int32),
         ("st_boundary", C.c_int32),
         ("st_w", C.c_double * 9),
+    ]
+
+
+class Precond(C.Structure):
+    """mirror of ``struct mfx_precond``: what ``Operator.ctx`` points at for ``OP_PRECOND`` (a host struct)."""
+
+    _fields_ = [
+        ("pc_inner", C.c_void_p),  # const mfx_operator* (host): ctypes.addressof of the inner descriptor, which the owner keeps alive
+        ("pc_lt", C.c_void_p),
+        ("pc_mid", C.c_void_p),
+        ("pc_scale", C.c_void_p),
+        ("pc_rank", C.c_int64),
     ]
 
 
@@ -189,6 +201,8 @@ SYMBOLS = {
     ),
     "mfx_pcg_solve_reortho": (_I, [_OPP, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _P]),
     "mfx_precond_apply": (_I, [_I, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "mfx_lowrank_workspace_bytes": (_I64, [_I, _I64, _I64, _I64]),
+    "mfx_lowrank_apply": (_I, [_I, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
     "mfx_mbcg_workspace_bytes": (_I64, [_OPP, _I64, _I64, _I64, _I64]),
     "mfx_mbcg_solve": (
         _I,

@@ -97,6 +97,16 @@ class _NoGrad(torch.autograd.Function):
         raise RuntimeError
 
 
+class _NoGradInvSqrt(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pre, v, s):
+        return pre._apply_inv_sqrt(v, s)
+
+    @staticmethod
+    def backward(ctx, _g):
+        raise RuntimeError
+
+
 class Preconditioner:
     """solve(v, s) = (s I + L L^T)^{-1} v by the Woodbury identity (low_rank.py:31-43)."""
 
@@ -106,6 +116,48 @@ class Preconditioner:
         self.rank, self.n = self.lt.shape
         assert self.rank <= self.n, (self.n, self.rank)  # tall, not wide (low_rank.py:26-29)
         self._gram = None
+        self._eig = None
+
+    def inv_sqrt(self, s):
+        """P^-1/2 = scale (I - L mid L^T) for P = s I + L L^T -> (mid (rank, rank) in the dtype of L, scale (1,) = s^-1/2).  With
+        L^T L = V diag(g) V^T (fp64, the Gram matrix ``minv`` caches, g clamped at 0): mid = V diag(c) V^T,
+        c_i = 1 / ((s + g_i) + sqrt(s (s + g_i))) -- the form without cancellation as g_i -> 0.  Not differentiable (``_NoGrad``
+        convention); works on CPU tensors like ``minv``."""
+        with torch.no_grad():
+            if self._gram is None:
+                self._gram = (self.lt @ self.lt.t()).double()
+            if self._eig is None:
+                gamma, vecs = torch.linalg.eigh(self._gram)
+                self._eig = (gamma.clamp_min(0.0), vecs)
+            gamma, vecs = self._eig
+            s = torch.as_tensor(s, dtype=torch.float64, device=self.lt.device).detach().reshape(1)
+            c = 1.0 / ((s + gamma) + torch.sqrt(s * (s + gamma)))
+            mid = (vecs * c) @ vecs.t()
+            mid = 0.5 * (mid + mid.t())
+            return mid.to(self.lt.dtype).contiguous(), torch.rsqrt(s).to(self.lt.dtype).contiguous()
+
+    def _apply_inv_sqrt(self, v, s):
+        V = (v if v.dim() == 2 else v[None]).detach().contiguous()
+        p, n = V.shape
+        if n != self.n or V.dtype != self.lt.dtype:
+            raise ValueError(f"preconditioner of size {self.n} ({self.lt.dtype}) applied to {tuple(v.shape)} ({v.dtype})")
+        mid, scale = self.inv_sqrt(s)
+        if not V.is_cuda:  # host tensors (tests of the formula): the same expression in torch
+            z = scale * (V - ((V @ self.lt.t()) @ mid) @ self.lt)
+            return z if v.dim() == 2 else z[0]
+        lib, code = _lib.get(), _lib.dtype_code(V.dtype)
+        ws = _lib.scratch(int(lib.mfx_lowrank_workspace_bytes(code, n, self.rank, p)), V.device)
+        z = torch.empty_like(V)
+        _lib.check(lib.mfx_lowrank_apply(code, n, self.rank, _lib.ptr(self.lt), _lib.ptr(mid), _lib.ptr(scale), _lib.ptr(V), n,
+                                         _lib.ptr(z), n, p, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(V.device)))
+        return z if v.dim() == 2 else z[0]
+
+    def apply_inv_sqrt(self, v, s):
+        """P^-1/2 v on (n,) or (p, n) by ``mfx_lowrank_apply``; not differentiable (``_NoGrad`` convention)."""
+        if torch.is_grad_enabled() and (v.requires_grad or (torch.is_tensor(s) and s.requires_grad)):
+            s_t = s if torch.is_tensor(s) else torch.as_tensor(s, dtype=v.dtype, device=v.device)
+            return _NoGradInvSqrt.apply(self, v, s_t)
+        return self._apply_inv_sqrt(v, s)
 
     def minv(self, s):
         """(s I + L^T L)^{-1} (rank, rank) and the device scalar s."""
@@ -175,6 +227,12 @@ class BoundPreconditioner:
 
     def logdet(self):
         return self.pre.logdet(self.s)
+
+    def inv_sqrt(self):
+        return self.pre.inv_sqrt(self.s)
+
+    def apply_inv_sqrt(self, v):
+        return self.pre.apply_inv_sqrt(v, self.s)
 
     def sample(self, seed, num, first_probe=0):
         return self.pre.sample(seed, num, self.s, first_probe=first_probe)

@@ -15,6 +15,7 @@ whole Krylov loop, the transposed matvec and the parameter-gradient sweep run as
                                     makes the inputs its lazy kernel closes over differentiable too)
   StencilOp(shape, stencil, ...)    params = (coef,) or ()        util/pde_util.py:74-157 (3x3 heat / wave systems, matrix-free)
   GgnMlpOp(x_train, theta, widths)  params = (alpha,)             util/bnn_util.py:263-293,477-499 (GGN of an MLP + alpha I, theta fixed)
+  PreconditionedOp(op, pre, s)      params = those of ``op``      P^-1/2 A P^-1/2 for a low_rank.Preconditioner held constant
   CallbackOp(fn)                    any Python ``fn(v, *params)`` (torch ops); per-step host control
 
 ``MlpJacobian(x, theta, widths)`` is not an operator (it is rectangular): the Jacobian of the same MLP at the points x as the pair of
@@ -62,6 +63,11 @@ class NativeOp:
         desc.dtype = _lib.dtype_code(dtype)
         desc.n = n
         self.fill(desc, *cparams)
+        # The descriptor borrows device pointers of the constrained parameters.  `constrain` returns fresh tensors (softplus of the raw
+        # values), so a caller that writes op.descriptor(op.constrain(*params), ...) holds no other reference to them: without this one
+        # the caching allocator hands their memory to the next tensor the caller creates (its output, say) and the kernels read the
+        # hyper-parameters out of that tensor while they write it.
+        desc._params = tuple(cparams)
         return desc
 
     def size(self, *cparams):
@@ -105,6 +111,9 @@ class RowShardedOp:
         if isinstance(op, StencilOp):
             raise NotImplementedError("row sharding a StencilOp needs a halo exchange of the grid rows next to a shard's edge, which is "
                                       "not implemented; shard the probes, or assemble the system (pde_util.wave_operator) as a CsrOp")
+        if isinstance(op, PreconditionedOp):
+            raise NotImplementedError("row sharding a PreconditionedOp is not implemented: L would need its rows sharded and L^T v "
+                                      "all-reduced, as the row-sharded PCG does; shard the probes")
         if isinstance(op, GgnMlpOp):
             raise NotImplementedError("row sharding a GgnMlpOp is not implemented: every output row sums over all samples; shard the probes")
         _refuse_input_grad(op)
@@ -996,6 +1005,58 @@ class RbfGramOp(NativeOp):
         return st, g
 
 
+class PreconditionedOp(NativeOp):
+    """B(theta) = S A(theta) S with S = P^-1/2 for a ``low_rank.Preconditioner`` P = s I + L L^T that is held CONSTANT:
+    log det A = log det P + tr log B, and the gradient of the right-hand side with respect to theta is that of log det A, so SLQ
+    with adjoints on B plus ``logdet()`` is the estimator of the same quantity with a spectrum clustered at 1.
+
+    ``op`` is any native operator, ``pre`` the preconditioner, ``s`` its shift (detached here: no gradient flows through P).
+    Parameters, ``constrain``, ``size`` and the gradient fields are those of ``op`` (X of a kernel-Gram operator included); the two
+    applications of S per matvec run in libmfx (``MFX_OP_PRECOND``, csrc/mfx_lowrank.hip)."""
+
+    kind = _lib.OP_PRECOND
+
+    def __init__(self, op, pre, s):
+        if not isinstance(op, NativeOp) or isinstance(op, PreconditionedOp):
+            raise TypeError("PreconditionedOp needs a native operator (DenseOp, CsrOp, RbfGramOp, StencilOp, GgnMlpOp) that is not "
+                            "itself preconditioned")
+        self.op, self.pre = op, pre
+        self.s = s.detach() if torch.is_tensor(s) else s
+        self._factor = None
+
+    def constrain(self, *params):
+        return self.op.constrain(*params)
+
+    def size(self, *cparams):
+        return self.op.size(*cparams)
+
+    def new_grads(self, *cparams):
+        return self.op.new_grads(*cparams)
+
+    def logdet(self):
+        """log det P (fp64 scalar): what ``tr log B`` lacks of ``log det A``."""
+        return self.pre.logdet(self.s)
+
+    def descriptor(self, cparams, dtype, n):
+        inner = self.op.descriptor(cparams, dtype, n)
+        if self.pre.n != n or self.pre.lt.dtype != dtype:
+            raise ValueError(f"PreconditionedOp: a preconditioner of size {self.pre.n} ({self.pre.lt.dtype}) around an operator of "
+                             f"size {n} ({dtype})")
+        _lib.require_device(self.pre.lt)
+        if self._factor is None:
+            self._factor = self.pre.inv_sqrt(self.s)
+        mid, scale = self._factor
+        desc = _lib.Operator()
+        desc.kind, desc.dtype, desc.n = self.kind, _lib.dtype_code(dtype), n
+        pc = _lib.Precond()
+        pc.pc_inner = C.addressof(inner)
+        pc.pc_lt, pc.pc_mid, pc.pc_scale = self.pre.lt.data_ptr(), mid.data_ptr(), scale.data_ptr()
+        pc.pc_rank = self.pre.rank
+        desc.ctx = C.addressof(pc)
+        desc._keep = (pc, inner, mid, scale)  # the host struct and the inner descriptor live as long as the outer one
+        return desc
+
+
 class _PtrRegistry:
     """Maps raw device pointers handed to a callback back to torch views (no copies)."""
 
@@ -1174,6 +1235,8 @@ KernelGramOp = RbfGramOp  # the operator covers the reference's three stationary
 
 def differentiable_inputs(op):
     """Tensors an operator closes over that need a gradient: RbfGramOp's X when it requires grad, else ()."""
+    if isinstance(op, PreconditionedOp):
+        return differentiable_inputs(op.op)
     return (op.X,) if isinstance(op, RbfGramOp) and op.X.requires_grad else ()
 
 
@@ -1182,6 +1245,9 @@ def with_inputs(op, inputs):
     if not inputs:
         return op
     new = copy.copy(op)
+    if isinstance(op, PreconditionedOp):
+        new.op = with_inputs(op.op, inputs)
+        return new
     (new.X,) = inputs
     return new
 

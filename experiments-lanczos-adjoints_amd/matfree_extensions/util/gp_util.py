@@ -15,7 +15,7 @@ import ctypes as C
 import math
 
 from .. import _lib, cg, hutchinson, lanczos, low_rank
-from ..operators import CallbackOp, RbfGramOp, as_operator, softplus
+from ..operators import BoundOp, CallbackOp, NativeOp, PreconditionedOp, RbfGramOp, as_operator, softplus
 
 
 def constraint_greater_than(minval, /):
@@ -165,6 +165,29 @@ def krylov_logdet_slq(krylov_depth, /, *, sample, num_batches: int, checkpoint: 
         mean = values.mean(dim=0)
         std = values.std(dim=0, unbiased=False)
         return mean, {"std_abs": std, "std_rel": std / mean.abs()}
+
+    return logdet
+
+
+def krylov_logdet_slq_p(krylov_depth, /, *, sample, num_batches: int):
+    """logdet(A, key, P=...) -> (value, info): the SLQ log-determinant on the preconditioned operator.
+
+    For the SPD preconditioner P that likelihood_pdf_p builds (a ``low_rank.BoundPreconditioner``) and S = P^-1/2 held constant,
+    log det A = log det P + tr log(S A S): the value is ``P.logdet()`` plus ``krylov_logdet_slq`` on ``PreconditionedOp``, whose
+    spectrum clusters at 1 -- a small ``krylov_depth`` converges, and far deeper ones break down as the reference's recurrence does.
+    ``A`` is a bound native operator.  Differentiable with respect to everything ``krylov_logdet_slq`` is (the inputs X of a
+    kernel-Gram operator included), with the gradient of log det A itself; no gradient flows through P.  No counterpart in the
+    reference."""
+    slq = krylov_logdet_slq(krylov_depth, sample=sample, num_batches=num_batches)
+
+    def logdet(A, /, key, *, P):
+        if not (isinstance(A, BoundOp) and isinstance(A.op, NativeOp)):
+            raise TypeError("krylov_logdet_slq_p: A must be a bound native operator (op.bind(*params))")
+        if not isinstance(P, low_rank.BoundPreconditioner):
+            raise TypeError("krylov_logdet_slq_p: P must be the bound preconditioner likelihood_pdf_p passes (pre.bind(noise))")
+        B = PreconditionedOp(A.op, P.pre, P.s)
+        value, info = slq(B.bind(*A.params), key)
+        return value + B.logdet().to(value.dtype), info
 
     return logdet
 
@@ -340,6 +363,21 @@ def logpdf_krylov_p(solve_p, logdet):
 
     def logpdf(y, *params_logdet, mean, cov_matvec, P):
         logdet_, info_logdet = logdet(cov_matvec, *params_logdet)
+        logdet_ = logdet_ / 2
+        tmp, info_solve = solve_p(cov_matvec, y - mean, P=P)
+        mahalanobis = (y - mean) @ tmp
+        info = {"logdet": info_logdet, "solve": info_solve}
+        (n,) = mean.shape
+        return -logdet_ - 0.5 * mahalanobis - n / 2 * math.log(2 * math.pi), info
+
+    return logpdf
+
+
+def logpdf_krylov_pslq(solve_p, logdet_p):
+    """``logpdf_krylov_p`` with the preconditioner forwarded to the log-determinant as well (``krylov_logdet_slq_p``)."""
+
+    def logpdf(y, *params_logdet, mean, cov_matvec, P):
+        logdet_, info_logdet = logdet_p(cov_matvec, *params_logdet, P=P)
         logdet_ = logdet_ / 2
         tmp, info_solve = solve_p(cov_matvec, y - mean, P=P)
         mahalanobis = (y - mean) @ tmp

@@ -59,6 +59,8 @@ parser.add_argument("--num_samples", type=int, required=True)
 parser.add_argument("--num_epochs", type=int, required=True)
 parser.add_argument("--cg_tol", type=float, required=True)
 parser.add_argument("--precision", type=str, default="f16x3")
+# SLQ on P^-1/2 A P^-1/2 plus log det P (gp_util.krylov_logdet_slq_p): the same log-determinant at a small --num_matvecs
+parser.add_argument("--precond_slq", action="store_true")
 args = parser.parse_args()
 print(args)
 
@@ -88,8 +90,12 @@ prior = gp_util.model_gp(m, k)
 def make_loss(n, cg_atol, maxiter):
     solve_p = cg.pcg_adaptive(rtol=0.0, atol=cg_atol, maxiter=maxiter, miniter=10)
     sample = hutchinson.sampler_rademacher(torch.ones(n, dtype=dt, device=dev), num=args.num_samples)
-    logdet = gp_util.krylov_logdet_slq(args.num_matvecs, sample=sample, num_batches=1, checkpoint=True)
-    logpdf_p = gp_util.logpdf_krylov_p(solve_p=solve_p, logdet=logdet)
+    if args.precond_slq:
+        logdet_p = gp_util.krylov_logdet_slq_p(args.num_matvecs, sample=sample, num_batches=1)
+        logpdf_p = gp_util.logpdf_krylov_pslq(solve_p=solve_p, logdet_p=logdet_p)
+    else:
+        logdet = gp_util.krylov_logdet_slq(args.num_matvecs, sample=sample, num_batches=1, checkpoint=True)
+        logpdf_p = gp_util.logpdf_krylov_p(solve_p=solve_p, logdet=logdet)
     likelihood, p_likelihood = gp_util.likelihood_pdf_p(gram_matvec, logpdf_p, precondition, constrain=constrain)
     return gp_util.target_logml(prior, likelihood), p_likelihood
 

@@ -30,10 +30,12 @@ extern "C" {
                            bump, as for mfx_op_grads.x): callers that zero-fill the descriptor never select them.  MFX_OP_GGN is
                            additive too: its data travels through the existing `ctx` pointer, no struct grows.  So are the three
                            mfx_mlp_jac_* entry points: new symbols, no struct or existing signature changes.  So are
-                           mfx_ggn_diag and mfx_ggn_diag_workspace_bytes: new symbols again, no bump */
+                           mfx_ggn_diag and mfx_ggn_diag_workspace_bytes: new symbols again, no bump.  MFX_OP_PRECOND is additive as
+                           MFX_OP_GGN was (struct mfx_precond through `ctx`), and so are mfx_lowrank_apply / mfx_lowrank_workspace_bytes */
 
 enum { MFX_F32 = 0, MFX_F64 = 1 };
 enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4, MFX_OP_GGN = 5 };
+enum { MFX_OP_PRECOND = 6 }; /* S A S around a native operator, S = P^-1/2 of the partial-Cholesky preconditioner: struct mfx_precond */
 /* Matrix-free 3x3 stencil operator (MFX_OP_STENCIL; util/pde_util.py:18-157).  With S the padded 3x3 correlation below and coef
  * the coefficient field:
  *   MFX_STENCIL_HEAT   state u,       n = ny nx:    y = coef o (S u)                  pde_heat                (:74-87)
@@ -168,6 +170,7 @@ int mfx_ggn_diag(const mfx_ggn_net* net, int dtype, void* diag, void* ws, int64_
  *   RBF      (K(X,X) + noise I) x           util/gp_util.py:69-184 (RBF / Matern kernels),225-226,525-549
  *   STENCIL  coef o conv3x3(pad(u))         util/pde_util.py:74-157 (heat / wave systems, both boundaries)
  *   GGN      (sum_i J_i^T H_i J_i + alpha I) x  util/bnn_util.py:263-293,477-499 (MLP, fixed theta; struct mfx_ggn_net above)
+ *   PRECOND  S A S x, S = P^-1/2 held constant  (not in the reference) a native operator A between two low-rank applies (struct mfx_precond below)
  *   CALLBACK any Python callable                                                              */
 typedef struct mfx_operator {
   int32_t kind;  /* MFX_OP_* */
@@ -205,7 +208,7 @@ typedef struct mfx_operator {
   const void* outputscale;
   const void* noise; /* GGN: the shift alpha (1) */
 
-  /* CALLBACK; GGN: ctx = const mfx_ggn_net* (host) */
+  /* CALLBACK; GGN: ctx = const mfx_ggn_net* (host); PRECOND: ctx = const mfx_precond* (host) */
   mfx_callback_fn callback;
   void* ctx;
 
@@ -231,6 +234,31 @@ typedef struct mfx_operator {
   int32_t st_boundary;
   mfx_stencil_weights st_w;
 } mfx_operator;
+
+/* Preconditioned operator (MFX_OP_PRECOND; not in the reference): B = S A S with A = *pc_inner and S = pc_scale (I - L pc_mid L^T) the
+ * inverse square root of the partial-Cholesky preconditioner P = s I + L L^T (pc_scale = s^-1/2; pc_mid = V diag(1 / ((s + g_i) +
+ * sqrt(s (s + g_i)))) V^T for L^T L = V diag(g) V^T), so that log det A = log det P + tr log B and, S being a constant, the parameter
+ * gradients of B are those of A on (S L_b, S R_b).  mfx_operator.ctx points at this HOST struct (borrowed, valid for the call), as
+ * for MFX_OP_GGN: mfx_operator itself does not grow.
+ *   pc_inner  HOST pointer to the descriptor of A (borrowed, valid for the call): any native kind except PRECOND itself, with the
+ *             dtype and n of the outer descriptor and nrows == 0;
+ *   pc_lt     L^T, (pc_rank, n) row-major;  pc_mid (pc_rank, pc_rank) symmetric;  pc_scale one value -- device pointers in the
+ *             operator's dtype;  1 <= pc_rank <= n.
+ * mode 0: y = S A S x;  transpose: y = S A^T S x.  mfx_op_grads means what it means for A (grads->x of a kernel-Gram inner
+ * included); the sweep applies S to both factors 64 batch rows at a time, so its scratch is 2 * 64 * n elements.  A's per-call
+ * preparation still runs once per driver call.
+ * Refused before any launch: MFX_ERR_INVALID for a NULL ctx, a NULL, CALLBACK or PRECOND inner operator, an inner operator its own
+ * kind refuses, a dtype or n that differs, an inner row block, pc_rank outside [1, n], a NULL pc_lt, pc_mid or pc_scale;
+ * MFX_ERR_UNSUPPORTED for pc_rank > 4096, a row block (nrows > 0) and the row-sharded drivers (L would need its rows sharded and
+ * L^T v all-reduced, as mfx_pcg_solve_sharded does).  The element access of mfx_partial_cholesky and the Gram-only entry points
+ * refuse the kind, as they refuse every kind but their own. */
+typedef struct mfx_precond {
+  const mfx_operator* pc_inner;
+  const void* pc_lt;
+  const void* pc_mid;
+  const void* pc_scale;
+  int64_t pc_rank;
+} mfx_precond;
 
 /* Parameter-gradient outputs (device pointers, ACCUMULATED into, caller zero-fills).  NULL = skip.
  *   dense_a (n, n) row-major, leading dimension = n;  val (CSR: nnz stored values; STENCIL: the (st_ny, st_nx) coefficient field,
@@ -539,6 +567,22 @@ int mfx_pcg_solve_reortho(const mfx_operator* op, const void* b, int64_t ldb, in
 int mfx_precond_apply(int dtype, int64_t n, int64_t rank, const void* lt, const void* minv,
                       const void* shift, const void* v, int64_t ldv, void* z, int64_t ldz, int64_t p,
                       void* ws, int64_t ws_bytes, void* stream);
+
+/* Z_b = scale (V_b - L M L^T V_b) for b < p: the shape of mfx_precond_apply's expression with the middle matrix and the factor
+ * free -- M = mid (rank, rank) SYMMETRIC, scale a device scalar, lt = L^T (rank, n) row-major, all in `dtype` -- and L^T read once
+ * per group of 16 vectors instead of once per vector: ceil(p / 16) * rank * n elements of L^T per pass (one projection pass, one
+ * update pass).  With mid = (s I + L^T L)^-1 and scale = 1 / s it is mfx_precond_apply; with the mid and scale of
+ * struct mfx_precond it is P^-1/2.  Three kernels: per-slice partial sums of L^T V; U = M (L^T V) with both sums in fp64 and the
+ * slices in index order; the update.  No atomics, and no order that depends on p: a vector's result is bit-identical whatever p is
+ * and wherever it sits in the batch (the convention of mfx_probe_group).  Arithmetic in `dtype` (no f16 split).
+ * Z == V with ldz == ldv is allowed (in place).  Asynchronous on `stream`.
+ *   mfx_lowrank_workspace_bytes   bytes for p vectors (host arithmetic); -1 for arguments the call would refuse.
+ * Refused before any launch.  MFX_ERR_INVALID: rank < 1 or rank > n; lt, mid, scale, V or Z NULL; p < 1; ldv or ldz < n; Z
+ * overlapping V in any other way than Z == V with ldz == ldv.  MFX_ERR_UNSUPPORTED: a dtype other than MFX_F32 / MFX_F64; rank >
+ * 4096; p > 16 * 65535.  MFX_ERR_WORKSPACE: ws NULL or ws_bytes too small. */
+int64_t mfx_lowrank_workspace_bytes(int dtype, int64_t n, int64_t rank, int64_t p);
+int mfx_lowrank_apply(int dtype, int64_t n, int64_t rank, const void* lt, const void* mid, const void* scale, const void* v,
+                      int64_t ldv, void* z, int64_t ldz, int64_t p, void* ws, int64_t ws_bytes, void* stream);
 
 /* Modified batched CG (mBCG; Gardner et al. 2018, the estimator behind GPyTorch's marginal likelihood that
  * optim_logml_gpytorch_adaptive.py trains with): mfx_pcg_solve that keeps the scalars of its own iteration, so that ONE
