@@ -25,12 +25,14 @@
 //
 //   k_jac_tiles     out[b][i][:] = J_i v_b: the forward tangent of k_ggn_tiles, written per sample; no workspace, no sum
 //   k_jac_t_tiles   the backward accumulation started at g_L = U[b][i][:], per-workgroup partial sums as above
-//   k_jac_t_reduce  y = sum over workgroups, in index order
+//   k_jac_t_reduce  y = sum over workgroups, in index order: ggn_reduce without the shift, k_ggn_reduce is the same sum with it
 //
 // The exact diagonal sum_i diag(J_i^T H_i J_i) (mfx_ggn_diag: the diagonal-Laplace baseline) is a fourth pass over the same tape:
 //
 //   k_ggn_diag_tiles   the backward sweep once per class, squared where it is produced; the waves of a workgroup share the classes
 //                      instead of holding probes; partial sums as above, added by k_jac_t_reduce
+//
+// Shared: ggn_stage, ggn_accumulate, ggn_reduce, the host code.  The sweeps stay spelled out per kernel: DESIGN.md section 3.11.
 #include "mfx_internal.h"
 
 namespace mfx {
@@ -65,13 +67,15 @@ struct GgnLds {
   T tb[GgnGroup<T>::value][kGgnW][TSP];                     // per probe: tangents t_l / cotangents g_l, [unit][sample]
 };
 
-// aT[kk][i] = M[i0 + i][k0 + kk] for the nv samples of the tile and the units of the chunk, 0 elsewhere (M: (N, width) row-major)
-template <typename T>
+// aT[kk][i] = M[i0 + i][k0 + kk] (its square where Square) for the nv samples of the tile and the units of the chunk, 0 elsewhere
+// (M: (N, width) row-major)
+template <bool Square, typename T>
 __device__ __forceinline__ void ggn_stage(GgnLds<T>& sm, const T* __restrict__ M, int width, int k0, int64_t i0, int nv) {
   for (int e = threadIdx.x; e < kGgnW * kGgnTS; e += blockDim.x) {
     const int kk = e & (kGgnW - 1), i = e / kGgnW;
     const int k = k0 + kk;
-    sm.aT[kk][i] = (i < nv && k < width) ? M[(i0 + i) * width + k] : T(0);
+    const T m = (i < nv && k < width) ? M[(i0 + i) * width + k] : T(0);
+    sm.aT[kk][i] = Square ? m * m : m;
   }
 }
 
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T
       for (int i = 0; i < TS; ++i) s[i] = vb;
       for (int k0 = 0; k0 < wi; k0 += W) {
         __syncthreads();  // the chunk before this one has been consumed
-        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        ggn_stage<false>(sm, a.act[l - 1], wi, k0, i0, nv);
         __syncthreads();
         if (on) {
           const int kc = wi - k0 < W ? wi - k0 : W;
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T
       }
       __syncthreads();  // every wave is done with t_{l-1} and with the last chunk
       if (l < L) {      // the slopes of the tile, staged once for the whole group (0 past the end of the tape)
-        ggn_stage<T>(sm, a.dact[l], wo, 0, i0, nv);
+        ggn_stage<false>(sm, a.dact[l], wo, 0, i0, nv);
         __syncthreads();
       }
       if (on) {
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T
     }
 
     // ---- H product: u = p o t_L - p (p . t_L), or u = t_L; samples past the end of the tape contribute nothing ----
-    if (a.loss == MFX_GGN_CROSS_ENTROPY) ggn_stage<T>(sm, a.prob, c, 0, i0, nv);  // aT is free: the barrier above
+    if (a.loss == MFX_GGN_CROSS_ENTROPY) ggn_stage<false>(sm, a.prob, c, 0, i0, nv);  // aT is free: the barrier above
     __syncthreads();
     if (live && j < c) {
       if (a.loss == MFX_GGN_CROSS_ENTROPY) {
@@ -181,7 +185,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T
       }
       for (int k0 = 0; k0 < wi; k0 += W) {
         __syncthreads();
-        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        ggn_stage<false>(sm, a.act[l - 1], wi, k0, i0, nv);
         __syncthreads();
         if (on) {
           const int kc = wi - k0 < W ? wi - k0 : W;
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T
 #pragma unroll
           for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
         }
-        ggn_stage<T>(sm, a.dact[l - 1], wi, 0, i0, nv);  // aT is free as well: the slopes of layer l - 1, staged once for the group
+        ggn_stage<false>(sm, a.dact[l - 1], wi, 0, i0, nv);  // aT is free as well: the slopes of layer l - 1, staged once for the group
         __syncthreads();
         if (live && j < wi) {
           const T* __restrict__ Wrow = a.theta + a.off[l] + wo + (int64_t)j * wo;
@@ -219,17 +223,6 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_tiles(GgnArgs<T
     }
     __syncthreads();  // the next tile stages into aT and writes tb
   }
-}
-
-// y_b[i] = sum_blk part[blk][b][i] + alpha x_b[i], the workgroups in index order
-template <typename T>
-__global__ __launch_bounds__(256) void k_ggn_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, const T* __restrict__ alpha,
-                                                    const T* __restrict__ x, int64_t ldx, T* __restrict__ y, int64_t ldy) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, p = gridDim.y;
-  if (i >= P) return;
-  T acc = T(0);
-  for (int64_t blk = 0; blk < nblk; ++blk) acc += part[(blk * p + b) * P + i];
-  y[b * ldy + i] = acc + alpha[0] * x[b * ldx + i];
 }
 
 // out[b][i][:] = J_i v_b for every probe b and sample i < N (out: (p, N, c) contiguous): the forward tangent of k_ggn_tiles with the
@@ -260,7 +253,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_tiles(GgnArgs<T
       for (int i = 0; i < TS; ++i) s[i] = vb;
       for (int k0 = 0; k0 < wi; k0 += W) {
         __syncthreads();  // the chunk before this one has been consumed
-        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        ggn_stage<false>(sm, a.act[l - 1], wi, k0, i0, nv);
         __syncthreads();
         if (on) {
           const int kc = wi - k0 < W ? wi - k0 : W;
@@ -283,7 +276,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_tiles(GgnArgs<T
       }
       __syncthreads();  // every wave is done with t_{l-1} and with the last chunk
       if (l < L) {      // the slopes of the tile, staged once for the whole group
-        ggn_stage<T>(sm, a.dact[l], wo, 0, i0, nv);
+        ggn_stage<false>(sm, a.dact[l], wo, 0, i0, nv);
         __syncthreads();
         if (on) {
 #pragma unroll
@@ -336,7 +329,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_t_tiles(GgnArgs
       }
       for (int k0 = 0; k0 < wi; k0 += W) {
         __syncthreads();
-        ggn_stage<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        ggn_stage<false>(sm, a.act[l - 1], wi, k0, i0, nv);
         __syncthreads();
         if (on) {
           const int kc = wi - k0 < W ? wi - k0 : W;
@@ -356,7 +349,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_t_tiles(GgnArgs
 #pragma unroll
           for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
         }
-        ggn_stage<T>(sm, a.dact[l - 1], wi, 0, i0, nv);  // aT is free as well: the slopes of layer l - 1, staged once for the group
+        ggn_stage<false>(sm, a.dact[l - 1], wi, 0, i0, nv);  // aT is free as well: the slopes of layer l - 1, staged once for the group
         __syncthreads();
         if (live && j < wi) {
           const T* __restrict__ Wrow = a.theta + a.off[l] + wo + (int64_t)j * wo;
@@ -376,20 +369,29 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_jac_t_tiles(GgnArgs
   }
 }
 
-// y_b[i] = sum_blk part[blk][b][i], the workgroups in index order
-template <typename T>
-__global__ __launch_bounds__(256) void k_jac_t_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, T* __restrict__ y,
-                                                      int64_t ldy) {
+// y_b[i] = sum_blk part[blk][b][i], the workgroups in index order, + alpha x_b[i] where Shift: k_ggn_reduce with, k_jac_t_reduce without
+template <bool Shift, typename T>
+__device__ __forceinline__ void ggn_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, const T* __restrict__ alpha,
+                                           const T* __restrict__ x, int64_t ldx, T* __restrict__ y, int64_t ldy) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, p = gridDim.y;
   if (i >= P) return;
   T acc = T(0);
   for (int64_t blk = 0; blk < nblk; ++blk) acc += part[(blk * p + b) * P + i];
-  y[b * ldy + i] = acc;
+  y[b * ldy + i] = Shift ? acc + alpha[0] * x[b * ldx + i] : acc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_ggn_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, const T* __restrict__ alpha,
+                                                    const T* __restrict__ x, int64_t ldx, T* __restrict__ y, int64_t ldy) {
+  ggn_reduce<true, T>(part, nblk, P, alpha, x, ldx, y, ldy);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_jac_t_reduce(const T* __restrict__ part, int64_t nblk, int64_t P, T* __restrict__ y,
+                                                      int64_t ldy) {
+  ggn_reduce<false, T>(part, nblk, P, nullptr, nullptr, 0, y, ldy);
 }
 
 // ---- the exact diagonal sum_i diag(J_i^T H_i J_i) (mfx_ggn_diag); include/mfx.h has the formulas ----
-// The steps of k_ggn_diag_tiles that the kernels above spell out in place are helpers here: the staging of a squared tape chunk, one
-// layer of the backward sweep, and the fixed-order sum over the waves of a workgroup.
 
 // D = max(m1 - m2^2, 0), the product rounded on its own: contracted to fma(-m2, m2, m1) it is not 0 where m1 = round(m2 * m2) (c = 1),
 // and hipcc contracts across statements (and through __fmul_rn) unless the expression says otherwise
@@ -398,17 +400,6 @@ __device__ __forceinline__ T ggn_variance(T m1, T m2) {
 #pragma clang fp contract(off)
   const T d = m1 - m2 * m2;
   return d > T(0) ? d : T(0);  // a variance under p: round-off below 0 is cut off
-}
-
-// aT[kk][i] = M[i0 + i][k0 + kk]^2 for the nv samples of the tile and the units of the chunk, 0 elsewhere: ggn_stage with a square
-template <typename T>
-__device__ __forceinline__ void ggn_stage_sq(GgnLds<T>& sm, const T* __restrict__ M, int width, int k0, int64_t i0, int nv) {
-  for (int e = threadIdx.x; e < kGgnW * kGgnTS; e += blockDim.x) {
-    const int kk = e & (kGgnW - 1), i = e / kGgnW;
-    const int k = k0 + kk;
-    const T m = (i < nv && k < width) ? M[(i0 + i) * width + k] : T(0);
-    sm.aT[kk][i] = m * m;
-  }
 }
 
 // One layer down, for the cotangents s of wave g (lane j = unit j of layer l on entry, of layer l - 1 on return):
@@ -423,7 +414,7 @@ __device__ __forceinline__ void ggn_down(GgnLds<T>& sm, const GgnArgs<T>& a, int
 #pragma unroll
     for (int i = 0; i < TS; ++i) sm.tb[g][j][i] = s[i];
   }
-  ggn_stage<T>(sm, a.dact[l - 1], wi, 0, i0, nv);
+  ggn_stage<false>(sm, a.dact[l - 1], wi, 0, i0, nv);
   __syncthreads();
   if (j < wi) {
     const T* __restrict__ Wrow = a.theta + a.off[l] + wo + (int64_t)j * wo;
@@ -520,7 +511,7 @@ __global__ __launch_bounds__(64 * GgnGroup<T>::value) void k_ggn_diag_tiles(GgnA
       }
       for (int k0 = 0; k0 < wi; k0 += W) {
         __syncthreads();  // the chunk before this one (or the sums over the waves) has been consumed
-        ggn_stage_sq<T>(sm, a.act[l - 1], wi, k0, i0, nv);
+        ggn_stage<true>(sm, a.act[l - 1], wi, k0, i0, nv);
         __syncthreads();
         if (j < wo) {
           const int kc = wi - k0 < W ? wi - k0 : W;
@@ -579,6 +570,10 @@ static int64_t ggn_dot_blocks(int64_t n) {
   return blocks < kGgnDotBlocks ? blocks : kGgnDotBlocks;
 }
 
+static int64_t ggn_part_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {  // bytes of the partial sums part[workgroup][p][P]
+  return ggn_blocks(net->nsamples) * p * ggn_params(net) * (int64_t)dtype_size(dtype);
+}
+
 // the checks of a net that the operator and the Jacobian maps share; `who` opens the message
 static int ggn_check_net(const mfx_ggn_net* net, const char* who) {
   MFX_REQUIRE(net->nlayers >= 1 && net->nlayers <= MFX_GGN_MAX_LAYERS, MFX_ERR_INVALID, "%s: nlayers = %d is outside 1..%d", who,
@@ -606,15 +601,24 @@ static int ggn_check_limits(const mfx_ggn_net* net, const char* who) {
   return MFX_OK;
 }
 
+// the loss of the operator and of the diagonal (the maps read neither loss nor prob), in two steps: the operator checks its shift between
+static int ggn_check_loss(const mfx_ggn_net* net, const char* who) {
+  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "%s: unknown loss %d", who, net->loss);
+  return MFX_OK;
+}
+static int ggn_check_prob(const mfx_ggn_net* net, const char* who) {
+  MFX_REQUIRE(net->loss != MFX_GGN_CROSS_ENTROPY || net->prob, MFX_ERR_INVALID, "%s: prob is NULL (cross-entropy)", who);
+  return MFX_OK;
+}
+
 static int ggn_check(const mfx_operator* op) {
   static const char* who = "GGN operator";
   const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
   MFX_REQUIRE(net, MFX_ERR_INVALID, "GGN operator: ctx (the mfx_ggn_net) is NULL");
   MFX_TRY(ggn_check_net(net, who));
-  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "GGN operator: unknown loss %d",
-              net->loss);
+  MFX_TRY(ggn_check_loss(net, who));
   MFX_REQUIRE(op->noise, MFX_ERR_INVALID, "GGN operator: noise (the shift alpha) is NULL");
-  MFX_REQUIRE(net->loss != MFX_GGN_CROSS_ENTROPY || net->prob, MFX_ERR_INVALID, "GGN operator: prob is NULL (cross-entropy)");
+  MFX_TRY(ggn_check_prob(net, who));
   const int64_t P = ggn_params(net);
   MFX_REQUIRE(op->n == P, MFX_ERR_INVALID, "GGN operator: n = %lld, but the widths give P = %lld parameters", (long long)op->n,
               (long long)P);
@@ -633,7 +637,7 @@ static int ggn_check_grads(const mfx_operator*, const mfx_op_grads* grads, bool)
 static int64_t ggn_workspace_bytes(const mfx_operator* op, int64_t, int64_t p_apply) {
   const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
   if (!net || net->nlayers < 1 || net->nlayers > MFX_GGN_MAX_LAYERS || net->nsamples < 1) return 256;  // refused before any use
-  const int64_t apply = ggn_blocks(net->nsamples) * (p_apply > 0 ? p_apply : 1) * ggn_params(net) * (int64_t)dtype_size(op->dtype);
+  const int64_t apply = ggn_part_bytes(net, op->dtype, p_apply > 0 ? p_apply : 1);
   const int64_t dot = kGgnDotBlocks * (int64_t)sizeof(double);
   return align_up(apply > dot ? apply : dot, 256);
 }
@@ -664,22 +668,38 @@ static GgnArgs<T> ggn_args(const mfx_ggn_net* net) {
   return a;
 }
 
+// the launch of a tile kernel: nblk workgroups along the samples, one per group of G vectors across, a wave per vector
+template <typename T, typename Tiles>
+static int ggn_launch(int64_t nblk, int64_t p, Tiles tiles) {
+  constexpr int G = GgnGroup<T>::value;
+  tiles(dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+// tile kernel, then reduce: part[workgroup][p][P] from at most 64 workgroups along the samples, y_b = their sum, + alpha x_b where Shift
+template <typename T, bool Shift = false, typename Tiles>
+static int ggn_pass(const GgnArgs<T>& a, int64_t p, Tiles tiles, const T* part, T* y, int64_t ldy, hipStream_t stream,
+                    const T* alpha = nullptr, const T* x = nullptr, int64_t ldx = 0) {
+  const int64_t nblk = ggn_blocks(a.N);
+  MFX_TRY(ggn_launch<T>(nblk, p, tiles));
+  const dim3 grid((unsigned)((a.P + 255) / 256), (unsigned)p);
+  if constexpr (Shift) k_ggn_reduce<T><<<grid, 256, 0, stream>>>(part, nblk, a.P, alpha, x, ldx, y, ldy);
+  else k_jac_t_reduce<T><<<grid, 256, 0, stream>>>(part, nblk, a.P, y, ldy);
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
 template <typename T>
 static int ggn_apply(const mfx_operator* op, int, const void* xv, int64_t ldx, const void*, int64_t, void* y, int64_t ldy, int64_t p,
                      void* ws, int64_t ws_bytes, hipStream_t stream) {  // symmetric: the mode is ignored
   const T* x = (const T*)xv;
   const mfx_ggn_net* net = (const mfx_ggn_net*)op->ctx;
   const GgnArgs<T> a = ggn_args<T>(net);
-  const int64_t nblk = ggn_blocks(a.N);
-  const int64_t need = nblk * p * a.P * (int64_t)sizeof(T);
+  const int64_t need = ggn_part_bytes(net, op->dtype, p);
   MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "GGN operator: workspace too small: need %lld bytes", (long long)need);
-  constexpr int G = GgnGroup<T>::value;
-  k_ggn_tiles<T><<<dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G, 0, stream>>>(a, x, ldx, p, (T*)ws);
-  MFX_CHECK_LAUNCH();
-  k_ggn_reduce<T><<<dim3((unsigned)((a.P + 255) / 256), (unsigned)p), 256, 0, stream>>>((const T*)ws, nblk, a.P, (const T*)op->noise, x,
-                                                                                      ldx, (T*)y, ldy);
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  const auto tiles = [&](dim3 grid, int block) { k_ggn_tiles<T><<<grid, block, 0, stream>>>(a, x, ldx, p, (T*)ws); };
+  return ggn_pass<T, true>(a, p, tiles, (const T*)ws, (T*)y, ldy, stream, (const T*)op->noise, x, ldx);
 }
 
 // adds sum_b L_b . R_b to grads->noise (NULL: no launch)
@@ -720,30 +740,17 @@ static int jac_check(const mfx_ggn_net* net, int dtype, int64_t p) {
   return MFX_OK;
 }
 
-static int64_t jac_t_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {
-  return ggn_blocks(net->nsamples) * p * ggn_params(net) * (int64_t)dtype_size(dtype);
-}
-
 template <typename T>
 static int jac_apply_t(const mfx_ggn_net* net, const T* V, int64_t ldv, int64_t p, T* out, hipStream_t stream) {
   const GgnArgs<T> a = ggn_args<T>(net);
-  constexpr int G = GgnGroup<T>::value;
   const int64_t nblk = a.ntiles < kJacMaxBlocks ? a.ntiles : kJacMaxBlocks;
-  k_jac_tiles<T><<<dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G, 0, stream>>>(a, V, ldv, p, out);
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return ggn_launch<T>(nblk, p, [&](dim3 grid, int block) { k_jac_tiles<T><<<grid, block, 0, stream>>>(a, V, ldv, p, out); });
 }
 
 template <typename T>
 static int jac_t_apply_t(const mfx_ggn_net* net, const T* U, int64_t p, T* Y, int64_t ldy, T* ws, hipStream_t stream) {
   const GgnArgs<T> a = ggn_args<T>(net);
-  constexpr int G = GgnGroup<T>::value;
-  const int64_t nblk = ggn_blocks(a.N);
-  k_jac_t_tiles<T><<<dim3((unsigned)nblk, (unsigned)((p + G - 1) / G)), 64 * G, 0, stream>>>(a, U, p, ws);
-  MFX_CHECK_LAUNCH();
-  k_jac_t_reduce<T><<<dim3((unsigned)((a.P + 255) / 256), (unsigned)p), 256, 0, stream>>>(ws, nblk, a.P, Y, ldy);
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return ggn_pass<T>(a, p, [&](dim3 grid, int block) { k_jac_t_tiles<T><<<grid, block, 0, stream>>>(a, U, p, ws); }, ws, Y, ldy, stream);
 }
 
 // ---- the exact diagonal of the GGN (mfx_ggn_diag): one value per parameter, so not an operator application ----
@@ -752,27 +759,21 @@ static const char* const kDiagWho = "GGN diagonal";
 static int diag_check(const mfx_ggn_net* net, int dtype) {
   MFX_REQUIRE(net, MFX_ERR_INVALID, "GGN diagonal: net is NULL");
   MFX_TRY(ggn_check_net(net, kDiagWho));
-  MFX_REQUIRE(net->loss == MFX_GGN_CROSS_ENTROPY || net->loss == MFX_GGN_MSE, MFX_ERR_INVALID, "GGN diagonal: unknown loss %d", net->loss);
-  MFX_REQUIRE(net->loss != MFX_GGN_CROSS_ENTROPY || net->prob, MFX_ERR_INVALID, "GGN diagonal: prob is NULL (cross-entropy)");
+  MFX_TRY(ggn_check_loss(net, kDiagWho));
+  MFX_TRY(ggn_check_prob(net, kDiagWho));
   MFX_TRY(ggn_check_limits(net, kDiagWho));
   MFX_REQUIRE(dtype == MFX_F32 || dtype == MFX_F64, MFX_ERR_UNSUPPORTED, "GGN diagonal: unsupported dtype %d", dtype);
   return MFX_OK;
 }
 
-static int64_t diag_bytes(const mfx_ggn_net* net, int dtype) {  // part[workgroup][P]
-  return ggn_blocks(net->nsamples) * ggn_params(net) * (int64_t)dtype_size(dtype);
+template <typename T>
+static int diag_t(const mfx_ggn_net* net, T* diag, T* ws, hipStream_t stream) {  // part[workgroup][P]: one "vector"
+  const GgnArgs<T> a = ggn_args<T>(net);
+  return ggn_pass<T>(a, 1, [&](dim3 grid, int block) { k_ggn_diag_tiles<T><<<grid, block, 0, stream>>>(a, ws); }, ws, diag, a.P, stream);
 }
 
-template <typename T>
-static int diag_t(const mfx_ggn_net* net, T* diag, T* ws, hipStream_t stream) {
-  const GgnArgs<T> a = ggn_args<T>(net);
-  const int64_t nblk = ggn_blocks(a.N);
-  k_ggn_diag_tiles<T><<<dim3((unsigned)nblk), 64 * GgnGroup<T>::value, 0, stream>>>(a, ws);
-  MFX_CHECK_LAUNCH();
-  k_jac_t_reduce<T><<<dim3((unsigned)((a.P + 255) / 256), 1), 256, 0, stream>>>(ws, nblk, a.P, diag, a.P);  // one "vector"
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
-}
+template <typename F>  // the typed tail of an entry point: f(T()) with T = float or double for a checked dtype
+static int ggn_by_dtype(int dtype, F f) { return dtype == MFX_F32 ? f(float()) : f(double()); }
 
 }  // namespace mfx
 
@@ -782,22 +783,21 @@ extern "C" {
 
 int64_t mfx_ggn_diag_workspace_bytes(const mfx_ggn_net* net, int dtype) {
   if (diag_check(net, dtype) != MFX_OK) return -1;
-  return align_up(diag_bytes(net, dtype), 256);
+  return align_up(ggn_part_bytes(net, dtype, 1), 256);
 }
 
 int mfx_ggn_diag(const mfx_ggn_net* net, int dtype, void* diag, void* ws, int64_t ws_bytes, void* stream) {
   MFX_TRY(diag_check(net, dtype));
   MFX_REQUIRE(diag, MFX_ERR_INVALID, "GGN diagonal: diag is NULL");
-  const int64_t need = diag_bytes(net, dtype);
+  const int64_t need = ggn_part_bytes(net, dtype, 1);
   MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "GGN diagonal: workspace too small: need %lld bytes", (long long)need);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == MFX_F32) return diag_t<float>(net, (float*)diag, (float*)ws, s);
-  return diag_t<double>(net, (double*)diag, (double*)ws, s);
+  return ggn_by_dtype(dtype, [&](auto t) { return diag_t(net, (decltype(t)*)diag, (decltype(t)*)ws, s); });
 }
 
 int64_t mfx_mlp_jac_workspace_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {
   if (jac_check(net, dtype, p) != MFX_OK) return -1;
-  return align_up(jac_t_bytes(net, dtype, p), 256);
+  return align_up(ggn_part_bytes(net, dtype, p), 256);
 }
 
 int mfx_mlp_jac_apply(const mfx_ggn_net* net, int dtype, const void* V, int64_t ldv, int64_t p, void* out, void* stream) {
@@ -806,8 +806,7 @@ int mfx_mlp_jac_apply(const mfx_ggn_net* net, int dtype, const void* V, int64_t 
   MFX_REQUIRE(ldv >= ggn_params(net), MFX_ERR_INVALID, "MLP Jacobian: ldv = %lld is less than the P = %lld parameters", (long long)ldv,
               (long long)ggn_params(net));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == MFX_F32) return jac_apply_t<float>(net, (const float*)V, ldv, p, (float*)out, s);
-  return jac_apply_t<double>(net, (const double*)V, ldv, p, (double*)out, s);
+  return ggn_by_dtype(dtype, [&](auto t) { return jac_apply_t(net, (const decltype(t)*)V, ldv, p, (decltype(t)*)out, s); });
 }
 
 int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_t p, void* Y, int64_t ldy, void* ws, int64_t ws_bytes,
@@ -816,11 +815,11 @@ int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_
   MFX_REQUIRE(U && Y, MFX_ERR_INVALID, "MLP Jacobian: U or Y is NULL");
   MFX_REQUIRE(ldy >= ggn_params(net), MFX_ERR_INVALID, "MLP Jacobian: ldy = %lld is less than the P = %lld parameters", (long long)ldy,
               (long long)ggn_params(net));
-  const int64_t need = jac_t_bytes(net, dtype, p);
+  const int64_t need = ggn_part_bytes(net, dtype, p);
   MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "MLP Jacobian: workspace too small: need %lld bytes", (long long)need);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == MFX_F32) return jac_t_apply_t<float>(net, (const float*)U, p, (float*)Y, ldy, (float*)ws, s);
-  return jac_t_apply_t<double>(net, (const double*)U, p, (double*)Y, ldy, (double*)ws, s);
+  return ggn_by_dtype(dtype, [&](auto t) {
+    return jac_t_apply_t(net, (const decltype(t)*)U, p, (decltype(t)*)Y, ldy, (decltype(t)*)ws, static_cast<hipStream_t>(stream));
+  });
 }
 
 }  // extern "C"

@@ -272,6 +272,24 @@ def test_the_ggn_operator_is_the_two_maps_around_the_loss_hessian(n, widths, los
     assert _close(got, want), float(np.abs(got - want).max())
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("case", [(65, (5, 64, 64, 2), "tanh"), (64, (130, 4, 1, 4, 3), "relu"), (2081, (3, 2), "tanh")],
+                         ids=lambda c: f"N{c[0]}-{'x'.join(map(str, c[1]))}-{c[2]}")
+def test_the_mse_operator_without_shift_has_the_bits_of_the_two_maps_back_to_back(case, dtype):
+    """For mse the loss Hessian is the identity.  The fused kernel and the kernels of the two maps are separate code that forms every
+    product and sum in the same order, so op(V, 0) and jac.t_apply(jac.apply(V)) must be the same bits: this pins that agreement.  The
+    shapes: a ragged second tile, a three-chunk first layer with a width-1 layer, a workgroup that walks more than one tile; p = 5 is
+    a ragged group."""
+    n, widths, activation = case
+    rng = np.random.default_rng(n * 131 + len(widths))
+    theta, x = T(rng.standard_normal(gr.param_count(widths)) * 0.7, dtype), T(rng.standard_normal((n, widths[0])), dtype)
+    op = GgnMlpOp(x, theta, widths, activation=activation, loss="mse")
+    jac = op.jacobian()
+    V = T(rng.standard_normal((5, op.n)), dtype)
+    got, want = op(V, T(0.0, dtype)), jac.t_apply(jac.apply(V))
+    assert bool(want.abs().sum() > 0) and torch.equal(got, want)
+
+
 # ---- the predictive tier: native pieces against the same compositions on dense pieces (fp64) ----
 class _DenseJac:
     """the interface of MlpJacobian over a dense (N, c, P) Jacobian: torch products on the device"""
