@@ -490,10 +490,10 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
   float agpr_seed = 0.f;
   asm volatile("; accumulators in AGPRs" : "+a"(agpr_seed));
 
-  auto issue_tile_dma = [&](int tl) {
+  auto issue_tile_dma = [&](int tl, int b) {  // tile tl into LDS buffer b = tl & 1 (a constant at every call)
     const char* asrc = reinterpret_cast<const char*>(pka) + (t_first + tl) * (int64_t)S::kABytes;
     const char* vsrc = reinterpret_cast<const char*>(pkv) + ((int64_t)blockIdx.y * ntile_all + t_first + tl) * S::kVBytes;
-    char* dst = fat_smem + (tl & 1) * S::kTile;
+    char* dst = fat_smem + b * S::kTile;
 #pragma unroll
     for (int c = 0; c < (S::kABytes / 1024 + 3) / 4; ++c) {
       const int piece = wid + 4 * c;
@@ -502,8 +502,8 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
 #pragma unroll
     for (int c = 0; c < S::kVBytes / 4096; ++c) glds16(vsrc + (wid + 4 * c) * 1024 + lane * 16, dst + S::kABytes + (wid + 4 * c) * 1024);
   };
-  if (0 < ntl) issue_tile_dma(0);
-  if (1 < ntl) issue_tile_dma(1);
+  if (0 < ntl) issue_tile_dma(0, 0);
+  if (1 < ntl) issue_tile_dma(1, 1);
 
   // row operand of the distance product, resident: [Bh | Bl | Bh | 0] of [x_i, 1, |x_i|^2] along k = 8 g + e, negated for odd 32-row blocks
   half8 bi[8];
@@ -548,15 +548,20 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
   // ---- the distance MFMA: asm, because its four results must land in VGPRs (v_exp cannot read an accumulation register) while the
   //      function's intrinsic MFMAs are in AGPR form.  The compiler sees no MFMA here and pads nothing:
   //      * operands: the row operand is written once before the sweep; the column operand arrives by ds_read_b128, whose s_waitcnt is
-  //        data flow and kept.  The leading s_nop 1 covers a register copy of either that the allocator might put in front of the
-  //        statement (VALU write -> MFMA A/B read).
+  //        data flow and kept.  What is left is a register copy of either that the allocator might put in front of the statement
+  //        (VALU write -> MFMA A/B read: 2 wait states).  PAD = true opens the statement with an s_nop 1 against it: the prologue and
+  //        the peeled tile, which run once.  The two-tile loop body takes PAD = false: nothing is carried across its back edge by
+  //        a copy, its code holds no v_mov / v_accvgpr_* at all (read from the code object of all four instances), and
+  //        the instruction in front of the statement is then the chain step of the slot before it (a v_exp behind slot 7, the
+  //        v_cvt_pk behind slot 9), which writes the ring entry or the hi fragment of unit u + 1 -- never an operand of this MFMA.
   //      * result: a v_mfma_f32_16x16x32_f16 is an 8-pass MFMA; a VALU instruction may read its VGPR result 12 wait states after
   //        issue at the earliest.  The first reader of distance MFMA c2 (slot 8 + 2 c2 of unit u) is the v_exp behind slot 4 c2 of unit
   //        u + 1: six (c2 = 0) or eight (c2 = 1) MFMAs of this wave -- which owns the SIMD's matrix pipe, 16 cycles each -- and the
   //        chain's VALU instructions behind them (one per slot 0-7, two per slot 8-13) lie between: >= 12 instructions by the
-  //        MFMAs and the table alone, and >= 96 cycles.  The prologue has no such schedule and pads by hand. ------------------------------------------------------------------------------------------
-  auto dist16 = [&](floatx4& kd, const half8& a, const half8& b) {
-    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(kd) : "v"(a), "v"(b));
+  //        MFMAs and the table alone, and >= 96 cycles, with or without the s_nop.  The prologue has no such schedule and pads by hand.
+  auto dist16 = [&](floatx4& kd, const half8& a, const half8& b, auto pad) {
+    if constexpr (decltype(pad)::value) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(kd) : "v"(a), "v"(b));
+    else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(kd) : "v"(a), "v"(b));
   };
   // ---- one micro-step of the split chain of a unit (entries w[c2][r], e = 4 c2 + r): t = 0 exp2 of entry i; 1 hi pair i; 2 lo half
   //      of entry i (v_fma_mixlo / mixhi straight into its half of the packed lo register, as k_rbf_fat_apply) -------------------------
@@ -610,36 +615,29 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
 #pragma unroll
   for (int f = 0; f < 8; ++f) read_v(vf[0][f], 0, 0, f);
 #pragma unroll
-  for (int c2 = 0; c2 < 2; ++c2) dist16(wr[0][c2], aj[0][c2], bi[0]);
+  for (int c2 = 0; c2 < 2; ++c2) dist16(wr[0][c2], aj[0][c2], bi[0], std::true_type{});
 #pragma unroll
-  for (int c2 = 0; c2 < 2; ++c2) dist16(wr[1][c2], aj[0][c2], bi[1]);
+  for (int c2 = 0; c2 < 2; ++c2) dist16(wr[1][c2], aj[0][c2], bi[1], std::true_type{});
   // no MFMA follows here: the 12 wait states (and more) between the last distance MFMA and the first v_exp, by hand
   asm volatile("s_nop 15\n\ts_nop 15" : "+v"(wr[0][0]), "+v"(wr[0][1]), "+v"(wr[1][0]), "+v"(wr[1][1]));
 #pragma unroll
   for (int slot = 0; slot < 14; ++slot) chain_slot(slot, wr[0], ah[0], al[0], lp, false);
 
   const float sc = outputscale[0];
-  for (int tl = 0; tl < ntl; ++tl) {
-    const int buf = tl & 1;
-    if (tl > 0 && (tl % kChainTiles) == 0) {  // chain fold: masters += accumulators, accumulators restart from zero
-#pragma unroll
-      for (int it = 0; it < 8; ++it)
-#pragma unroll
-        for (int pg = 0; pg < 4; ++pg)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            mst[it][pg][r] += acc[it][pg][r];
-            acc[it][pg][r] = 0.f;
-          }
-    }
+  // One tile, in LDS buffer `buf`.  The tile loop below runs TWO tiles per iteration, the period of the buffer rotation: the buffer
+  // is a constant of the code (every LDS offset an immediate) and the loop body ends with every accumulator, fragment and ring entry
+  // in the register it started in -- nothing is carried across the back edge by a copy.
+  auto tile = [&](auto bc, auto pad, const int tl) {  // pad: the peeled tile (dist16's PAD; the sweep ends behind it)
+    constexpr int buf = decltype(bc)::value;
+    constexpr bool kLast = decltype(pad)::value;
     auto unit = [&](auto uc) {
       constexpr int u = decltype(uc)::value;
       constexpr int jb = u >> 3, it = u & 7;
       constexpr int u1 = (u + 1) & 15, u2 = (u + 2) & 15;  // the unit being split and the one whose distances are computed (may lie in the next tile)
       constexpr bool neg_n = (((u1 >> 3) + ((u1 & 7) >> 1)) & 1) != 0;
       // the fragments of column block jb ^ 1 roll in during column block jb: this tile's block 1, or the NEXT tile's block 0 (behind the barrier)
-      const int nbuf = jb == 1 ? buf ^ 1 : buf;
-      if (u == 9 && tl + 2 < ntl) issue_tile_dma(tl + 2);  // (this tile's buffer has been dead since the barrier behind unit 7)
+      constexpr int nbuf = jb == 1 ? buf ^ 1 : buf;
+      if (u == 9 && tl + 2 < ntl) issue_tile_dma(tl + 2, buf);  // (this tile's buffer has been dead since the barrier behind unit 7)
 #pragma unroll
       for (int slot = 0; slot < 14; ++slot) {
         __builtin_amdgcn_sched_barrier(0);
@@ -647,7 +645,11 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
         // other accumulators between two MFMAs on the same one, and the lo fragment -- finished last -- is read last
         if (slot == 8 || slot == 10) {
           const int c2 = (slot - 8) / 2;
-          dist16(wr[(u + 2) & 3][c2], aj[(u2 >> 3) & 1][c2], bi[u2 & 7]);
+          // (the peeled tile ends the sweep: no unit 16 or 17 follows.  Their distances must not even be issued: the result of an asm
+          //  MFMA lands 8 passes after issue, unseen by the compiler, and a ring entry nobody reads is dead at the statement -- its
+          //  registers are handed to the next chain step at once and the late result lands on top of it.  Measured so: the hi
+          //  fragment of unit 15 overwritten, NaN in row tile 7 behind every odd tile count.  In the loop body every entry is read.)
+          if constexpr (!(kLast && u >= 14)) dist16(wr[(u + 2) & 3][c2], aj[(u2 >> 3) & 1][c2], bi[u2 & 7], pad);
         } else {
           const int m = slot < 8 ? slot : (slot == 9 ? 8 : slot - 2);
           const int w = m / 4, pg = m % 4;
@@ -655,7 +657,7 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
                                                                acc[it][pg], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        chain_slot(slot, wr[(u + 1) & 3], ah[(u + 1) & 1], al[(u + 1) & 1], lp, neg_n);
+        if constexpr (!(kLast && u == 15)) chain_slot(slot, wr[(u + 1) & 3], ah[(u + 1) & 1], al[(u + 1) & 1], lp, neg_n);
         // fragment reads: one probe fragment of the next column block per unit; its column operand in unit it = 3 (first needed by the
         // distances issued in unit it = 6)
         if (slot == 2) read_v(vf[jb ^ 1][it], nbuf, jb ^ 1, it);
@@ -686,7 +688,30 @@ __global__ __launch_bounds__(256, 1) void k_rbf_fat_apply16(const float* __restr
     unit(std::integral_constant<int, 13>{});
     unit(std::integral_constant<int, 14>{});
     unit(std::integral_constant<int, 15>{});
+  };
+  // The sweep chain by chain: the fold stands in front of every tile tl > 0 with tl % kChainTiles == 0, between the chains and not in
+  // the tile loop, whose only loop-carried values are then the ones a tile itself carries.  A chain is an even number of tiles, so
+  // only the sweep's last tile can be left over: it is peeled (it is an even tile: buffer 0), behind its fold if it opens a chain.
+  static_assert(kChainTiles % 2 == 0, "a chain is a whole number of two-tile loop bodies");
+  for (int t0 = 0; t0 < ntl; t0 += kChainTiles) {
+    if (t0 > 0) {  // chain fold: masters += accumulators, accumulators restart from zero
+#pragma unroll
+      for (int it = 0; it < 8; ++it)
+#pragma unroll
+        for (int pg = 0; pg < 4; ++pg)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            mst[it][pg][r] += acc[it][pg][r];
+            acc[it][pg][r] = 0.f;
+          }
+    }
+    const int t1 = t0 + kChainTiles < ntl ? t0 + kChainTiles : ntl;
+    for (int tl = t0; tl + 1 < t1; tl += 2) {
+      tile(std::integral_constant<int, 0>{}, std::false_type{}, tl);
+      tile(std::integral_constant<int, 1>{}, std::false_type{}, tl + 1);
+    }
   }
+  if (ntl & 1) tile(std::integral_constant<int, 0>{}, std::true_type{}, ntl - 1);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // no LDS-DMA of mine is left in flight
 #pragma unroll
   for (int it = 0; it < 8; ++it)

@@ -10,7 +10,8 @@
 //
 // Variants (bit mask VAR): 1 chain on; 2 the three products of an accumulator back to back (else product-major: 4 different
 // accumulators between two MFMAs on the same one); 4 LDS fragment reads on; 8 LDS-DMA of the tile images + barrier per tile;
-// 16 the 32x32x16 reference loop of tools/shape_bench.hip (SHAPE 0) instead.
+// 16 the 32x32x16 reference loop of tools/shape_bench.hip (SHAPE 0) instead; 512 the tile loop of k_rbf_fat_apply16 as shipped: two
+// tiles per iteration, the LDS buffer a constant of the code (every offset an immediate, nothing carried across the back edge).
 // The like-for-like row: the 32x32x16 loop (k32) has the fragment reads of k_rbf_fat_apply in every form; with DMA = 1 it also has
 // the kernel's LDS-DMA (21 pieces of 1 KiB per 64-column tile = 8 blocks, requested in block 5) and its one barrier per tile
 // (behind block 4).  That row, not the bare chain row, is what the full 16x16x32 row (VAR 1 + 4 + 8) compares with.
@@ -62,6 +63,7 @@ constexpr Tab16 kT1 = {{0, 1, 2, 3, 5, 6, 8, 9}, {4, 4, 10, 10}, {7, 11, 7, 11, 
 template <int VAR>
 __global__ __launch_bounds__(256, 1) void k16(const _Float16* __restrict__ rnd, const _Float16* __restrict__ img, float* out, long long* cyc, int tiles) {
   constexpr bool CHAIN = VAR & 1, SAMEACC = VAR & 2, LDSRD = VAR & 4, DMA = VAR & 8, TAB1 = (VAR & 32) != 0;
+  constexpr bool TWO = (VAR & 512) != 0;
   constexpr bool NOEXP = (VAR & 64) != 0, NOCVT = (VAR & 128) != 0, NOMIX = (VAR & 256) != 0;  // parts of the chain compiled out
   constexpr Tab16 T = TAB1 ? kT1 : kT0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -102,8 +104,8 @@ __global__ __launch_bounds__(256, 1) void k16(const _Float16* __restrict__ rnd, 
   for (int u = 0; u < 4; ++u)
     for (int q = 0; q < 8; ++q) wr[u][q >> 2][q & 3] = -0.5f * (float)(q + 1) - 1e-3f * lane - 0.1f * u;
   const long long t0 = __builtin_readcyclecounter();
-  for (int t = 0; t < tiles; ++t) {
-    const int buf = t & 1;
+  auto tile = [&](auto bc, const int t) {  // bc: the tile's buffer, t & 1 -- an int, or (TWO) a constant
+    const int buf = bc;
     const char* tb = base + buf * 20480;
     auto body = [&](auto uc) {
       constexpr int u = decltype(uc)::value;   // unit of the tile: column half jh, row tile it
@@ -170,6 +172,14 @@ __global__ __launch_bounds__(256, 1) void k16(const _Float16* __restrict__ rnd, 
     body(std::integral_constant<int, 13>{});
     body(std::integral_constant<int, 14>{});
     body(std::integral_constant<int, 15>{});
+  };
+  if (TWO) {
+    for (int t = 0; t + 1 < tiles; t += 2) {  // (the tile counts of main() are even)
+      tile(std::integral_constant<int, 0>{}, t);
+      tile(std::integral_constant<int, 1>{}, t + 1);
+    }
+  } else {
+    for (int t = 0; t < tiles; ++t) tile(t & 1, t);
   }
   const long long t1 = __builtin_readcyclecounter();
   __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -390,6 +400,7 @@ int main() {
     run16<1 + 2>("16x16x32 + chain T0, accumulator-major", rnd, d);
     run16<1 + 4>("16x16x32 + chain T0 + LDS reads", rnd, d);
     run16<1 + 4 + 8>("16x16x32 + chain T0 + LDS reads + DMA/barrier", rnd, d);
+    run16<1 + 4 + 8 + 512>("16x16x32 + chain T0 + reads + DMA/barrier, two tiles/iter", rnd, d);
     run16<1 + 4 + 8 + 32>("16x16x32 + chain T1 + LDS reads + DMA/barrier", rnd, d);
     run16<4 + 8>("16x16x32 MFMAs + LDS reads + DMA/barrier", rnd, d);
     run16<1 + 2 + 128 + 256>("16x16x32 acc-major + exps only", rnd, d);
