@@ -921,12 +921,15 @@ int mfx_precond_apply(int dtype, int64_t n, int64_t rank, const void* lt, const 
               "mfx_precond_apply: workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
   Precond pc{lt, minv, shift, rank};
+  // vector b of v and z starts at b * ldv and b * ldz: 16-byte accesses need strides that keep the alignment of vector 0
   if (dtype == MFX_F32) {
-    Ctx<float> c(n, rank, p, pick_vec<float>(n, {v, z, lt}), s);
+    const bool strides_ok = ldv % VecWidth<float>::value == 0 && ldz % VecWidth<float>::value == 0;
+    Ctx<float> c(n, rank, p, strides_ok ? pick_vec<float>(n, {v, z, lt}) : 1, s);
     return precond_apply_t<float>(c, pc, (const float*)v, ldv, (float*)z, ldz, (float*)w.part_a, (float*)w.u, nullptr,
                                   nullptr);
   }
-  Ctx<double> c(n, rank, p, pick_vec<double>(n, {v, z, lt}), s);
+  const bool strides_ok = ldv % VecWidth<double>::value == 0 && ldz % VecWidth<double>::value == 0;
+  Ctx<double> c(n, rank, p, strides_ok ? pick_vec<double>(n, {v, z, lt}) : 1, s);
   return precond_apply_t<double>(c, pc, (const double*)v, ldv, (double*)z, ldz, (double*)w.part_a, (double*)w.u, nullptr,
                                  nullptr);
 }
