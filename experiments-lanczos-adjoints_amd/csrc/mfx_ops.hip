@@ -3,7 +3,7 @@
 // for DENSE, CSR and matrix-free RBF-Gram operators, plus the CALLBACK trampoline.
 //
 // The RBF kernels in this file are the generic VALU path (any dtype, any number of probes); the
-// fp32 MFMA path for wide probe batches lives in mfx_rbf_mfma.hip and is selected in rbf_apply().
+// matrix-core paths live in mfx_rbf_mfma.hip (matvec, selected in rbf_apply()) and mfx_rbf_mfma_grad.hip (parameter sweeps).
 #include <type_traits>
 
 #include "mfx_internal.h"

@@ -1,5 +1,6 @@
-// Host-side interface of the kernel-Gram operator across its three translation units: what mfx_ops.hip (carve, VALU kernels, path
-// switch) calls in mfx_rbf_mfma.hip (matrix-core kernels), what that file calls in mfx_rbf_fat.hip, and what they share to get there --
+// Host-side interface of the kernel-Gram operator across its four translation units: what mfx_ops.hip (carve, VALU kernels, path
+// switch) calls in mfx_rbf_mfma.hip (matrix-core matvec) and mfx_rbf_mfma_grad.hip (matrix-core parameter sweeps), what the matvec
+// file calls in mfx_rbf_fat.hip, and what they share to get there --
 // the padded-dimension dispatch, the run-time -> compile-time helpers of the launch sites and the layouts of the workspace regions.
 #pragma once
 #include <type_traits>
@@ -70,8 +71,8 @@ inline bool vec4_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int6
          (reinterpret_cast<uintptr_t>(b) % 16 == 0);
 }
 
-// ---- which kernels run (mfx_rbf_mfma.hip, next to the kernels the answers describe) ------------------------------------------
-enum class RbfApplyPath { valu, exact, h3 };    // VALU kernel | exact-fp32 MFMA | 3 x f16 split (fat-wave or h3 kernel)
+// ---- which kernels run (mfx_rbf_mfma.hip / mfx_rbf_mfma_grad.hip, next to the kernels the answers describe) --------------------
+enum class RbfApplyPath { valu, exact, h3 };    // VALU kernel | exact-fp32 MFMA | 3 x f16 split (fat-wave kernels or the h3 pair)
 enum class RbfGradPath { valu, exact, split };  // VALU sweep | exact-fp32 MFMA GEMM | 3 x f16 split GEMM
 RbfApplyPath rbf_apply_path(const mfx_operator* op, int64_t p);
 RbfGradPath rbf_grad_path(const mfx_operator* op, int64_t batch, bool have_hws);  // have_hws: the split-gradient region was carved
@@ -112,7 +113,7 @@ inline int64_t rbf_grad_h_ws_bytes(int64_t n, int64_t batch) { return rbf_grad_h
 // rows of (dpad + 2) doubles the matrix-core sweeps write into rbf_carve's gradient partials: one per workgroup
 int64_t rbf_mfma_grad_partial_rows(int64_t n);
 
-// ---- entry points of the matrix-core kernels (mfx_rbf_mfma.hip) --------------------------------------------------------------
+// ---- entry points of the matrix-core kernels (matvec: mfx_rbf_mfma.hip; parameter sweeps: mfx_rbf_mfma_grad.hip) --------------
 int rbf_mfma_apply(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* x, int64_t ldx,
                    float* y, int64_t ldy, int64_t p, hipStream_t stream);
 int rbf_mfma_apply_h3(const mfx_operator* op, const float* xs, const float* sq, int dpad, const float* x, int64_t ldx,
@@ -125,7 +126,7 @@ int rbf_mfma_grad_h(const mfx_operator* op, const float* xs, const float* sq, in
                     const float* R, int64_t ldr, int64_t batch, int64_t inner, double* partial, int64_t* nblocks_out, void* hws,
                     const float** scales_out, hipStream_t stream);
 
-// What one launch of the split matvec kernels (k_rbf_mfma_apply_h3, k_rbf_fat_apply) takes, in the kernels' parameter order;
+// What one launch of the split matvec kernels (k_rbf_h3_packed, k_rbf_h3_split, k_rbf_fat_apply) takes, in the kernels' parameter order;
 // pkv / pka are the uintx4 tile images of the pack region
 struct RbfMatvecArgs {
   const float *xs, *sq;

@@ -1,5 +1,6 @@
-// Pieces shared by the matrix-core RBF / Matern Gram kernels (mfx_rbf_mfma.hip, mfx_rbf_fat.hip): vector types, the kernel
-// family's constants, the hi / lo f16 split, the LDS-DMA copy and the layout of the pre-packed tile images.
+// Pieces shared by the matrix-core RBF / Matern Gram kernels (mfx_rbf_mfma.hip, mfx_rbf_mfma_grad.hip, mfx_rbf_fat.hip): vector
+// types, the kernel family's constants, the hi / lo f16 split and its power-of-two scale rule, the LDS-DMA
+// copy and the layout of the pre-packed tile images.
 #pragma once
 #include "mfx_internal.h"
 #include "mfx_rbf.h"
@@ -75,6 +76,19 @@ __device__ __forceinline__ void split_hi_lo(float x, float& hi, float& lo) {
 }
 
 
+// Power-of-two scale of an f16-split operand: 2^(14 - e) for |max| = f 2^e (1 for an all-zero row), so that the largest entry
+// becomes ~2^14.  Tiny / denormal rows (|max| < 2^-112): the exponent is clamped at 126, s and 1/s stay finite and normal.
+// The one statement of the rule: the matvec's per-vector scales and the gradient GEMM's per-operand scales both call it.
+__device__ __forceinline__ float row_scale_of(float m) {
+  int e = 0;
+  float s = 1.f;
+  if (m > 0.f && m < 3.0e38f) {
+    frexpf(m, &e);  // m = f * 2^e, f in [0.5, 1)
+    s = ldexpf(1.f, 14 - e < 126 ? 14 - e : 126);
+  }
+  return s;
+}
+
 // The reference clamps the squared distance at 0 before the exponential (util/gp_util.py:173).  In fp32 a computed squared
 // distance is negative only by round-off (|t| <~ 1e-6 of the operands' squares), so the clamp changes K_ij by at most that
 // round-off -- the same size as the error of every other entry -- while costing one VALU instruction per entry (7 % of the
@@ -91,7 +105,10 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// tile of the pipelined kernel: RbfTileH plus the f16 hi/lo image of the distance operand (DH variant).
+// tile of the pipelined ("h3") kernels: the fp32 column operand of the distance product `aj` (in-kernel-split kernel), its f16
+// [Ah | Ah | Al | 0] image `ajh` (packed kernel, and what k_pack_tiles writes) and the hi / lo f16 images of the probe tile.
+// `aj` is dead weight in the packed kernel's tile: it never touches it, but the bytes count towards that kernel's LDS size and
+// hence its residency -- trimming it is a layout change that wants a measurement of its own.
 // PADROW: the in-kernel split stores 8-byte pieces from many rows at once and needs the row pad; the pre-packed path copies the image
 // by LDS-DMA in 1 KiB pieces and wants [ajh | vhi | vlo] contiguous (the b128 fragment reads are conflict-free either way).
 template <int DPAD, int NB, int kTJ, bool PADROW = true>

@@ -1,14 +1,14 @@
 // libmfx: the matrix-core Gram matvec (3 x f16 split) as ONE wave per SIMD -- "fat waves", gfx950.
 //   W[i][b] = s * sum_j K(x_i, x_j) V[j][b] + noise V[i][b]   (util/gp_util.py:160-176,225-226,536-541 of the reference)
 //
-// Why (round-3 measurements): with two waves per SIMD -- the same-program kernel k_rbf_mfma_apply_h3 as well as
+// Why (round-3 measurements): with two waves per SIMD -- the same-program kernel k_rbf_h3_packed as well as
 // the producer / consumer split (round 3; tools/experiments/pc_matvec/) -- the matrix pipe idles a third of the time: a wave's MFMA and another wave's
 // VALU instruction compete for the SIMD's one vector issue port, and neither wave can see the other's schedule.  ONE wave that
 // owns the SIMD can: tools/valu_mix_bench.hip runs 14 MFMAs plus the whole exp / hi-lo split chain of a 32 x 32 block in 470
 // cycles (452 for the MFMAs alone) when every VALU instruction is placed behind a chosen MFMA so that
 //   * no MFMA gap carries more than ~24 issue cycles of VALU work (v_exp_f32 = 8, the others 4) and at most two v_exp,
 //   * no instruction follows its producer within one gap (exp -> cvt hi -> fma_mix -> cvt lo, one gap apart each),
-// against 532 for the "pair by pair" order of the h3 kernel.  That placement is the table kSplit below.
+// against 532 for the "pair by pair" order of the h3 kernels.  That placement is the table kSplit below.
 //
 // Shapes: RBF, d <= 16 (two distance MFMAs per block for d <= 8, three for d = 9 .. 12 -- BASELINE config 2 has d = 9 --, four for d = 13 .. 16),
 // any number of vectors.

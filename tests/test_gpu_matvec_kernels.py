@@ -1,6 +1,6 @@
 """The matrix-core Gram matvec kernels against the fp64 NumPy oracle: the fat-wave kernel (`k_rbf_fat_apply`,
 csrc/mfx_rbf_fat.hip: the default for RBF with d <= 16 -- BASELINE config 4's matvec and config 2's -- in its two forms, chunks of 64 vectors and,
-for at most 32 vectors, one 32-probe block) and the same-program kernel `k_rbf_mfma_apply_h3` (every other shape, and
+for at most 32 vectors, one 32-probe block) and the same-program kernel `k_rbf_h3_packed` (every other shape, and
 MFX_RBF_FAT=0).
 
 What is specific to these kernels and therefore tested here: two probe chunks with a ragged second one, ragged n (last tile and
@@ -31,9 +31,12 @@ DEV = torch.device("cuda:0")
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _setup(n, d, p, kernel, ard, seed):
+def _setup(n, d, p, kernel, ard, seed, outlier=False):
     rng = np.random.default_rng(seed)
     X = rng.standard_normal((n, d))
+    if outlier:  # one point far from all others: |x / l|^2 ~ 1e5 > 6e4, so k_pack_tiles raises the f16 range flag
+        X[17] = 0.0
+        X[17, 0] = 400.0
     raw = (rng.standard_normal(d) * 0.2 + 0.8 if ard else np.array(0.9), np.array(0.4), np.array(-1.0))
     V = rng.standard_normal((p, n)) * np.exp(rng.standard_normal((p, 1)) * 3.0)  # rows of very different magnitude
     o = orc.RbfGramOp(X, noise_minval=1e-4, kernel=kernel, eps=float(torch.finfo(torch.float32).eps))
@@ -55,6 +58,28 @@ def test_pc_matvec_against_the_oracle(kernel, n, d, p, ard):
     o, op, raw, params, V = _setup(n, d, p, kernel, ard, seed=n + p)
     y = op(torch.tensor(V, dtype=torch.float32, device=DEV), *params)
     assert _rel_err_rows(y, o.apply(V, *raw)) < 3e-5  # per vector, relative to its largest entry
+
+
+@pytest.mark.parametrize("kernel,outlier", [("rbf", False), ("matern32", False), ("matern32", True)])
+@pytest.mark.parametrize("p", [5, 40])
+@pytest.mark.parametrize("d", [3, 20])
+def test_n300_h3_pair_combinations_against_the_oracle(d, p, kernel, outlier):
+    """Every (kernel of the h3 pair, probe blocks NB, padded dimension) combination that a call can reach, through the host launch
+    path (wave count, LDS bytes, grid), at n = 300: four whole 64-column tiles plus a ragged one, across the 256-row workgroup
+    boundary of k_rbf_h3_split (one ragged 512-row workgroup of k_rbf_h3_packed).
+      no outlier: k_rbf_h3_packed does the work -- d = 3: DPAD <= 16 with NB = 1 (p = 5) and NB = 2 (p = 40), for the Matern kernel
+        and, in the MFX_RBF_FAT=0 re-run of this file, for RBF; d = 20: DPAD = 32, NB = 1 (chunks of 32 vectors) for both kernels.
+      outlier: the f16 range flag is up, k_rbf_h3_packed returns at once and k_rbf_h3_split does the work with the same NB.  Matern
+        only: there the self-distance of the far point is set exactly (the diagonal fix) and its kernel values with every other
+        point underflow to 0 in fp32 as they all but do in fp64, so the file's bound holds; RBF has no diagonal fix, and the far
+        point's fp32 self-distance (a difference of numbers ~1e5) would be off by ~1e-2.
+    The fifth built combination of k_rbf_h3_split, DPAD = 32 with NB = 2, needs a call without the pack region; mfx_op_apply
+    always carves one for an fp32 operator with d <= 32, so no call reaches it."""
+    o, op, raw, params, V = _setup(300, d, p, kernel, False, seed=300 + d + p, outlier=outlier)
+    y = op(torch.tensor(V, dtype=torch.float32, device=DEV), *params)
+    err = _rel_err_rows(y, o.apply(V, *raw))
+    print(f"d {d} p {p} {kernel} outlier {outlier}: err {err:.3e}")
+    assert err < 3e-5  # per vector, relative to its largest entry: the bound of every case of this file
 
 
 def _apply_block(op, cparams, V, row0, nrows):
@@ -126,7 +151,7 @@ def test_unsplit_sweep_with_chain_folds_and_bit_identity_of_the_two_kernels(tmp_
 
 
 def test_every_parity_case_on_the_same_program_kernel():
-    """The oracle, row-block and block-position cases of this file, re-run with MFX_RBF_FAT=0 (k_rbf_mfma_apply_h3 for every shape)."""
+    """The oracle, row-block and block-position cases of this file, re-run with MFX_RBF_FAT=0 (k_rbf_h3_packed for every shape)."""
     env = dict(os.environ, MFX_RBF_FAT="0")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-k", "oracle or row_blocks or position",
                         "-p", "no:cacheprovider"], cwd=os.path.dirname(HERE), env=env, capture_output=True, text=True, timeout=900)
