@@ -134,8 +134,8 @@ struct Carver {
 };
 
 // operator layer (mfx_ops.hip)
-// The rules of ONE operator kind (MFX_OP_*).  Each kind fills in one of these next to its kernels (dense, CSR, kernel-Gram, callback:
-// mfx_ops.hip; stencil: mfx_stencil.hip; GGN: mfx_ggn.hip; preconditioned: mfx_lowrank.hip); the drivers reach a kind through the generic functions below only.
+// The rules of ONE operator kind (MFX_OP_*).  Each kind fills in one of these next to its kernels (dense, CSR, callback:
+// mfx_ops.hip; kernel-Gram: mfx_rbf_valu.hip; stencil: mfx_stencil.hip; GGN: mfx_ggn.hip; preconditioned: mfx_lowrank.hip); the drivers reach a kind through the generic functions below only.
 struct OpKind {
   int (*check)(const mfx_operator* op);  // every refusal of the descriptor that is specific to the kind, before any launch
   // the gradient fields the kind does not have (NULL: every field but grads->x, the input gradient of a kernel-Gram operator)
@@ -178,6 +178,12 @@ struct PrepScope {
   PrepScope(const PrepScope&) = delete;
   PrepScope& operator=(const PrepScope&) = delete;
 };
+// Sets this thread's PrepScope aside for its lifetime: around a call out of the library (the callback kind), whose nested calls
+// are calls of their own.  Both live with the k_rbf_prep cache in mfx_rbf_valu.hip.
+struct PrepSuspend {
+  PrepSuspend();
+  ~PrepSuspend();
+};
 
 int op_apply(const mfx_operator* op, int mode, const void* x, int64_t ldx, const void* aux, int64_t ldaux, void* y, int64_t ldy,
              int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);
@@ -187,6 +193,7 @@ int op_vjp_params(const mfx_operator* op, const void* L, int64_t ldl, const void
                   int64_t batch, const mfx_op_grads* grads, void* ws, int64_t ws_bytes,
                   hipStream_t stream, int64_t inner = 1);
 
+// cross-covariance of a kernel-Gram operator (mfx_rbf_valu.hip)
 int64_t rbf_cross_ws_bytes(const mfx_operator* op, int64_t m);
 int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const void* v, int64_t ldv, void* y, int64_t ldy,
                    int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream);

@@ -1,13 +1,17 @@
-// Host-side interface of the kernel-Gram operator across its four translation units: what mfx_ops.hip (carve, VALU kernels, path
-// switch) calls in mfx_rbf_mfma.hip (matrix-core matvec) and mfx_rbf_mfma_grad.hip (matrix-core parameter sweeps), what the matvec
-// file calls in mfx_rbf_fat.hip, and what they share to get there --
-// the padded-dimension dispatch, the run-time -> compile-time helpers of the launch sites and the layouts of the workspace regions.
+// Host-side interface of the kernel-Gram operator across its four translation units, and to the operator table: what
+// mfx_rbf_valu.hip (carve, VALU kernels, path switch, the operator kind) calls in mfx_rbf_mfma.hip (matrix-core matvec) and
+// mfx_rbf_mfma_grad.hip (matrix-core parameter sweeps), what the matvec file calls in mfx_rbf_fat.hip, what they share to get there --
+// the padded-dimension dispatch, the run-time -> compile-time helpers of the launch sites and the layouts of the workspace regions --
+// and what mfx_ops.hip takes from the VALU file: the kind for its table.
 #pragma once
 #include <type_traits>
 
 #include "mfx_internal.h"
 
 namespace mfx {
+
+// ---- for the operator table (mfx_rbf_valu.hip) -----------------------------------------------------------------------------------
+const OpKind* gram_kind();
 
 // ---- padded dimension ----------------------------------------------------------------------------------------------------------
 constexpr int kRbfMaxD = 1024;  // wide inputs (d > 32): padded to a multiple of 32, k_rbf_apply_wide / k_rbf_grad_wide

@@ -159,7 +159,7 @@ def test_rbf_op_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kerne
                                    (300, 70, 8), (300, 90, 40), (301, 90, 40), (301, 100, 40), (301, 40, 40)])
 def test_rbf_wide_inputs_apply_and_param_sweep(dtype, tol, precision, ard, n, d, p, kernel):
     """d > 32: the reference's kernels take any input dimension (util/gp_util.py:151-184) and its UCI loaders reach d = 90 (song) and
-    385 (slice) (util/uci_util.py:85-99,303-310).  The wide kernels of csrc/mfx_ops.hip (distance as a small GEMM over chunks of the d
+    385 (slice) (util/uci_util.py:85-99,303-310).  The wide kernels of csrc/mfx_rbf_valu.hip (distance as a small GEMM over chunks of the d
     axis; with ARD the sweep's grid selects 32 lengthscale derivatives at a time) against the NumPy oracle: matvec, its transpose
     through autograd, all parameter gradients (d of them with ARD), the cross-covariance matvec of the posterior mean.  Every mode
     runs the same arithmetic here: VALU for d > 128 (and for fp64, few vectors at small n, the cross-covariance), the exact-fp32 matrix-core

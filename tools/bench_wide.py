@@ -1,4 +1,4 @@
-"""Gram matvec and parameter sweep at input dimensions beyond 16, for the record: the wide VALU kernels of csrc/mfx_ops.hip (d > 64; the
+"""Gram matvec and parameter sweep at input dimensions beyond 16, for the record: the wide VALU kernels of csrc/mfx_rbf_valu.hip (d > 64; the
 shapes of the reference's widest UCI loaders, util/uci_util.py: song d = 90, slice d = 385), the exact-fp32 matrix-core kernels
 (16 < d <= 64; sweep <= 32) and, for scale, d = 16 on the split kernels.    python tools/bench_wide.py"""
 import os, sys, time

@@ -7,7 +7,8 @@ Instructions are compared as llvm-objdump prints them, without addresses, encodi
 naming (k_rbf_cross_grad_dense[_wide]<.., TRANS>) are matched with the weight-source instantiations that replaced them
 (k_rbf_cross_grad[_wide]<.., DenseSrc<T, TRANS>> / <.., FactoredSrc<T>>), and the two overloads each of k_rbf_mfma_grad[_h] (runtime
 families <..>, Matern-5/2 <.., 3>) with the one template that replaced them (<.., false> / <.., true>).  For every function that differs, the register, LDS,
-scratch and spill figures of both builds are printed.  Exit status 1 if anything differs or is unmatched."""
+scratch and spill figures of both builds are printed, with the waves per SIMD that the registers allow, and at the end how many of
+them gained scratch or spills, changed their LDS size or lost a wave per SIMD.  Exit status 1 if anything differs or is unmatched."""
 import os
 import re
 import shutil
@@ -17,6 +18,11 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin/"
 KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count")
+
+
+def waves_per_simd(vgprs):
+    """gfx950: 512 registers per lane of a SIMD (vector and accumulation registers together), handed out in blocks of 8, at most 8 waves"""
+    return min(8, 512 // ((max(vgprs, 1) + 7) // 8 * 8))
 
 
 def canonical(name):
@@ -83,11 +89,21 @@ def main():
         print("only in old:", n)
     for n in sorted(set(new) - set(old)):
         print("only in new:", n)
+    worse = {"scratch or spills gained": 0, "LDS bytes changed": 0, "fewer waves per SIMD": 0}
     for n in sorted(differ):
         print("differs:", n)
+        a, b = old[n][1], new[n][1]
         for k in KEYS:
-            print(f"    {k}: {old[n][1].get(k)} -> {new[n][1].get(k)}")
+            print(f"    {k}: {a.get(k)} -> {b.get(k)}")
         print(f"    instructions: {old[n][0].count(chr(10)) + 1} -> {new[n][0].count(chr(10)) + 1}")
+        if a and b:
+            print(f"    waves per SIMD: {waves_per_simd(a['vgpr_count'])} -> {waves_per_simd(b['vgpr_count'])}")
+            worse["scratch or spills gained"] += (b["private_segment_fixed_size"] > a["private_segment_fixed_size"]
+                                                  or b["vgpr_spill_count"] > a["vgpr_spill_count"])
+            worse["LDS bytes changed"] += b["group_segment_fixed_size"] != a["group_segment_fixed_size"]
+            worse["fewer waves per SIMD"] += waves_per_simd(b["vgpr_count"]) < waves_per_simd(a["vgpr_count"])
+    if differ:
+        print("of the differing functions: " + ", ".join(f"{k} {v}" for k, v in worse.items()))
     return 1 if differ or set(old) ^ set(new) else 0
 
 
