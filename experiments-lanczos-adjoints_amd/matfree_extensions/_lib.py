@@ -220,6 +220,8 @@ SYMBOLS = {
     "mfx_gram_cross_vjp_dense": (_I, [_OPP, _P, _I64, _P, _I64, _GRP, _P, _P, _I64, _P]),
     "mfx_gram_block_workspace_bytes": (_I64, [_OPP, _I64, _I64]),
     "mfx_gram_block": (_I, [_OPP, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "mfx_rff_apply": (_I, [_I, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I, _P, _P, _I64, _I64, _P, _I64, _P]),
+    "mfx_rff_grad_x": (_I, [_I, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P]),
     "mfx_mlp_jac_workspace_bytes": (_I64, [_NETP, _I, _I64]),
     "mfx_mlp_jac_apply": (_I, [_NETP, _I, _P, _I64, _I64, _P, _P]),
     "mfx_mlp_jac_t_apply": (_I, [_NETP, _I, _P, _I64, _P, _I64, _P, _I64, _P]),

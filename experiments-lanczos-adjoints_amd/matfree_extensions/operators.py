@@ -1005,6 +1005,138 @@ class RbfGramOp(NativeOp):
         return st, g
 
 
+def _rows(t):
+    """(tensor, leading dimension) of a 2-d tensor as libmfx reads it: rows of unit stride, any row pitch >= the row length."""
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+class _RffFn(torch.autograd.Function):
+    """(S, n) = RandomFeatures.evaluate; backward = one mfx_rff_grad_x call onto x."""
+
+    @staticmethod
+    def forward(ctx, feats, x, ls, s):
+        x, ldx = _rows(x)
+        out = torch.empty((feats.num_samples, x.shape[0]), dtype=x.dtype, device=x.device)
+        _lib.check(_lib.get().mfx_rff_apply(*feats._args(x, ldx, ls, s), _lib.ptr(out), out.shape[1], _lib.stream_ptr(x.device)))
+        ctx.feats = feats
+        ctx.save_for_backward(x, ls, s)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, ls, s = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        g, ldg = _rows(dy)
+        dx = torch.empty((x.shape[0], x.shape[1]), dtype=x.dtype, device=x.device)
+        _lib.check(_lib.get().mfx_rff_grad_x(*ctx.feats._args(x, x.stride(0) if x.shape[0] > 1 else x.shape[1], ls, s), _lib.ptr(g), ldg,
+                                             _lib.ptr(dx), dx.shape[1], _lib.stream_ptr(x.device)))
+        return None, dx, None, None
+
+
+class RandomFeatures:
+    """S prior sample paths f_s(x) = c sum_j cos(omega_j . x / l + b_j) W_sj, c = sqrt(2 outputscale / m), of a stationary GP prior:
+    a random-Fourier-feature expansion whose frequencies follow the kernel's spectral density (the prior term of Matheron's
+    rule, gp_util.likelihood_condition_pathwise).  Frequencies omega (m, d) in units of 1 / lengthscale, phases b (m) and weights
+    W (S, m) are drawn ONCE, from a torch generator seeded from ``key`` as hutchinson.sampler_normal seeds its own (the same key gives
+    the same paths; they are drawn in fp64 on the device of ``like`` and cast to its dtype):
+
+        rbf                              omega ~ N(0, I)
+        matern12 / matern32 / matern52   omega = z sqrt(2 nu / g), z ~ N(0, I_d), g a sum of 2 nu = 1 / 3 / 5 squared standard
+                                         normals per feature (the multivariate-t spectral density of the MFX_KERNEL_* formulas)
+        b ~ U[0, 2 pi),  W ~ N(0, 1)
+
+    Explicit tensors ``omega=``, ``phase=``, ``weights=`` are taken as given instead (then the key is not used for them).
+
+    ``evaluate(x, lengthscale, outputscale)`` -> (S, n) for points x (n, d): mfx_rff_apply, the (n, m) feature matrix never stored.
+    lengthscale (() or (d,)) and outputscale arrive constrained, as RbfGramOp.constrain returns them.  Differentiable with respect to
+    x ONLY (backward: one mfx_rff_grad_x call).  Gradients with respect to the lengthscale, the outputscale, W, omega or b are
+    REFUSED: a tensor among them that requires grad raises ValueError.  CPU tensors raise; there is no fallback.
+
+    A finite m under-represents the prior variance far from the data: the sample variance of the paths is outputscale only in
+    expectation over the frequencies, with a relative spread of order 1 / sqrt(m)."""
+
+    _NU2 = {"rbf": None, "matern12": 1, "matern32": 3, "matern52": 5}
+
+    def __init__(self, key, *, kernel, dim, num_features, num_samples, like, omega=None, phase=None, weights=None):
+        if kernel not in self._NU2:
+            raise ValueError(f"kernel must be one of {sorted(self._NU2)}")
+        self.kernel, self.dim, self.num_features, self.num_samples = kernel, int(dim), int(num_features), int(num_samples)
+        if self.dim < 1 or self.dim > 1024:
+            raise ValueError(f"RandomFeatures: dim must be in 1..1024, got {dim}")
+        if self.num_features < 1 or self.num_samples < 1:
+            raise ValueError(f"RandomFeatures: num_features and num_samples must be >= 1, got {num_features} and {num_samples}")
+        _lib.dtype_code(like.dtype)
+        dtype, device = like.dtype, like.device
+        m, d, S = self.num_features, self.dim, self.num_samples
+        gen = None
+        if omega is None or phase is None or weights is None:
+            if key is None or torch.is_tensor(key):
+                missing = [name for name, t in (("omega", omega), ("phase", phase), ("weights", weights)) if t is None]
+                raise ValueError(f"RandomFeatures: {', '.join(missing)} must be drawn, which needs an integer key (or (seed, offset)), "
+                                 f"got {'a tensor' if torch.is_tensor(key) else None}; or pass them explicitly")
+            seed = key[0] ^ (key[1] * 0x9E3779B1) if isinstance(key, tuple) else key
+            gen = torch.Generator(device=device)
+            gen.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+
+        def normal(*shape):
+            return torch.randn(shape, dtype=torch.float64, device=device, generator=gen)
+
+        # the draws are consumed in a fixed order (z, g, b, W) whichever of them are given explicitly
+        if omega is None:
+            omega = normal(m, d)
+            nu2 = self._NU2[kernel]
+            if nu2 is not None:
+                omega = omega * torch.sqrt(nu2 / normal(m, nu2).square().sum(dim=1, keepdim=True))
+        if phase is None:
+            phase = 2 * math.pi * torch.rand((m,), dtype=torch.float64, device=device, generator=gen)
+        if weights is None:
+            weights = normal(S, m)
+        for name, t, shape in (("omega", omega, (m, d)), ("phase", phase, (m,)), ("weights", weights, (S, m))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"RandomFeatures: {name} {tuple(t.shape)} must be {shape}")
+            if t.device != device:
+                raise ValueError(f"RandomFeatures: {name} is on {t.device}, `like` on {device}")
+        self.omega, self.phase, self.weights = omega.to(dtype), phase.to(dtype), weights.to(dtype)
+        # what the kernel reads: frequencies and phases in revolutions (divided in fp64, then rounded once)
+        self._omega_rev = (self.omega.double() / (2 * math.pi)).to(dtype).contiguous()
+        self._phase_rev = (self.phase.double() / (2 * math.pi)).to(dtype).contiguous()
+        self._weights, self._ldw = _rows(self.weights.detach())  # rows of unit stride, made once and kept: the kernels read this tensor
+
+    def _args(self, x, ldx, ls, s):
+        W, ldw = self._weights, self._ldw
+        return (_lib.dtype_code(x.dtype), _lib.ptr(x), ldx, x.shape[0], self.dim, _lib.ptr(self._omega_rev), _lib.ptr(self._phase_rev),
+                self.num_features, _lib.ptr(ls), int(ls.numel() == self.dim), _lib.ptr(s),
+                _lib.ptr(W), ldw, self.num_samples)
+
+    def evaluate(self, x, lengthscale, outputscale):
+        """The S paths at the points x (n, d) -> (S, n); see the class docstring for what is differentiable and what is refused."""
+        for name, t in (("lengthscale", lengthscale), ("outputscale", outputscale), ("weights", self.weights), ("omega", self.omega),
+                        ("phase", self.phase)):
+            if t.requires_grad:
+                raise ValueError(f"RandomFeatures.evaluate: the gradient with respect to {name} is refused (only x is differentiable "
+                                 "through the random features); pass it detached")
+        _lib.require_device(x, lengthscale, outputscale, self.weights)
+        for name, t in (("x", x), ("lengthscale", lengthscale), ("outputscale", outputscale)):
+            if t.device != self.weights.device:
+                raise ValueError(f"RandomFeatures.evaluate: {name} is on {t.device}, the features on {self.weights.device}")
+        if x.dim() != 2 or x.shape[1] != self.dim or x.shape[0] < 1:
+            raise ValueError(f"RandomFeatures.evaluate: x {tuple(x.shape)} must be (n >= 1, {self.dim})")
+        dtype = self.weights.dtype
+        if x.dtype != dtype:
+            raise TypeError(f"RandomFeatures.evaluate: x must have the dtype of the features ({dtype}), got {x.dtype}")
+        ls = lengthscale.to(dtype).reshape(-1).contiguous()
+        if ls.numel() not in (1, self.dim):
+            raise ValueError(f"RandomFeatures.evaluate: lengthscale must have shape () or ({self.dim},)")
+        s = outputscale.to(dtype).reshape(-1)
+        if s.numel() != 1:
+            raise ValueError("RandomFeatures.evaluate: outputscale must be a scalar")
+        return _RffFn.apply(self, x, ls, s)
+
+
 class PreconditionedOp(NativeOp):
     """B(theta) = S A(theta) S with S = P^-1/2 for a ``low_rank.Preconditioner`` P = s I + L L^T that is held CONSTANT:
     log det A = log det P + tr log B, and the gradient of the right-hand side with respect to theta is that of log det A, so SLQ

@@ -15,7 +15,8 @@ import ctypes as C
 import math
 
 from .. import _lib, cg, hutchinson, lanczos, low_rank
-from ..operators import BoundOp, CallbackOp, NativeOp, PreconditionedOp, RbfGramOp, as_operator, softplus
+from ..operators import (BoundOp, CallbackOp, NativeOp, PreconditionedOp, RandomFeatures, RbfGramOp, RowShardedOp, as_operator,
+                         softplus)
 
 
 def constraint_greater_than(minval, /):
@@ -592,6 +593,108 @@ def likelihood_condition_p(matvec, solve_p, *, precondition, constrain):
         return condition_partial
 
     return likelihood, {"raw_noise": torch.empty(())}
+
+
+def _refuse_sharded_paths(A):
+    op = A.op if isinstance(A, BoundOp) else A
+    if isinstance(op, RowShardedOp):
+        raise NotImplementedError("pathwise posterior samples are not available on row-sharded operators (the random features and "
+                                  "K(xs, X) need the whole operator); use the operator itself, or shard the samples")
+
+
+class PathwisePosterior:
+    """S posterior sample paths of a GP by Matheron's rule, as functions: ``paths(xs)`` -> (S, len(xs)), and a second call at other
+    points evaluates the SAME S functions there.
+
+        f_s(x*) = m(x*) + phi(x*) . w_s + K(x*, X) v_s,    v_s = (K + noise I)^-1 (y - m(X) - phi(X) . w_s - eps_s)
+
+    The representer weights v (S, n) come from ONE batched solve at construction (``info["solve"]``) and are constants afterwards.
+    An evaluation is one RandomFeatures.evaluate, one RbfGramOp.cross_apply with the S weight vectors, and the mean; it is
+    differentiable with respect to xs (nothing else: the hyper-parameters must not require grad)."""
+
+    def __init__(self, cov_matvec, solve, mean, features, inputs, targets, *, key=None, eps=None):
+        _refuse_sharded_paths(cov_matvec)
+        op = cov_matvec.op if isinstance(cov_matvec, BoundOp) else None
+        if not isinstance(op, RbfGramOp):
+            raise TypeError("PathwisePosterior needs a bound RbfGramOp (gram_operator(X).bind(...)): the features follow its kernel")
+        if features.kernel != op.kernel or features.dim != op.d:
+            raise ValueError(f"PathwisePosterior: the features are for kernel {features.kernel!r} in {features.dim} dimensions, the "
+                             f"operator has kernel {op.kernel!r} in {op.d}")
+        S, n = features.num_samples, op.n
+        ls, s, nz = op.constrain(*cov_matvec.params)[:3]
+        self.cov_matvec, self.mean, self.features = cov_matvec, mean, features
+        self.lengthscale, self.outputscale = ls, s
+        with torch.no_grad():
+            prior = features.evaluate(op.X.detach(), ls, s)  # (S, n); refuses hyper-parameters that require grad
+            if eps is None:
+                if key is None or torch.is_tensor(key):
+                    raise ValueError("PathwisePosterior: the noise draws eps need an integer key (or (seed, offset)); or pass eps= "
+                                     f"({S}, {n}) explicitly")
+                eps = hutchinson.sampler_normal(op.X[:, 0], num=S)(key) * torch.sqrt(nz)
+            if tuple(eps.shape) != (S, n):
+                raise ValueError(f"PathwisePosterior: eps {tuple(eps.shape)} must be ({S}, {n})")
+            residual = (targets - _mean_array(mean, inputs)).reshape(1, n).to(prior.dtype)
+            weights, info = solve(cov_matvec, residual - prior - eps.to(prior.dtype))
+        self.weights, self.info = weights.detach(), {"solve": info}
+
+    def __call__(self, xs):
+        op = self.cov_matvec.op
+        xs = xs.to(op.X.dtype)
+        prior = self.features.evaluate(xs, self.lengthscale, self.outputscale)
+        update = op.cross_apply(xs, self.weights, *self.cov_matvec.params)
+        return _mean_array(self.mean, xs).reshape(1, -1) + prior + update
+
+
+def _pathwise_likelihood(matvec, solve_with, constrain, num_samples, num_features, key, omega, phase, weights, eps):
+    _refuse_sharded_paths(matvec)
+    if int(num_samples) < 1 or int(num_features) < 1:
+        raise ValueError(f"num_samples and num_features must be >= 1, got {num_samples} and {num_features}")
+    if torch.is_tensor(key):
+        raise ValueError("the key must be an integer seed (or (seed, offset)): explicit draws go in omega=, phase=, weights= and eps=")
+    explicit = {"omega": omega, "phase": phase, "weights": weights, "eps": eps}
+    if key is None and any(t is None for t in explicit.values()):
+        raise ValueError(f"key=None needs every draw given explicitly; missing: {', '.join(k for k, t in explicit.items() if t is None)}")
+    key_features, key_eps = (None, None) if key is None else hutchinson.split(key, 2)
+
+    def likelihood(inputs, mean, kernel, params: dict):
+        cov_matvec = _native_cov(matvec, inputs, kernel, constrain, params["raw_noise"])
+        features = RandomFeatures(key_features, kernel=cov_matvec.op.kernel, dim=cov_matvec.op.d, num_features=num_features,
+                                  num_samples=num_samples, like=cov_matvec.op.X, omega=omega, phase=phase, weights=weights)
+        solve = solve_with(cov_matvec, constrain(params["raw_noise"]), len(inputs))
+
+        def condition_partial(xs, targets):
+            paths = PathwisePosterior(cov_matvec, solve, mean, features, inputs, targets, key=key_eps, eps=eps)
+            return paths, paths.info
+
+        return condition_partial
+
+    return likelihood, {"raw_noise": torch.empty(())}
+
+
+def likelihood_condition_pathwise(matvec, solve, *, constrain, num_samples, num_features, key, omega=None, phase=None, weights=None,
+                                  eps=None):
+    """likelihood_condition that draws posterior FUNCTIONS: condition(xs, targets) -> (paths, info), paths a PathwisePosterior --
+    ``paths(points)`` -> (num_samples, len(points)), callable again at other points for the same functions, differentiable with
+    respect to the points.  ``xs`` is accepted for target_posterior's signature and not used: nothing is evaluated until
+    ``paths`` is called.  One batched solve with num_samples right-hand sides per condition() call (info["solve"]).
+
+    The num_features random features (operators.RandomFeatures) and the noise draws eps ~ N(0, noise I) come from ``key`` (split in
+    two); explicit ``omega=, phase=, weights=`` (m, d), (m,), (S, m) and ``eps=`` (S, n) -- the draws themselves, variance noise --
+    are taken as given.  Refused: a RowShardedOp (before any collective), hyper-parameters that require grad (ValueError from
+    RandomFeatures.evaluate).  Known limit: a finite num_features under-represents the prior variance far from the data."""
+    return _pathwise_likelihood(matvec, lambda _cov, _noise, _n: solve, constrain, num_samples, num_features, key, omega, phase, weights,
+                                eps)
+
+
+def likelihood_condition_pathwise_p(matvec, solve_p, *, precondition, constrain, num_samples, num_features, key, omega=None, phase=None,
+                                    weights=None, eps=None):
+    """likelihood_condition_pathwise with a preconditioned solve, as likelihood_condition_p."""
+
+    def solve_with(cov_matvec, noise, n):
+        pre, _info = precondition(low_rank.without_noise(cov_matvec), n)
+        return lambda A, B: solve_p(A, B, P=pre.bind(noise))
+
+    return _pathwise_likelihood(matvec, solve_with, constrain, num_samples, num_features, key, omega, phase, weights, eps)
 
 
 def _predictive_variance(cov_matvec, solve, xs, noise, observation_noise, chunk):

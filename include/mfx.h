@@ -688,6 +688,27 @@ int64_t mfx_gram_block_workspace_bytes(const mfx_operator* op, int64_t ma, int64
 int mfx_gram_block(const mfx_operator* op, const void* xa, int64_t ma, const void* xb, int64_t mb, void* out, int64_t ldo,
                    void* ws, int64_t ws_bytes, void* stream);
 
+/* The random-Fourier-feature prior path of a pathwise GP posterior sample (Matheron's rule), the (n, m) feature matrix never stored:
+ *   mfx_rff_apply   out[s * ldout + i] = c sum_{j<m} cos(2 pi (sum_{t<d} omega[j * d + t] x[i * ldx + t] / l_t + phase[j])) W[s * ldw + j]
+ *   mfx_rff_grad_x  dx[i * lddx + t]   = -2 pi c / l_t sum_{s<S} g[s * ldg + i] sum_{j<m} sin(2 pi (...)_ij) W[s * ldw + j] omega[j * d + t]
+ * with c = sqrt(2 outputscale / m).  x (n, d) row-major, leading dimension ldx; omega (m, d) contiguous and phase (m) in REVOLUTIONS
+ * (the kernel's spectral frequencies at unit lengthscale and the phases, both divided by 2 pi: the phase is reduced with fract() and
+ * goes to a cosine that takes revolutions, so phases of 10^4 and more lose nothing to the reduction); lengthscale: 1 (ard = 0) or d
+ * (ard = 1) device values and outputscale: 1 device value, already constrained, as the Gram operator gets them; W (S, m), g (S, n)
+ * and out (S, n) probe batches with leading dimensions ldw, ldg, ldout; dx (n, d), leading dimension lddx, is OVERWRITTEN.  All
+ * arrays in `dtype` (MFX_F32 / MFX_F64).  mfx_rff_grad_x is the vector-Jacobian product of mfx_rff_apply onto x: it recomputes the
+ * phases, keeps nothing from the forward, and sums within a row only.  Any n, m, S >= 1 and 1 <= d <= 1024; S beyond one chunk of
+ * samples is looped inside.  No workspace, no atomics, a fixed summation order: bit-identical from run to run.  16-byte loads of x
+ * and W are used when the pointer and the leading dimension allow them.
+ * Refuse before any launch with MFX_ERR_INVALID: an unknown dtype, a NULL array, n, m or S < 1, d outside 1..1024, ard not 0 / 1,
+ * ldx < d, ldw < m, ldout < n, ldg < n, lddx < d. */
+int mfx_rff_apply(int dtype, const void* x, int64_t ldx, int64_t n, int64_t d, const void* omega, const void* phase, int64_t m,
+                  const void* lengthscale, int ard, const void* outputscale, const void* W, int64_t ldw, int64_t S, void* out,
+                  int64_t ldout, void* stream);
+int mfx_rff_grad_x(int dtype, const void* x, int64_t ldx, int64_t n, int64_t d, const void* omega, const void* phase, int64_t m,
+                   const void* lengthscale, int ard, const void* outputscale, const void* W, int64_t ldw, int64_t S, const void* g,
+                   int64_t ldg, void* dx, int64_t lddx, void* stream);
+
 /* Per-kernel-class device timing with hipEvents recorded on the caller's stream (no host syncs
  * while enabled; events are read back in mfx_timing_read, which synchronises the events).
  * classes: 0 = operator apply, 1 = operator parameter-gradient sweep, 2 = Krylov vector kernels. */
