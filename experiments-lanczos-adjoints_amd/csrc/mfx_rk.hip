@@ -1,0 +1,413 @@
+// libmfx: fixed-step explicit Runge-Kutta solves of y' = A y with their discrete and continuous (backsolve) adjoints -- the
+// baselines of the reference's PDE work-precision study (util/pde_util.py:177-237) as native drivers.
+//
+//   Y_i = y + dt sum_{j<i} a_ij K_j,   K_i = A Y_i,   y+ = y + dt sum_i b_i K_i
+//
+// One kernel, k_rk_combine: out = c0 base + sum_j c_j V_j over up to 16 rows of a panel, the coefficients kernel arguments, zero
+// coefficients skipped through a wave-uniform mask; it forms the stage values, the update, the adjoint's Kbar_i, the scaled L rows
+// and the lambda accumulation.  (k_update of mfx_vec.h, behind mfx_basis_combine, reads its coefficients from device memory through an
+// LDS prologue and has no factor on its base term: serving host coefficients through it would add an upload per launch, so the
+// body is not shared; the thread-owned loads and stores are.)  The operator is applied through op_apply only.  A stage kernel that
+// fuses the combination into the stencil apply was measured and is slower or within the noise: tools/experiments/rk_fused_stage,
+// DESIGN.md section 3.4b.  No atomics anywhere.
+#include <math.h>
+
+#include "mfx_vec.h"
+
+namespace mfx {
+
+constexpr int kRkBaseBit = MFX_RK_MAX_STAGES;  // bit of RkCoef::mask that says "the base term is present"
+
+template <typename T>
+struct RkCoef {
+  unsigned mask;  // bit j < 16: c[j] != 0; bit 16: c0 != 0
+  T c0;
+  T c[MFX_RK_MAX_STAGES];
+};
+
+// the two steps of one element of a combination, in the order base, row 0, row 1, ...
+template <typename T>
+__device__ __forceinline__ T rk_scale(T c0, T base) {
+  return c0 * base;
+}
+template <typename T>
+__device__ __forceinline__ T rk_axpy(T c, T v, T acc) {
+  return fma(c, v, acc);
+}
+
+// out[b] = c0 base[b] + sum_j c_j rows[b][j]: grid = (slices, p), EPT elements per thread held in registers across the rows.
+// out may be base (every thread reads its own elements before it writes them).
+template <typename T, int VEC, int EPT>
+__global__ __launch_bounds__(kBlock) void k_rk_combine(RkCoef<T> k, const T* base, int64_t ldbase, const T* __restrict__ rows,
+                                                       int64_t rows_ldb, int64_t row_stride, T* out, int64_t ldout, int64_t n) {
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.y;
+  const int64_t slice0 = (int64_t)blockIdx.x * ((int64_t)blockDim.x * EPT);
+  T acc[EPT];
+  if (k.mask >> kRkBaseBit & 1u) {
+    load_own<T, VEC>(acc, base + b * ldbase, slice0, n, tid);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) acc[e] = rk_scale<T>(k.c0, acc[e]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) acc[e] = T(0);
+  }
+  const T* rb = rows + b * rows_ldb;
+#pragma unroll
+  for (int j = 0; j < MFX_RK_MAX_STAGES; ++j) {
+    if (k.mask >> j & 1u) {
+      T v[EPT];
+      load_own<T, VEC>(v, rb + (int64_t)j * row_stride, slice0, n, tid);
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) acc[e] = rk_axpy<T>(k.c[j], v[e], acc[e]);
+    }
+  }
+  store_own<T, VEC>(acc, out + b * ldout, slice0, n, tid);
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct RkGeom {  // what MFX_VEC_EPT_SWITCH reads
+  int vec, ept, wg, nblk;
+};
+
+template <typename T>
+struct RkCtx {
+  const mfx_operator* op;
+  const mfx_rk_tableau* tab;
+  int64_t n, p;
+  int s;
+  void* opws;
+  int64_t opws_bytes;
+  hipStream_t stream;
+};
+
+template <typename T>
+static RkCoef<T> rk_coef(double c0, bool has_base, const double* coef, int nrows) {
+  RkCoef<T> k{};
+  k.c0 = (T)c0;
+  if (has_base && c0 != 0.0) k.mask |= 1u << kRkBaseBit;
+  for (int j = 0; j < nrows; ++j) {
+    k.c[j] = (T)coef[j];
+    if (coef[j] != 0.0) k.mask |= 1u << j;
+  }
+  return k;
+}
+
+// out = c0 base + sum_{j < nrows} coef[j] rows[:, j, :]   (base NULL: no base term; nrows 0: no rows)
+template <typename T>
+static int rk_combine(const RkCtx<T>& c, double c0, const T* base, int64_t ldbase, const double* coef, int nrows, const T* rows,
+                      int64_t rows_ldb, int64_t row_stride, T* out, int64_t ldout) {
+  const RkCoef<T> k = rk_coef<T>(c0, base != nullptr, coef, nrows);
+  constexpr int V = VecWidth<T>::value;
+  RkGeom g;
+  g.vec = pick_vec<T>(c.n, {base, rows, out});
+  if (c.p > 1 && (ldbase % V || rows_ldb % V || ldout % V)) g.vec = 1;
+  if (row_stride % V) g.vec = 1;
+  g.wg = pick_wg(c.n, c.p);
+  g.ept = kEpt;
+  g.nblk = (int)((c.n + (int64_t)g.wg * kEpt - 1) / ((int64_t)g.wg * kEpt));
+  if (g.vec > 1 && g.wg == kBlock && (int64_t)g.nblk * c.p < 128) {  // Ctx::fine: one 16-byte load per thread and row
+    g.ept = V;
+    g.nblk = (int)((c.n + (int64_t)g.wg * V - 1) / ((int64_t)g.wg * V));
+  }
+  const dim3 grid((unsigned)g.nblk, (unsigned)c.p);
+  if (!base) base = out;  // never read (the base bit is clear)
+  if (!rows) rows = out;  // never read (no row bit is set)
+  MFX_VEC_EPT_SWITCH(g, (k_rk_combine<T, VEC, EPT><<<grid, g.wg, 0, c.stream>>>(k, base, ldbase, rows, rows_ldb, row_stride, out, ldout, c.n)));
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+// stage i of a step of size h from `base`: K[:, i, :] = A (base + h sum_{j<i} a_ij K[:, j, :]); the stage value goes to yrow when
+// that is asked for, else to ytmp
+template <typename T>
+static int rk_stage(const RkCtx<T>& c, int i, double h, const T* base, int64_t ldbase, T* K, T* yrow, int64_t ldyrow, T* ytmp) {
+  const int64_t ldk = (int64_t)c.s * c.n;
+  double coef[MFX_RK_MAX_STAGES] = {};
+  bool any = false;
+  for (int j = 0; j < i; ++j) {
+    coef[j] = h * c.tab->a[i][j];
+    any = any || coef[j] != 0.0;
+  }
+  T* Ki = K + (int64_t)i * c.n;
+  const T* x = base;
+  int64_t ldx = ldbase;
+  if (any || yrow) {  // Y_1 = y needs no combination unless the stage value itself is wanted
+    T* dst = yrow ? yrow : ytmp;
+    const int64_t lddst = yrow ? ldyrow : c.n;
+    MFX_TRY(rk_combine<T>(c, 1.0, base, ldbase, coef, i, K, ldk, c.n, dst, lddst));
+    x = dst;
+    ldx = lddst;
+  }
+  return op_apply(c.op, 0, x, ldx, nullptr, 0, Ki, ldk, c.p, c.opws, c.opws_bytes, c.stream);
+}
+
+// the update of a step of size h: out = base + h sum_i b_i K[:, i, :]
+template <typename T>
+static int rk_advance(const RkCtx<T>& c, double h, const T* base, int64_t ldbase, const T* K, T* out, int64_t ldout) {
+  double coef[MFX_RK_MAX_STAGES] = {};
+  for (int i = 0; i < c.s; ++i) coef[i] = h * c.tab->b[i];
+  return rk_combine<T>(c, 1.0, base, ldbase, coef, c.s, K, (int64_t)c.s * c.n, c.n, out, ldout);
+}
+
+struct RkWs {
+  void *y, *ytmp, *lam, *K, *Y, *Kbar, *Ybar, *opws;  // Kbar / Ybar: the backsolve's lambda stages and their images under A^T
+  int64_t opws_bytes;
+};
+
+// mode 0: solve, 1: discrete adjoint, 2: backsolve
+static int64_t rk_carve(const mfx_operator* op, int s, int64_t n, int64_t p, int mode, void* ws, int64_t ws_bytes, RkWs* out) {
+  const int64_t es = (int64_t)dtype_size(op->dtype), vec = p * n * es, panel = p * s * n * es;
+  Carver cv(ws, ws_bytes);
+  RkWs w{};
+  if (mode != 1) w.y = cv.take(vec);
+  w.ytmp = cv.take(vec);
+  if (mode != 0) w.lam = cv.take(vec);
+  w.K = cv.take(panel);
+  if (mode != 0) {
+    w.Y = cv.take(panel);
+    w.Kbar = cv.take(panel);
+    w.Ybar = cv.take(panel);
+  }
+  w.opws_bytes = op_workspace_bytes(op, mode == 0 ? 1 : p * s, p);
+  w.opws = cv.take(w.opws_bytes);
+  if (out) *out = w;
+  return cv.off;
+}
+
+template <typename T>
+static int rk_solve_t(const RkCtx<T>& c, const double* dts, int64_t nsteps, const T* y0, int64_t ldy0, T* y1, int64_t ldy1, T* ys,
+                      const RkWs& w) {
+  const int64_t n = c.n, ldys = (nsteps + 1) * n;
+  if (ys) MFX_TRY(copy_rows_async(ys, ldys * sizeof(T), y0, ldy0 * sizeof(T), n * sizeof(T), c.p, c.stream));
+  for (int64_t step = 0; step < nsteps; ++step) {
+    const T* cur;
+    T* nxt;
+    int64_t ldcur, ldnxt;
+    if (ys) {
+      cur = ys + step * n, nxt = ys + (step + 1) * n, ldcur = ldnxt = ldys;
+    } else {
+      cur = step == 0 ? y0 : (const T*)w.y, ldcur = step == 0 ? ldy0 : n;
+      nxt = step == nsteps - 1 ? y1 : (T*)w.y, ldnxt = step == nsteps - 1 ? ldy1 : n;
+    }
+    for (int i = 0; i < c.s; ++i) MFX_TRY(rk_stage<T>(c, i, dts[step], cur, ldcur, (T*)w.K, nullptr, 0, (T*)w.ytmp));
+    MFX_TRY(rk_advance<T>(c, dts[step], cur, ldcur, (const T*)w.K, nxt, ldnxt));
+  }
+  if (ys) MFX_TRY(copy_rows_async(y1, ldy1 * sizeof(T), ys + nsteps * n, ldys * sizeof(T), n * sizeof(T), c.p, c.stream));
+  return MFX_OK;
+}
+
+template <typename T>
+static int rk_adjoint_t(const RkCtx<T>& c, const double* dts, int64_t nsteps, const T* ys, const T* dy1, int64_t lddy1, T* dy0,
+                        int64_t lddy0, const mfx_op_grads* grads, const RkWs& w) {
+  const int64_t n = c.n, ldys = (nsteps + 1) * n, ldp = (int64_t)c.s * n;
+  const int s = c.s;
+  const bool native = op_kind(c.op)->native;
+  T *lam = (T*)w.lam, *K = (T*)w.K, *Y = (T*)w.Y, *Kbar = (T*)w.Kbar, *Ybar = (T*)w.Ybar;
+  MFX_TRY(copy_rows_async(lam, n * sizeof(T), dy1, lddy1 * sizeof(T), n * sizeof(T), c.p, c.stream));
+  double ones[MFX_RK_MAX_STAGES];
+  for (int i = 0; i < MFX_RK_MAX_STAGES; ++i) ones[i] = 1.0;
+  for (int64_t step = nsteps - 1; step >= 0; --step) {
+    const double dt = dts[step];
+    const T* cur = ys + step * n;
+    for (int i = 0; i < s; ++i) MFX_TRY(rk_stage<T>(c, i, dt, cur, ldys, K, Y + (int64_t)i * n, ldp, (T*)w.ytmp));
+    for (int i = s - 1; i >= 0; --i) {
+      double coef[MFX_RK_MAX_STAGES] = {};
+      for (int j = i + 1; j < s; ++j) coef[j] = dt * c.tab->a[j][i];
+      MFX_TRY(rk_combine<T>(c, dt * c.tab->b[i], lam, n, coef, s, Ybar, ldp, n, Kbar + (int64_t)i * n, ldp));
+      MFX_TRY(op_apply(c.op, 1, Kbar + (int64_t)i * n, ldp, Y + (int64_t)i * n, ldp, Ybar + (int64_t)i * n, ldp, c.p, c.opws, c.opws_bytes,
+                       c.stream));
+    }
+    if (native && grads) MFX_TRY(op_vjp_params(c.op, Kbar, n, Y, n, c.p * s, grads, c.opws, c.opws_bytes, c.stream));
+    if (step > 0) {
+      MFX_TRY(rk_combine<T>(c, 1.0, lam, n, ones, s, Ybar, ldp, n, lam, n));
+    } else if (dy0) {
+      MFX_TRY(rk_combine<T>(c, 1.0, lam, n, ones, s, Ybar, ldp, n, dy0, lddy0));
+    }
+  }
+  return MFX_OK;
+}
+
+template <typename T>
+static int rk_backsolve_t(const RkCtx<T>& c, const double* dts, int64_t nsteps, const T* y1, int64_t ldy1, const T* dy1, int64_t lddy1,
+                          T* dy0, int64_t lddy0, const mfx_op_grads* grads, const RkWs& w) {
+  const int64_t n = c.n, ldp = (int64_t)c.s * n;
+  const int s = c.s;
+  const bool native = op_kind(c.op)->native;
+  T *y = (T*)w.y, *lam = (T*)w.lam, *Ky = (T*)w.K, *Y = (T*)w.Y, *Lam = (T*)w.Kbar, *Kl = (T*)w.Ybar, *tmp = (T*)w.ytmp;
+  MFX_TRY(copy_rows_async(y, n * sizeof(T), y1, ldy1 * sizeof(T), n * sizeof(T), c.p, c.stream));
+  MFX_TRY(copy_rows_async(lam, n * sizeof(T), dy1, lddy1 * sizeof(T), n * sizeof(T), c.p, c.stream));
+  for (int64_t step = nsteps - 1; step >= 0; --step) {
+    const double dt = dts[step], h = -dt;
+    for (int i = 0; i < s; ++i) MFX_TRY(rk_stage<T>(c, i, h, y, n, Ky, Y + (int64_t)i * n, ldp, tmp));
+    // lam' = -A^T lam with step h: Lam_i = lam + dt sum_{j<i} a_ij (A^T Lam_j), lam+ = lam + dt sum_i b_i (A^T Lam_i)
+    for (int i = 0; i < s; ++i) {
+      double coef[MFX_RK_MAX_STAGES] = {};
+      for (int j = 0; j < i; ++j) coef[j] = dt * c.tab->a[i][j];
+      T* Li = Lam + (int64_t)i * n;
+      MFX_TRY(rk_combine<T>(c, 1.0, lam, n, coef, i, Kl, ldp, n, Li, ldp));
+      const T* aux = Y + (int64_t)i * n;
+      int64_t ldaux = ldp;
+      if (!native) {  // a callback accumulates x^T dA aux inside the application: the quadrature weight -h b_i goes onto aux
+        MFX_TRY(rk_combine<T>(c, dt * c.tab->b[i], aux, ldp, nullptr, 0, nullptr, 0, 0, tmp, n));
+        aux = tmp;
+        ldaux = n;
+      }
+      MFX_TRY(op_apply(c.op, 1, Li, ldp, aux, ldaux, Kl + (int64_t)i * n, ldp, c.p, c.opws, c.opws_bytes, c.stream));
+    }
+    if (native && grads) {  // thetabar += sum_i (-h b_i Lam_i)^T dA Y_i
+      for (int i = 0; i < s; ++i) {
+        T* Li = Lam + (int64_t)i * n;
+        MFX_TRY(rk_combine<T>(c, dt * c.tab->b[i], Li, ldp, nullptr, 0, nullptr, 0, 0, Li, ldp));
+      }
+      MFX_TRY(op_vjp_params(c.op, Lam, n, Y, n, c.p * s, grads, c.opws, c.opws_bytes, c.stream));
+    }
+    MFX_TRY(rk_advance<T>(c, h, y, n, Ky, y, n));
+    if (step > 0) {
+      MFX_TRY(rk_advance<T>(c, dt, lam, n, Kl, lam, n));
+    } else if (dy0) {
+      MFX_TRY(rk_advance<T>(c, dt, lam, n, Kl, dy0, lddy0));
+    }
+  }
+  return MFX_OK;
+}
+
+static int rk_check_tableau(const mfx_rk_tableau* tab) {
+  MFX_REQUIRE(tab != nullptr, MFX_ERR_INVALID, "Runge-Kutta tableau is NULL");
+  MFX_REQUIRE(tab->stages >= 1 && tab->stages <= MFX_RK_MAX_STAGES, MFX_ERR_INVALID, "Runge-Kutta tableau: %d stages, 1..%d expected",
+              tab->stages, MFX_RK_MAX_STAGES);
+  for (int i = 0; i < tab->stages; ++i) {
+    MFX_REQUIRE(std::isfinite(tab->b[i]), MFX_ERR_INVALID, "Runge-Kutta tableau: b[%d] is not finite", i);
+    for (int j = 0; j < tab->stages; ++j) {
+      MFX_REQUIRE(std::isfinite(tab->a[i][j]), MFX_ERR_INVALID, "Runge-Kutta tableau: a[%d][%d] is not finite", i, j);
+      MFX_REQUIRE(j < i || tab->a[i][j] == 0.0, MFX_ERR_INVALID,
+                  "Runge-Kutta tableau: a[%d][%d] = %g on or above the diagonal (explicit methods only)", i, j, tab->a[i][j]);
+    }
+  }
+  return MFX_OK;
+}
+
+// every refusal that the three drivers share, in the order of include/mfx.h
+static int rk_check(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, int64_t n, int64_t p,
+                    const mfx_op_grads* grads, int flags) {
+  MFX_TRY(check_op(op));
+  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "the Runge-Kutta drivers take the whole operator (nrows = 0): there is no row-sharded form");
+  MFX_TRY(rk_check_tableau(tab));
+  MFX_REQUIRE(nsteps >= 1, MFX_ERR_INVALID, "nsteps = %lld must be at least 1", (long long)nsteps);
+  MFX_REQUIRE(p >= 1, MFX_ERR_INVALID, "p = %lld must be at least 1", (long long)p);
+  MFX_REQUIRE(n >= 1 && op->n == n, MFX_ERR_INVALID, "operator size %lld != n = %lld", (long long)op->n, (long long)n);
+  MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "p = %lld exceeds the grid limit 65535", (long long)p);
+  MFX_REQUIRE(dts != nullptr, MFX_ERR_INVALID, "dts is NULL");
+  for (int64_t i = 0; i < nsteps; ++i) MFX_REQUIRE(std::isfinite(dts[i]), MFX_ERR_INVALID, "dts[%lld] is not finite", (long long)i);
+  MFX_REQUIRE(flags == 0, MFX_ERR_INVALID, "unknown flag bits 0x%x (no flag is defined)", flags);
+  if (grads) {
+    MFX_REQUIRE(grads->x == nullptr, MFX_ERR_UNSUPPORTED,
+                "the Runge-Kutta adjoints do not sweep the input gradient of a kernel-Gram operator (grads->x)");
+    MFX_TRY(check_op_grads(op, grads, false));
+  }
+  return MFX_OK;
+}
+
+static GraphKey rk_key(int fn_id, const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, int64_t n,
+                       int64_t p, const mfx_op_grads* grads, int flags, const void* ws, int64_t ws_bytes, const void* stream) {
+  GraphKey key;
+  key.add(fn_id).add(*op).add(n).add(p).add(nsteps).add(flags).add(ws).add(ws_bytes).add(stream);
+  if (op_kind(op)->graph_key) op_kind(op)->graph_key(op, key);
+  key.add(tab->stages);
+  for (int i = 0; i < tab->stages; ++i) {
+    key.add(tab->b[i]);
+    for (int j = 0; j < i; ++j) key.add(tab->a[i][j]);
+  }
+  for (int64_t i = 0; i < nsteps; ++i) key.add(dts[i]);  // a step size is baked into the kernel arguments of its launches
+  const mfx_op_grads none{};
+  key.add(grads ? *grads : none).add(grads != nullptr);
+  return key;
+}
+
+template <typename T>
+static RkCtx<T> rk_ctx(const mfx_operator* op, const mfx_rk_tableau* tab, int64_t n, int64_t p, const RkWs& w, hipStream_t st) {
+  RkCtx<T> c;
+  c.op = op, c.tab = tab, c.n = n, c.p = p, c.s = tab->stages;
+  c.opws = w.opws, c.opws_bytes = w.opws_bytes, c.stream = st;
+  return c;
+}
+
+}  // namespace mfx
+
+using namespace mfx;
+
+extern "C" {
+
+int64_t mfx_rk_workspace_bytes(const mfx_operator* op, const mfx_rk_tableau* tab, int64_t n, int64_t p, int adjoint) {
+  if (!op || adjoint < 0 || adjoint > 2 || !tab || tab->stages < 1 || tab->stages > MFX_RK_MAX_STAGES || n < 1 || p < 1) return -1;
+  if (check_op(op) != MFX_OK || op->n != n) return -1;
+  return rk_carve(op, tab->stages, n, p, adjoint, nullptr, 0, nullptr);
+}
+
+#define MFX_RK_PROLOGUE(mode)                                                                                                   \
+  RkWs w;                                                                                                                       \
+  const int64_t need = rk_carve(op, tab->stages, n, p, mode, ws, ws_bytes, &w);                                                  \
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "workspace too small: %lld bytes given, %lld needed", (long long)ws_bytes, \
+              (long long)need);                                                                                                 \
+  hipStream_t s = static_cast<hipStream_t>(stream);                                                                             \
+  PrepScope prep_scope
+
+int mfx_rk_solve(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* y0, int64_t ldy0,
+                 int64_t n, int64_t p, void* y1, int64_t ldy1, void* ys, int flags, void* ws, int64_t ws_bytes, void* stream) {
+  MFX_TRY(rk_check(op, tab, dts, nsteps, n, p, nullptr, flags));
+  MFX_REQUIRE(y0 && y1, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(ldy0 >= n && ldy1 >= n, MFX_ERR_INVALID, "leading dimensions %lld, %lld are shorter than n = %lld", (long long)ldy0,
+              (long long)ldy1, (long long)n);
+  MFX_RK_PROLOGUE(0);
+  GraphKey key = rk_key(1, op, tab, dts, nsteps, n, p, nullptr, flags, ws, ws_bytes, stream);
+  key.add(y0).add(ldy0).add(y1).add(ldy1).add(ys);
+  return run_graphed(op_kind(op)->native, key, s, [&](hipStream_t st) {
+    if (op->dtype == MFX_F32)
+      return rk_solve_t<float>(rk_ctx<float>(op, tab, n, p, w, st), dts, nsteps, (const float*)y0, ldy0, (float*)y1, ldy1,
+                               (float*)ys, w);
+    return rk_solve_t<double>(rk_ctx<double>(op, tab, n, p, w, st), dts, nsteps, (const double*)y0, ldy0, (double*)y1, ldy1,
+                              (double*)ys, w);
+  });
+}
+
+int mfx_rk_adjoint(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* ys, int64_t n,
+                   int64_t p, const void* dy1, int64_t lddy1, void* dy0, int64_t lddy0, const mfx_op_grads* grads, int flags, void* ws,
+                   int64_t ws_bytes, void* stream) {
+  MFX_TRY(rk_check(op, tab, dts, nsteps, n, p, grads, flags));
+  MFX_REQUIRE(ys && dy1, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(lddy1 >= n && (!dy0 || lddy0 >= n), MFX_ERR_INVALID, "leading dimensions %lld, %lld are shorter than n = %lld",
+              (long long)lddy1, (long long)lddy0, (long long)n);
+  MFX_RK_PROLOGUE(1);
+  GraphKey key = rk_key(2, op, tab, dts, nsteps, n, p, grads, flags, ws, ws_bytes, stream);
+  key.add(ys).add(dy1).add(lddy1).add(dy0).add(lddy0);
+  return run_graphed(op_kind(op)->native, key, s, [&](hipStream_t st) {
+    if (op->dtype == MFX_F32)
+      return rk_adjoint_t<float>(rk_ctx<float>(op, tab, n, p, w, st), dts, nsteps, (const float*)ys, (const float*)dy1, lddy1,
+                                 (float*)dy0, lddy0, grads, w);
+    return rk_adjoint_t<double>(rk_ctx<double>(op, tab, n, p, w, st), dts, nsteps, (const double*)ys, (const double*)dy1,
+                                lddy1, (double*)dy0, lddy0, grads, w);
+  });
+}
+
+int mfx_rk_backsolve(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* y1, int64_t ldy1,
+                     int64_t n, int64_t p, const void* dy1, int64_t lddy1, void* dy0, int64_t lddy0, const mfx_op_grads* grads,
+                     int flags, void* ws, int64_t ws_bytes, void* stream) {
+  MFX_TRY(rk_check(op, tab, dts, nsteps, n, p, grads, flags));
+  MFX_REQUIRE(y1 && dy1, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(ldy1 >= n && lddy1 >= n && (!dy0 || lddy0 >= n), MFX_ERR_INVALID, "leading dimensions %lld, %lld, %lld are shorter than n = %lld",
+              (long long)ldy1, (long long)lddy1, (long long)lddy0, (long long)n);
+  MFX_RK_PROLOGUE(2);
+  GraphKey key = rk_key(3, op, tab, dts, nsteps, n, p, grads, flags, ws, ws_bytes, stream);
+  key.add(y1).add(ldy1).add(dy1).add(lddy1).add(dy0).add(lddy0);
+  return run_graphed(op_kind(op)->native, key, s, [&](hipStream_t st) {
+    if (op->dtype == MFX_F32)
+      return rk_backsolve_t<float>(rk_ctx<float>(op, tab, n, p, w, st), dts, nsteps, (const float*)y1, ldy1, (const float*)dy1,
+                                   lddy1, (float*)dy0, lddy0, grads, w);
+    return rk_backsolve_t<double>(rk_ctx<double>(op, tab, n, p, w, st), dts, nsteps, (const double*)y1, ldy1,
+                                  (const double*)dy1, lddy1, (double*)dy0, lddy0, grads, w);
+  });
+}
+
+}  // extern "C"

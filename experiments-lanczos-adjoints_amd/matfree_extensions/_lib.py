@@ -25,6 +25,7 @@ GGN_MAX_LAYERS = 8
 REORTHO_NONE, REORTHO_FULL = 0, 1
 RBF_FP32, RBF_F16X3_MATVEC, RBF_F16X3 = 0, 1, 2
 KERNEL_RBF, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 1, 2, 3
+RK_MAX_STAGES = 16
 
 CALLBACK_T = C.CFUNCTYPE(
     C.c_int,  # return
@@ -145,9 +146,20 @@ class OpGrads(C.Structure):
     ]
 
 
+class RkTableau(C.Structure):
+    """mirror of ``struct mfx_rk_tableau``: an explicit Runge-Kutta method (a HOST struct; ``a`` strictly lower triangular)."""
+
+    _fields_ = [
+        ("stages", C.c_int32),
+        ("a", (C.c_double * RK_MAX_STAGES) * RK_MAX_STAGES),
+        ("b", C.c_double * RK_MAX_STAGES),
+    ]
+
+
 # every symbol include/mfx.h declares: (name, restype, argtypes)
 _P, _I64, _I = C.c_void_p, C.c_int64, C.c_int
 _OPP, _GRP, _CMP, _NETP = C.POINTER(Operator), C.POINTER(OpGrads), C.POINTER(Comm), C.POINTER(GgnNet)
+_RKP, _DP = C.POINTER(RkTableau), C.POINTER(C.c_double)
 SYMBOLS = {
     "mfx_last_error": (C.c_char_p, []),
     "mfx_version": (_I, []),
@@ -227,6 +239,10 @@ SYMBOLS = {
     "mfx_mlp_jac_t_apply": (_I, [_NETP, _I, _P, _I64, _P, _I64, _P, _I64, _P]),
     "mfx_ggn_diag_workspace_bytes": (_I64, [_NETP, _I]),
     "mfx_ggn_diag": (_I, [_NETP, _I, _P, _P, _I64, _P]),
+    "mfx_rk_workspace_bytes": (_I64, [_OPP, _RKP, _I64, _I64, _I]),
+    "mfx_rk_solve": (_I, [_OPP, _RKP, _DP, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _I, _P, _I64, _P]),
+    "mfx_rk_adjoint": (_I, [_OPP, _RKP, _DP, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _GRP, _I, _P, _I64, _P]),
+    "mfx_rk_backsolve": (_I, [_OPP, _RKP, _DP, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _GRP, _I, _P, _I64, _P]),
     "mfx_timing_enable": (_I, [_I]),
     "mfx_timing_reset": (_I, []),
     "mfx_timing_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

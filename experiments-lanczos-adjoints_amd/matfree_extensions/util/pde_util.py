@@ -9,6 +9,12 @@ end to end.  The dense k x k ``expm`` / ``eigh`` are torch calls (k <= ~100: plu
 The reference's stencil vector fields themselves -- ``pde_heat`` / ``pde_heat_affine`` / ``pde_heat_anisotropic`` /
 ``pde_wave_anisotropic`` with ``boundary_dirichlet`` / ``boundary_neumann`` and any 3x3 stencil (:18-157) -- run matrix-free on
 ``operators.StencilOp``; ``wave_operator`` (the assembled CSR form of one of them) stays.
+
+The fixed-step Runge-Kutta baselines of the work-precision study (``solver_euler`` / ``solver_diffrax``, :177-237) are ``solver_rk``:
+the whole solve, its discrete adjoint and the continuous ("backsolve") adjoint are single libmfx driver calls (``mfx_rk_solve`` /
+``mfx_rk_adjoint`` / ``mfx_rk_backsolve``, csrc/mfx_rk.hip) on LINEAR autonomous fields y' = A y, A a native, bound or callback
+operator.  Out of scope: adaptive step sizes, nonlinear or affine fields (``pde_heat_affine`` has no ``rhs.flat``), gradients with
+respect to the times, row-sharded operators.
 """
 
 from __future__ import annotations
@@ -16,8 +22,12 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import arnoldi, lanczos
-from ..operators import BoundOp, CsrOp, NativeOp, RowShardedOp, StencilOp, as_operator
+import ctypes as C
+
+from .. import _lib, arnoldi, lanczos
+from ..operators import (BoundOp, CallbackOp, CsrOp, DriverCall, NativeOp, RbfGramOp, RowShardedOp, StencilOp, as_operator, rebuild_params,
+                         stash_params)
+from . import rk_tableaux
 
 
 def expm_arnoldi(krylov_depth, *, max_squarings: int = 32, reortho="full", custom_vjp=True):
@@ -106,6 +116,147 @@ def solver_expm(t0, t1, vector_field, /, expm):
         return out.reshape(shape), info
 
     return solve
+
+
+_RK_ADJOINTS = {"discrete": "discrete", "recursive_checkpoint": "discrete", "direct": "discrete", "backsolve": "backsolve"}
+
+
+def _dts_array(dts):
+    return (C.c_double * len(dts))(*dts)
+
+
+def _rk_forward(op, cparams, tab, dts, Y0, keep_ys):
+    """One mfx_rk_solve call on detached tensors -> (y1 (p, n), ys (p, nsteps + 1, n) or None)."""
+    lib = _lib.get()
+    Y0 = Y0.contiguous()
+    p, n = Y0.shape
+    dt, dev = Y0.dtype, Y0.device
+    call = DriverCall(op, cparams, dt, n)
+    tstruct = rk_tableaux.struct(tab)
+    y1 = torch.empty_like(Y0)
+    ys = torch.empty((p, len(dts) + 1, n), dtype=dt, device=dev) if keep_ys else None
+    ws = call.take(lambda desc: lib.mfx_rk_workspace_bytes(desc, C.byref(tstruct), n, p, 0), device=dev, visible=(Y0, y1, ys))
+    call.run(lib.mfx_rk_solve, C.byref(tstruct), _dts_array(dts), len(dts), _lib.ptr(Y0), n, n, p, _lib.ptr(y1), n, _lib.ptr(ys),
+             0, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    return y1, ys
+
+
+class _RkFn(torch.autograd.Function):
+    """``mfx_rk_solve`` with the iterates kept; backward = ``mfx_rk_adjoint``, the exact gradient of the discrete scheme."""
+
+    @staticmethod
+    def forward(ctx, op, tab, dts, Y0, *cparams):
+        tensors = stash_params(ctx, cparams)
+        _lib.require_device(Y0, *tensors)
+        y1, ys = _rk_forward(op, cparams, tab, dts, Y0, True)
+        ctx.op, ctx.tab, ctx.dts = op, tab, dts
+        ctx.save_for_backward(ys, *tensors)
+        return y1
+
+    @staticmethod
+    def backward(ctx, dy1):
+        ys, *tensors = ctx.saved_tensors
+        cparams = rebuild_params(ctx, tensors)
+        lib, tab, dts = _lib.get(), ctx.tab, ctx.dts
+        p, _, n = ys.shape
+        dt, dev = ys.dtype, ys.device
+        dy1 = dy1.contiguous()
+        dy0 = torch.empty_like(dy1) if ctx.needs_input_grad[3] else None  # NULL: the last lambda store is skipped
+        call = DriverCall(ctx.op, cparams, dt, n, want_grads=True)
+        tstruct = rk_tableaux.struct(tab)
+        ws = call.take(lambda desc: lib.mfx_rk_workspace_bytes(desc, C.byref(tstruct), n, p, 1), device=dev, visible=(ys, dy1, dy0))
+        call.run(lib.mfx_rk_adjoint, C.byref(tstruct), _dts_array(dts), len(dts), _lib.ptr(ys), n, p, _lib.ptr(dy1), n, _lib.ptr(dy0), n,
+                 call.gptr, 0, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        return (None, None, None, dy0, *call.grads)
+
+
+class _RkBacksolveFn(torch.autograd.Function):
+    """``mfx_rk_solve`` keeping only y1; backward = ``mfx_rk_backsolve``, the continuous adjoint integrated backwards from y1."""
+
+    @staticmethod
+    def forward(ctx, op, tab, dts, Y0, *cparams):
+        tensors = stash_params(ctx, cparams)
+        _lib.require_device(Y0, *tensors)
+        y1, _ = _rk_forward(op, cparams, tab, dts, Y0, False)
+        ctx.op, ctx.tab, ctx.dts = op, tab, dts
+        ctx.save_for_backward(y1, *tensors)
+        return y1
+
+    @staticmethod
+    def backward(ctx, dy1):
+        y1, *tensors = ctx.saved_tensors
+        cparams = rebuild_params(ctx, tensors)
+        lib, tab, dts = _lib.get(), ctx.tab, ctx.dts
+        p, n = y1.shape
+        dt, dev = y1.dtype, y1.device
+        dy1 = dy1.contiguous()
+        dy0 = torch.empty_like(dy1) if ctx.needs_input_grad[3] else None
+        call = DriverCall(ctx.op, cparams, dt, n, want_grads=True)
+        tstruct = rk_tableaux.struct(tab)
+        ws = call.take(lambda desc: lib.mfx_rk_workspace_bytes(desc, C.byref(tstruct), n, p, 2), device=dev, visible=(y1, dy1, dy0))
+        call.run(lib.mfx_rk_backsolve, C.byref(tstruct), _dts_array(dts), len(dts), _lib.ptr(y1), n, n, p, _lib.ptr(dy1), n, _lib.ptr(dy0),
+                 n, call.gptr, 0, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        return (None, None, None, dy0, *call.grads)
+
+
+def _rk_solver(dts, vector_field, method, adjoint):
+    if adjoint not in _RK_ADJOINTS:
+        raise ValueError(f"adjoint must be one of {sorted(_RK_ADJOINTS)}, got {adjoint!r}")
+    tab = rk_tableaux.get(method)
+    dts = tuple(float(d) for d in dts)
+    if len(dts) < 1:
+        raise ValueError("a Runge-Kutta solve needs at least one step")
+    if not isinstance(vector_field, (NativeOp, BoundOp, CallbackOp, RowShardedOp)):
+        raise TypeError("solver_rk integrates LINEAR autonomous fields y' = A y: vector_field must be a linear operator -- a native "
+                        "operator, op.bind(*params) (rhs.flat of the stencil vector fields) or operators.CallbackOp(fn) -- not a "
+                        f"plain callable ({type(vector_field).__name__}); nonlinear and affine fields are out of scope")
+    op, bound = as_operator(vector_field)
+    if isinstance(op, RowShardedOp):
+        raise NotImplementedError("solver_rk does not take row-sharded operators (the stage kernels have no halo exchange or "
+                                  "all-gather); use the operator itself")
+    if isinstance(op, RbfGramOp) and op.X.requires_grad:
+        raise NotImplementedError("solver_rk does not return the gradient with respect to the kernel inputs X; pass X.detach()")
+    fn = _RkFn if _RK_ADJOINTS[adjoint] == "discrete" else _RkBacksolveFn
+
+    def solve(y0, *p):
+        params = (tuple(bound) if bound is not None else ()) + tuple(p)
+        cparams = op.constrain(*params)
+        n = op.size(*cparams) if isinstance(op, NativeOp) else y0.numel()  # a callback's state is whatever it is handed
+        if y0.numel() == n:
+            Y0 = y0.reshape(1, n)
+        elif y0.dim() >= 2 and y0.shape[0] * n == y0.numel():  # one more dimension than the operator's state: a batch
+            Y0 = y0.reshape(y0.shape[0], n)
+        else:
+            raise ValueError(f"a state of shape {tuple(y0.shape)} does not match the operator's {n} unknowns")
+        y1 = fn.apply(op, tab, dts, Y0, *cparams)
+        info = {"num_matvecs": len(dts) * tab.order, "num_applies": len(dts) * len(tab.b)}
+        return y1.reshape(y0.shape), info
+
+    return solve
+
+
+def solver_rk(t0, t1, vector_field, /, *, num_steps, method, adjoint="discrete"):
+    """Fixed-step explicit Runge-Kutta solve of y' = A y from t0 to t1 in ``num_steps`` equal steps (the reference's solver_diffrax,
+    util/pde_util.py:196-237, on linear fields).  ``method``: a name of ``rk_tableaux``; ``adjoint``: "discrete" (also
+    "recursive_checkpoint" / "direct": discretise-then-differentiate, the exact gradient of the scheme) or "backsolve" (the
+    continuous adjoint).  ``vector_field``: a native operator, a bound one (``rhs.flat``) or a ``CallbackOp``.  ``solve(y0, *p)`` ->
+    ``(y1, info)``; a state of any shape is flattened; a leading batch dimension is taken when y0 holds more than one state of the
+    operator's size.  info["num_matvecs"] = num_steps x order is the reference's proxy, info["num_applies"] = num_steps x stages the
+    true count.  t0, t1 are plain numbers (not differentiable)."""
+    num_steps = int(num_steps)
+    if num_steps < 1:
+        raise ValueError("num_steps must be at least 1")
+    dt = (float(t1) - float(t0)) / num_steps
+    return _rk_solver((dt,) * num_steps, vector_field, method, adjoint)
+
+
+solver_diffrax = solver_rk
+
+
+def solver_euler(ts, vector_field, /):
+    """util/pde_util.py:177-193: explicit Euler over the (possibly non-uniform) grid ``ts``, discrete adjoint."""
+    ts = [float(t) for t in (ts.tolist() if hasattr(ts, "tolist") else ts)]
+    return _rk_solver([b - a for a, b in zip(ts[:-1], ts[1:])], vector_field, "euler", "discrete")
 
 
 def sampler_lanczos(*, mean, cov_matvec, num, lanczos_rank):

@@ -709,6 +709,55 @@ int mfx_rff_grad_x(int dtype, const void* x, int64_t ldx, int64_t n, int64_t d, 
                    const void* lengthscale, int ard, const void* outputscale, const void* W, int64_t ldw, int64_t S, const void* g,
                    int64_t ldg, void* dx, int64_t lddx, void* stream);
 
+/* ---- fixed-step explicit Runge-Kutta solves of y' = A y with native adjoints: the baselines of the PDE work-precision study ------
+ * (util/pde_util.py:177-237 solver_euler / solver_diffrax; experiments/applications/partial_differential_equation/workprecision.py).
+ * A is any operator the drivers above take.  Additive: new symbols, no struct or existing signature changes, MFX_VERSION stays 201.
+ *
+ * Tableau (HOST struct): `stages` in 1..MFX_RK_MAX_STAGES, `a` strictly lower triangular, nothing else assumed.  Per step of size dt:
+ *   Y_i = y + dt sum_{j<i} a[i][j] K_j,   K_i = A Y_i,   y+ = y + dt sum_i b[i] K_i.
+ * dts: nsteps HOST values (they may differ: solver_euler takes diff(ts)).  Vectors are (p, n) batches with the leading dimensions
+ * given; ys, when not NULL, is (p, nsteps + 1, n) contiguous and receives every iterate: row 0 is y0, the last row is y1 bit for bit.
+ *
+ *   mfx_rk_solve      y1 = the nsteps-th iterate from y0.
+ *   mfx_rk_adjoint    the DISCRETE adjoint (the exact gradient of the scheme): from ys and the cotangent dy1, per step from the last
+ *                     to the first, the stages Y_i, K_i are recomputed from ys[step]; for i = s .. 1:
+ *                     Kbar_i = dt b[i] lam + dt sum_{j>i} a[j][i] Ybar_j,  Ybar_i = A^T Kbar_i;  then lam += sum_i Ybar_i.  dy0 = lam after
+ *                     the first step; dy0 == NULL skips that last store (grads are bit for bit those of the call that has it).
+ *                     Parameter gradient: ONE mfx_op_vjp_params sweep per step, L = the Kbar rows, R = the Y rows, batch p s,
+ *                     ACCUMULATED into `grads` (caller zero-fills) as in the Krylov adjoints; a CALLBACK operator accumulates inside
+ *                     its transposed application (mode 1, aux = Y_i).
+ *   mfx_rk_backsolve  the CONTINUOUS adjoint integrated backwards from y1 with the same tableau, no ys: steps h = -dt, dts reversed,
+ *                     on y' = A y, lam' = -A^T lam, thetabar' = -(dA/dtheta)^T [lam, y]; the quadrature of a step is one
+ *                     mfx_op_vjp_params sweep with L = the stage values of lam scaled by -h b[i], R = the stage values of y.
+ *                     It differs from the discrete gradient by the discretisation error of the backward solve.
+ *   mfx_rk_workspace_bytes   bytes for adjoint = 0 (solve), 1 (adjoint), 2 (backsolve); host arithmetic; -1 for arguments the
+ *                     call would refuse.
+ * flags: none is defined; pass 0.  (A stage kernel that fused the combination into the stencil apply was measured slower or within
+ * the noise and is not in the library: DESIGN.md section 3.4b.)
+ * Each driver is one fixed sequence of launches on `stream`, replayed from a hipGraph for a native operator; the graph's key
+ * covers the tableau, every dts value, nsteps, flags, all pointers and sizes and the operator's own key.  No atomics: bit-identical
+ * from run to run.
+ * Refused before the workspace is carved and before any launch.  What the operator's kind refuses, first.  MFX_ERR_INVALID: a NULL
+ * tableau, dts, or vector argument other than ys / dy0 / grads; stages outside 1..16; a non-zero entry of `a` on or above the
+ * diagonal; a non-finite entry of `a`, `b` or dts; nsteps < 1; p < 1; n != op->n; a leading dimension < n; flags != 0.
+ * MFX_ERR_UNSUPPORTED: a row block (nrows > 0; there is no row-sharded form), p > 65535, grads->x set (the input gradient of a
+ * kernel-Gram operator is not swept here).  MFX_ERR_WORKSPACE: ws NULL or ws_bytes below the query. */
+#define MFX_RK_MAX_STAGES 16
+typedef struct mfx_rk_tableau {
+  int32_t stages;
+  double a[MFX_RK_MAX_STAGES][MFX_RK_MAX_STAGES];
+  double b[MFX_RK_MAX_STAGES];
+} mfx_rk_tableau;
+int64_t mfx_rk_workspace_bytes(const mfx_operator* op, const mfx_rk_tableau* tab, int64_t n, int64_t p, int adjoint);
+int mfx_rk_solve(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* y0, int64_t ldy0,
+                 int64_t n, int64_t p, void* y1, int64_t ldy1, void* ys, int flags, void* ws, int64_t ws_bytes, void* stream);
+int mfx_rk_adjoint(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* ys, int64_t n,
+                   int64_t p, const void* dy1, int64_t lddy1, void* dy0, int64_t lddy0, const mfx_op_grads* grads, int flags, void* ws,
+                   int64_t ws_bytes, void* stream);
+int mfx_rk_backsolve(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* y1, int64_t ldy1,
+                     int64_t n, int64_t p, const void* dy1, int64_t lddy1, void* dy0, int64_t lddy0, const mfx_op_grads* grads,
+                     int flags, void* ws, int64_t ws_bytes, void* stream);
+
 /* Per-kernel-class device timing with hipEvents recorded on the caller's stream (no host syncs
  * while enabled; events are read back in mfx_timing_read, which synchronises the events).
  * classes: 0 = operator apply, 1 = operator parameter-gradient sweep, 2 = Krylov vector kernels. */
