@@ -750,6 +750,39 @@ static int check_precond(int64_t n, int64_t rank, const void* lt, const void* mi
   return MFX_OK;
 }
 
+// The operator with its preconditioner: what the four CG entries refuse alike after their own checks of pointers, sizes and counts
+// (those stay in each entry, in its own order: which of two faults is reported is part of the C-ABI).
+// whole_only: the name of an entry that has no row-sharded form, NULL otherwise.  lt == NULL: no preconditioner
+static int check_cg_op(const mfx_operator* op, const char* whole_only, int64_t n, const Precond& pc) {
+  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
+  MFX_REQUIRE(!whole_only || op->nrows == 0, MFX_ERR_UNSUPPORTED, "%s: no row block (nrows > 0): mBCG is not row-sharded", whole_only);
+  MFX_TRY(check_op(op));
+  if (pc.lt) MFX_TRY(check_precond(n, pc.rank, pc.lt, pc.minv, pc.shift));
+  return MFX_OK;
+}
+
+// what a CG entry point holds once nothing is left to refuse; rest: the rest_bytes the entry asked for behind the solver's own carve
+struct CgCall { CgWs ws; hipStream_t stream; void* rest; };
+static int cg_prologue(const char* fn, const mfx_operator* op, int64_t nrows, int64_t p, int64_t rank, int64_t rest_bytes,
+                       const char* hint, void* ws, int64_t ws_bytes, void* stream, const mfx_comm* comm, CgCall* call) {
+  const int64_t base = cg_carve(op, nrows, p, rank, ws, ws_bytes, &call->ws, comm);
+  MFX_REQUIRE(ws && base + rest_bytes <= ws_bytes, MFX_ERR_WORKSPACE, "%s: workspace too small: %lld bytes given, %lld needed%s", fn,
+              (long long)ws_bytes, (long long)(base + rest_bytes), hint);
+  call->rest = static_cast<char*>(ws) + base;
+  call->stream = static_cast<hipStream_t>(stream);
+  return MFX_OK;
+}
+// the PCG solve behind mfx_pcg_solve, mfx_pcg_solve_sharded (comm != NULL) and mfx_pcg_solve_reortho (q != NULL)
+static int pcg_typed(const mfx_operator* op, const void* b, int64_t ldb, int64_t nrows, int64_t p, const Precond& pc, int64_t maxiter,
+                     int64_t miniter, double atol, double rtol, int adaptive, void* x, void* r, void* num_steps, void* q,
+                     const CgCall& call, const mfx_comm* comm) {
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return pcg_t<T>(op, as<T>(b), ldb, nrows, p, pc.lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive, as<T>(x), as<T>(r),
+                    as<int64_t>(num_steps), as<T>(q), call.ws, call.stream, comm);
+  });
+}
+
 extern "C" {
 
 int64_t mfx_pcg_workspace_bytes(const mfx_operator* op, int64_t n, int64_t p, int64_t rank) {
@@ -768,20 +801,12 @@ int mfx_pcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n,
               (long long)n, (long long)p, (long long)ldb);
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
   MFX_REQUIRE(maxiter >= 0 && miniter >= 0, MFX_ERR_INVALID, "negative iteration count");
-  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
-  MFX_TRY(check_op(op));
-  Precond pc{precond_lt, precond_minv, precond_shift, rank};
-  if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
-  CgWs w;
-  MFX_REQUIRE(ws && cg_carve(op, n, p, precond_lt ? rank : 0, ws, ws_bytes, &w) <= ws_bytes, MFX_ERR_WORKSPACE,
-              "mfx_pcg_solve: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Precond pc{precond_lt, precond_minv, precond_shift, rank};
+  MFX_TRY(check_cg_op(op, nullptr, n, pc));
+  CgCall call;
+  MFX_TRY(cg_prologue("mfx_pcg_solve", op, n, p, precond_lt ? rank : 0, 0, "", ws, ws_bytes, stream, nullptr, &call));
   PrepScope prep_scope;
-  if (op->dtype == MFX_F32)
-    return pcg_t<float>(op, (const float*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
-                        (float*)x, (float*)r, (int64_t*)num_steps, nullptr, w, s);
-  return pcg_t<double>(op, (const double*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
-                       (double*)x, (double*)r, (int64_t*)num_steps, nullptr, w, s);
+  return pcg_typed(op, b, ldb, n, p, pc, maxiter, miniter, atol, rtol, adaptive, x, r, num_steps, nullptr, call, nullptr);
 }
 
 static int64_t mbcg_log_bytes(const mfx_operator* op, int64_t p, int64_t maxiter) {
@@ -797,33 +822,27 @@ int mfx_mbcg_solve(const mfx_operator* op, const void* b, int64_t ldb, int64_t n
                    int64_t rank, const void* precond_minv, const void* precond_shift, int64_t maxiter, int64_t miniter,
                    double atol, double rtol, int adaptive, void* x, void* r, void* num_steps, void* w0, void* tdiag,
                    void* toff, void* rz0, void* depth, void* ws, int64_t ws_bytes, void* stream) {
-  MFX_REQUIRE(op && b && x && r, MFX_ERR_INVALID, "mfx_mbcg_solve: null argument");
-  MFX_REQUIRE(tdiag && toff && rz0 && depth, MFX_ERR_INVALID, "mfx_mbcg_solve: tdiag, toff, rz0 and depth are required");
+  static const char* fn = "mfx_mbcg_solve";
+  MFX_REQUIRE(op && b && x && r, MFX_ERR_INVALID, "%s: null argument", fn);
+  MFX_REQUIRE(tdiag && toff && rz0 && depth, MFX_ERR_INVALID, "%s: tdiag, toff, rz0 and depth are required", fn);
   MFX_REQUIRE(op->n == n && n >= 1 && p >= 1 && ldb >= n, MFX_ERR_INVALID, "mfx_mbcg_solve: bad sizes n=%lld p=%lld ldb=%lld",
               (long long)n, (long long)p, (long long)ldb);
   MFX_REQUIRE(maxiter >= 1 && miniter >= 0, MFX_ERR_INVALID, "mfx_mbcg_solve: maxiter %lld < 1 or negative miniter",
               (long long)maxiter);
   MFX_REQUIRE(maxiter < ((int64_t)1 << 30), MFX_ERR_UNSUPPORTED, "mfx_mbcg_solve: maxiter %lld too large", (long long)maxiter);
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
-  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
-  MFX_REQUIRE(op->nrows == 0, MFX_ERR_UNSUPPORTED, "mfx_mbcg_solve: no row block (nrows > 0): mBCG is not row-sharded");
-  MFX_TRY(check_op(op));
-  Precond pc{precond_lt, precond_minv, precond_shift, rank};
-  if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
-  CgWs w;
-  const int64_t base = ws ? cg_carve(op, n, p, precond_lt ? rank : 0, ws, ws_bytes, &w) : 0;
-  MFX_REQUIRE(ws && base + mbcg_log_bytes(op, p, maxiter) <= ws_bytes, MFX_ERR_WORKSPACE,
-              "mfx_mbcg_solve: workspace too small (mfx_mbcg_workspace_bytes)");
-  void* logs = static_cast<char*>(ws) + base;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Precond pc{precond_lt, precond_minv, precond_shift, rank};
+  MFX_TRY(check_cg_op(op, fn, n, pc));
+  CgCall call;
+  MFX_TRY(cg_prologue(fn, op, n, p, precond_lt ? rank : 0, mbcg_log_bytes(op, p, maxiter), " (mfx_mbcg_workspace_bytes)", ws, ws_bytes,
+                      stream, nullptr, &call));
   PrepScope prep_scope;
-  if (op->dtype == MFX_F32)
-    return mbcg_t<float>(op, (const float*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
-                         (float*)x, (float*)r, (int64_t*)num_steps, (float*)w0, (float*)tdiag, (float*)toff, (float*)rz0,
-                         (int64_t*)depth, w, logs, s);
-  return mbcg_t<double>(op, (const double*)b, ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
-                        (double*)x, (double*)r, (int64_t*)num_steps, (double*)w0, (double*)tdiag, (double*)toff, (double*)rz0,
-                        (int64_t*)depth, w, logs, s);
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return mbcg_t<T>(op, as<T>(b), ldb, n, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive, as<T>(x), as<T>(r),
+                     as<int64_t>(num_steps), as<T>(w0), as<T>(tdiag), as<T>(toff), as<T>(rz0), as<int64_t>(depth), call.ws, call.rest,
+                     call.stream);
+  });
 }
 
 int mfx_precond_sample(int dtype, int64_t n, int64_t rank, const void* lt, const void* shift, uint64_t seed,
@@ -838,14 +857,12 @@ int mfx_precond_sample(int dtype, int64_t n, int64_t rank, const void* lt, const
   if (gx > 2048) gx = 2048;
   const dim3 grid((unsigned)gx, (unsigned)((p + kSampleProbes - 1) / kSampleProbes));
   const size_t sh = (size_t)kSampleProbes * rank * dtype_size(dtype);
-  if (dtype == MFX_F32)
-    k_precond_sample<float><<<grid, 256, sh, s>>>(seed, first_probe, p, n, (int)rank, (const float*)lt, (const float*)shift,
-                                                  (float*)out);
-  else
-    k_precond_sample<double><<<grid, 256, sh, s>>>(seed, first_probe, p, n, (int)rank, (const double*)lt,
-                                                   (const double*)shift, (double*)out);
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    k_precond_sample<T><<<grid, 256, sh, s>>>(seed, first_probe, p, n, (int)rank, as<T>(lt), as<T>(shift), as<T>(out));
+    MFX_CHECK_LAUNCH();
+    return MFX_OK;
+  });
 }
 
 int64_t mfx_pcg_sharded_workspace_bytes(const mfx_operator* op, const mfx_comm* comm, int64_t n, int64_t p, int64_t rank) {
@@ -864,20 +881,12 @@ int mfx_pcg_solve_sharded(const mfx_operator* op, const mfx_comm* comm, const vo
   MFX_REQUIRE(ldb >= nrows, MFX_ERR_INVALID, "ldb = %lld < this rank's %lld rows", (long long)ldb, (long long)nrows);
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
   MFX_REQUIRE(maxiter >= 0 && miniter >= 0, MFX_ERR_INVALID, "negative iteration count");
-  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
-  MFX_TRY(check_op(op));
-  Precond pc{precond_lt, precond_minv, precond_shift, rank};
-  if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
-  CgWs w;
-  MFX_REQUIRE(ws && cg_carve(op, nrows, p, precond_lt ? rank : 0, ws, ws_bytes, &w, comm) <= ws_bytes, MFX_ERR_WORKSPACE,
-              "mfx_pcg_solve_sharded: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Precond pc{precond_lt, precond_minv, precond_shift, rank};
+  MFX_TRY(check_cg_op(op, nullptr, n, pc));
+  CgCall call;
+  MFX_TRY(cg_prologue("mfx_pcg_solve_sharded", op, nrows, p, precond_lt ? rank : 0, 0, "", ws, ws_bytes, stream, comm, &call));
   PrepScope prep_scope;
-  if (op->dtype == MFX_F32)
-    return pcg_t<float>(op, (const float*)b, ldb, nrows, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
-                        (float*)x, (float*)r, (int64_t*)num_steps, nullptr, w, s, comm);
-  return pcg_t<double>(op, (const double*)b, ldb, nrows, p, precond_lt ? &pc : nullptr, maxiter, miniter, atol, rtol, adaptive,
-                       (double*)x, (double*)r, (int64_t*)num_steps, nullptr, w, s, comm);
+  return pcg_typed(op, b, ldb, nrows, p, pc, maxiter, miniter, atol, rtol, adaptive, x, r, num_steps, nullptr, call, comm);
 }
 
 int mfx_pcg_solve_reortho(const mfx_operator* op, const void* b, int64_t ldb, int64_t n, int64_t p,
@@ -888,21 +897,13 @@ int mfx_pcg_solve_reortho(const mfx_operator* op, const void* b, int64_t ldb, in
   MFX_REQUIRE(p <= 65535, MFX_ERR_UNSUPPORTED, "at most 65535 right-hand sides per call");
   MFX_REQUIRE(num_matvecs >= 1 && num_matvecs <= 1024, MFX_ERR_INVALID, "num_matvecs %lld outside [1, 1024]",
               (long long)num_matvecs);
-  MFX_REQUIRE(op->dtype == MFX_F32 || op->dtype == MFX_F64, MFX_ERR_INVALID, "bad dtype");
-  MFX_TRY(check_op(op));
-  Precond pc{precond_lt, precond_minv, precond_shift, rank};
-  if (precond_lt) MFX_TRY(check_precond(n, rank, precond_lt, precond_minv, precond_shift));
+  const Precond pc{precond_lt, precond_minv, precond_shift, rank};
+  MFX_TRY(check_cg_op(op, nullptr, n, pc));
   const int64_t kdim = (precond_lt && rank > num_matvecs) ? rank : num_matvecs;
-  CgWs w;
-  MFX_REQUIRE(ws && cg_carve(op, n, p, kdim, ws, ws_bytes, &w) <= ws_bytes, MFX_ERR_WORKSPACE,
-              "mfx_pcg_solve_reortho: workspace too small (size it with rank = max(rank, num_matvecs))");
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  CgCall call;
+  MFX_TRY(cg_prologue("mfx_pcg_solve_reortho", op, n, p, kdim, 0, " (size it with rank = max(rank, num_matvecs))", ws, ws_bytes, stream, nullptr, &call));
   PrepScope prep_scope;
-  if (op->dtype == MFX_F32)
-    return pcg_t<float>(op, (const float*)b, ldb, n, p, precond_lt ? &pc : nullptr, num_matvecs, 0, 1.0, 0.0, 0, (float*)x,
-                        (float*)r, nullptr, (float*)q, w, s);
-  return pcg_t<double>(op, (const double*)b, ldb, n, p, precond_lt ? &pc : nullptr, num_matvecs, 0, 1.0, 0.0, 0, (double*)x,
-                       (double*)r, nullptr, (double*)q, w, s);
+  return pcg_typed(op, b, ldb, n, p, pc, num_matvecs, 0, 1.0, 0.0, 0, x, r, nullptr, q, call, nullptr);
 }
 
 int mfx_precond_apply(int dtype, int64_t n, int64_t rank, const void* lt, const void* minv, const void* shift,
@@ -916,22 +917,16 @@ int mfx_precond_apply(int dtype, int64_t n, int64_t rank, const void* lt, const 
   fake.dtype = dtype;
   fake.kind = MFX_OP_DENSE;
   fake.n = n;
-  CgWs w;
-  MFX_REQUIRE(ws && cg_carve(&fake, n, p, rank, ws, ws_bytes, &w) <= ws_bytes, MFX_ERR_WORKSPACE,
-              "mfx_precond_apply: workspace too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Precond pc{lt, minv, shift, rank};
-  // vector b of v and z starts at b * ldv and b * ldz: 16-byte accesses need strides that keep the alignment of vector 0
-  if (dtype == MFX_F32) {
-    const bool strides_ok = ldv % VecWidth<float>::value == 0 && ldz % VecWidth<float>::value == 0;
-    Ctx<float> c(n, rank, p, strides_ok ? pick_vec<float>(n, {v, z, lt}) : 1, s);
-    return precond_apply_t<float>(c, pc, (const float*)v, ldv, (float*)z, ldz, (float*)w.part_a, (float*)w.u, nullptr,
-                                  nullptr);
-  }
-  const bool strides_ok = ldv % VecWidth<double>::value == 0 && ldz % VecWidth<double>::value == 0;
-  Ctx<double> c(n, rank, p, strides_ok ? pick_vec<double>(n, {v, z, lt}) : 1, s);
-  return precond_apply_t<double>(c, pc, (const double*)v, ldv, (double*)z, ldz, (double*)w.part_a, (double*)w.u, nullptr,
-                                 nullptr);
+  CgCall call;
+  MFX_TRY(cg_prologue("mfx_precond_apply", &fake, n, p, rank, 0, "", ws, ws_bytes, stream, nullptr, &call));
+  const Precond pc{lt, minv, shift, rank};
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    // vector b of v and z starts at b * ldv and b * ldz: 16-byte accesses need strides that keep the alignment of vector 0
+    const bool strides_ok = ldv % VecWidth<T>::value == 0 && ldz % VecWidth<T>::value == 0;
+    Ctx<T> c(n, rank, p, strides_ok ? pick_vec<T>(n, {v, z, lt}) : 1, call.stream);
+    return precond_apply_t<T>(c, pc, as<T>(v), ldv, as<T>(z), ldz, as<T>(call.ws.part_a), as<T>(call.ws.u), nullptr, nullptr);
+  });
 }
 
 int64_t mfx_gram_cross_workspace_bytes(const mfx_operator* op, int64_t m) {
@@ -990,9 +985,10 @@ int mfx_partial_cholesky(const mfx_operator* op, int64_t rank, int pivot, int wi
   MFX_REQUIRE(rank >= 1, MFX_ERR_INVALID, "Rank must be positive, but %lld < 1.", (long long)rank);
   MFX_REQUIRE(rank <= 1024, MFX_ERR_UNSUPPORTED, "rank %lld > 1024 (the preconditioner applies at most 1024 columns)", (long long)rank);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (op->dtype == MFX_F32)
-    return pchol_t<float>(op, rank, pivot, with_noise, (float*)lt, (int64_t*)pivots, (int*)success, ws, ws_bytes, s);
-  return pchol_t<double>(op, rank, pivot, with_noise, (double*)lt, (int64_t*)pivots, (int*)success, ws, ws_bytes, s);
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return pchol_t<T>(op, rank, pivot, with_noise, as<T>(lt), as<int64_t>(pivots), as<int>(success), ws, ws_bytes, s);
+  });
 }
 
 }  // extern "C"

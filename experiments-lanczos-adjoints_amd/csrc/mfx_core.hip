@@ -112,6 +112,14 @@ static bool graphs_enabled() {
   return on;
 }
 
+GraphKey driver_key(DriverId id, const mfx_operator* op, int64_t n, int64_t depth, int64_t p, const mfx_op_grads* grads,
+                    const void* ws, int64_t ws_bytes, const void* stream) {
+  GraphKey key;
+  key.add(id).add(*op).add(n).add(depth).add(p).add(ws).add(ws_bytes).add(stream);
+  if (op_kind(op)->graph_key) op_kind(op)->graph_key(op, key);
+  return key.add(grads ? *grads : mfx_op_grads{}).add(grads != nullptr);
+}
+
 int run_graphed(bool eligible, const GraphKey& key, hipStream_t stream, const std::function<int(hipStream_t)>& fn) {
   if (!eligible || g_timing || !graphs_enabled()) return fn(stream);
   // A graph belongs to the device its kernels were captured for, and the capture stream is created on the CURRENT device: replay only

@@ -195,15 +195,12 @@ int mfx_funm_coeffs(const void* evals, const void* evecs, const void* fvals, con
   MFX_REQUIRE(k <= kSmallMaxDepth, MFX_ERR_UNSUPPORTED, "funm coefficients support k <= %d (got %lld)", kSmallMaxDepth, (long long)k);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t sh = (size_t)k * sizeof(double);
-  if (dtype == MFX_F32) {
-    k_funm_coeffs<float><<<(unsigned)p, kFunmBlock, sh, s>>>((const float*)evecs, (const float*)fvals, (const float*)scale, (int)k,
-                                                             (float*)coeffs);
-  } else {
-    k_funm_coeffs<double><<<(unsigned)p, kFunmBlock, sh, s>>>((const double*)evecs, (const double*)fvals, (const double*)scale, (int)k,
-                                                              (double*)coeffs);
-  }
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    k_funm_coeffs<T><<<(unsigned)p, kFunmBlock, sh, s>>>(as<T>(evecs), as<T>(fvals), as<T>(scale), (int)k, as<T>(coeffs));
+    MFX_CHECK_LAUNCH();
+    return MFX_OK;
+  });
 }
 
 int mfx_funm_coeffs_bwd(const void* evals, const void* evecs, const void* fvals, const void* dfvals, const void* dcoeffs,
@@ -219,31 +216,27 @@ int mfx_funm_coeffs_bwd(const void* evals, const void* evecs, const void* fvals,
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool deep = k > kSmallLdsDepth;
   const size_t sh = (size_t)(k + (deep ? 4 * k : k * k)) * sizeof(double);
-#define MFX_FUNM_LAUNCH(T, DEEP)                                                                                                \
-  do {                                                                                                                          \
-    MFX_TRY(allow_big_lds(k_funm_coeffs_bwd<T, DEEP>, sh));                                                                      \
-    k_funm_coeffs_bwd<T, DEEP><<<(unsigned)p, 64, sh, s>>>((const T*)evals, (const T*)evecs, (const T*)fvals, (const T*)dfvals, \
-                                                           (const T*)dcoeffs, (const T*)scale, (int)k, (T*)dalpha, (T*)dbeta,   \
-                                                           lddbeta, (T*)dscale);                                                \
-  } while (0)
-  if (dtype == MFX_F32) {
-    if (deep) MFX_FUNM_LAUNCH(float, true);
-    else MFX_FUNM_LAUNCH(float, false);
-  } else {
-    if (deep) MFX_FUNM_LAUNCH(double, true);
-    else MFX_FUNM_LAUNCH(double, false);
-  }
-#undef MFX_FUNM_LAUNCH
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return with_flag(deep, [&](auto deep_tag) -> int {
+      constexpr bool DEEP = decltype(deep_tag)::value;
+      MFX_TRY(allow_big_lds(k_funm_coeffs_bwd<T, DEEP>, sh));
+      k_funm_coeffs_bwd<T, DEEP><<<(unsigned)p, 64, sh, s>>>(as<T>(evals), as<T>(evecs), as<T>(fvals), as<T>(dfvals), as<T>(dcoeffs),
+                                                             as<T>(scale), (int)k, as<T>(dalpha), as<T>(dbeta), lddbeta, as<T>(dscale));
+      MFX_CHECK_LAUNCH();
+      return MFX_OK;
+    });
+  });
 }
 
 int mfx_basis_combine(const void* Q, const void* coeffs, int64_t n, int64_t k, int64_t p, int dtype, void* y, void* stream) {
   MFX_REQUIRE(Q && coeffs && y, MFX_ERR_INVALID, "null argument");
   MFX_TRY(check_combine_shape(n, k, p, dtype));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == MFX_F32) return basis_combine_t<float>((const float*)Q, (const float*)coeffs, n, k, p, (float*)y, s);
-  return basis_combine_t<double>((const double*)Q, (const double*)coeffs, n, k, p, (double*)y, s);
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return basis_combine_t<T>(as<T>(Q), as<T>(coeffs), n, k, p, as<T>(y), s);
+  });
 }
 
 int64_t mfx_basis_combine_workspace_bytes(int64_t n, int64_t k, int64_t p, int dtype) {
@@ -267,11 +260,10 @@ int mfx_basis_combine_bwd(const void* Q, const void* coeffs, const void* dy, int
     partial = ws;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == MFX_F32)
-    return basis_combine_bwd_t<float>((const float*)Q, (const float*)coeffs, (const float*)dy, n, k, p, (float*)dQ, (float*)dcoeffs,
-                                      (float*)partial, s);
-  return basis_combine_bwd_t<double>((const double*)Q, (const double*)coeffs, (const double*)dy, n, k, p, (double*)dQ,
-                                     (double*)dcoeffs, (double*)partial, s);
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return basis_combine_bwd_t<T>(as<T>(Q), as<T>(coeffs), as<T>(dy), n, k, p, as<T>(dQ), as<T>(dcoeffs), as<T>(partial), s);
+  });
 }
 
 }  // extern "C"

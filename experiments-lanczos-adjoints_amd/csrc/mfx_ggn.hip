@@ -772,9 +772,6 @@ static int diag_t(const mfx_ggn_net* net, T* diag, T* ws, hipStream_t stream) { 
   return ggn_pass<T>(a, 1, [&](dim3 grid, int block) { k_ggn_diag_tiles<T><<<grid, block, 0, stream>>>(a, ws); }, ws, diag, a.P, stream);
 }
 
-template <typename F>  // the typed tail of an entry point: f(T()) with T = float or double for a checked dtype
-static int ggn_by_dtype(int dtype, F f) { return dtype == MFX_F32 ? f(float()) : f(double()); }
-
 }  // namespace mfx
 
 using namespace mfx;
@@ -792,7 +789,7 @@ int mfx_ggn_diag(const mfx_ggn_net* net, int dtype, void* diag, void* ws, int64_
   const int64_t need = ggn_part_bytes(net, dtype, 1);
   MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "GGN diagonal: workspace too small: need %lld bytes", (long long)need);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return ggn_by_dtype(dtype, [&](auto t) { return diag_t(net, (decltype(t)*)diag, (decltype(t)*)ws, s); });
+  return with_dtype(dtype, [&](auto t) { return diag_t(net, (decltype(t)*)diag, (decltype(t)*)ws, s); });
 }
 
 int64_t mfx_mlp_jac_workspace_bytes(const mfx_ggn_net* net, int dtype, int64_t p) {
@@ -806,7 +803,7 @@ int mfx_mlp_jac_apply(const mfx_ggn_net* net, int dtype, const void* V, int64_t 
   MFX_REQUIRE(ldv >= ggn_params(net), MFX_ERR_INVALID, "MLP Jacobian: ldv = %lld is less than the P = %lld parameters", (long long)ldv,
               (long long)ggn_params(net));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return ggn_by_dtype(dtype, [&](auto t) { return jac_apply_t(net, (const decltype(t)*)V, ldv, p, (decltype(t)*)out, s); });
+  return with_dtype(dtype, [&](auto t) { return jac_apply_t(net, (const decltype(t)*)V, ldv, p, (decltype(t)*)out, s); });
 }
 
 int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_t p, void* Y, int64_t ldy, void* ws, int64_t ws_bytes,
@@ -817,7 +814,7 @@ int mfx_mlp_jac_t_apply(const mfx_ggn_net* net, int dtype, const void* U, int64_
               (long long)ggn_params(net));
   const int64_t need = ggn_part_bytes(net, dtype, p);
   MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "MLP Jacobian: workspace too small: need %lld bytes", (long long)need);
-  return ggn_by_dtype(dtype, [&](auto t) {
+  return with_dtype(dtype, [&](auto t) {
     return jac_t_apply_t(net, (const decltype(t)*)U, p, (decltype(t)*)Y, ldy, (decltype(t)*)ws, static_cast<hipStream_t>(stream));
   });
 }

@@ -6,6 +6,7 @@
 
 #include <functional>
 #include <string>
+#include <type_traits>
 
 #include "mfx.h"
 
@@ -63,6 +64,25 @@ struct GraphKey {
 // eligible = false (or graphs disabled, or kernel timing on): plain fn(stream).  fn must enqueue everything on the stream
 // it is given and nothing else (no synchronisation, no allocation).
 int run_graphed(bool eligible, const GraphKey& key, hipStream_t stream, const std::function<int(hipStream_t)>& fn);
+// One id per driver that replays from a graph, across all files: a key starts with it, so no two drivers can share a graph.
+enum DriverId : int { kIdArnoldiForward = 1, kIdArnoldiAdjoint, kIdLanczosForward, kIdLanczosAdjoint, kIdRkSolve, kIdRkAdjoint, kIdRkBacksolve };
+// What every driver's key starts with: the id, *op and what its kind adds (OpKind::graph_key), the sizes (depth: Krylov depth or
+// number of steps), the workspace, the stream and the gradient request (NULL: none).  The driver appends its own pointers and flags.
+GraphKey driver_key(DriverId id, const mfx_operator* op, int64_t n, int64_t depth, int64_t p, const mfx_op_grads* grads,
+                    const void* ws, int64_t ws_bytes, const void* stream);
+// ---- typed dispatch of the C entry points ---------------------------------------------------------
+// f, a generic lambda (`[&](auto t) -> int { using T = decltype(t); ... }`), gets a float or a double tag; any other dtype is refused
+template <typename F>
+static int with_dtype(int dtype, F&& f) {
+  if (dtype == MFX_F32) return f(float());
+  if (dtype == MFX_F64) return f(double());
+  set_error("unsupported dtype %d", dtype);
+  return MFX_ERR_UNSUPPORTED;
+}
+// the same for a template flag: f(std::true_type) or f(std::false_type)
+template <typename F> static int with_flag(bool flag, F&& f) { return flag ? f(std::true_type()) : f(std::false_type()); }
+template <typename T> inline T* as(void* p) { return static_cast<T*>(p); }
+template <typename T> inline const T* as(const void* p) { return static_cast<const T*>(p); }
 
 // ---- device fills / copies as KERNELS -------------------------------------------------------------
 // hipMemsetAsync / hipMemcpy2DAsync become memset / memcpy NODES when a driver call is captured into a hipGraph, and the memset

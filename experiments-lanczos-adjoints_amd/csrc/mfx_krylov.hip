@@ -1017,36 +1017,36 @@ int64_t mfx_workspace_bytes(const mfx_operator* op, int64_t n, int64_t k, int64_
 static bool graph_eligible(const mfx_operator* op, int64_t n, int64_t p) {
   return op_kind(op)->native && num_slices(n) * p < 256;
 }
-static GraphKey driver_key(int fn_id, const mfx_operator* op, int64_t n, int64_t k, int64_t p, const mfx_op_grads* grads,
-                           const void* ws, int64_t ws_bytes, const void* stream) {
-  GraphKey key;
-  key.add(fn_id).add(*op).add(n).add(k).add(p).add(ws).add(ws_bytes).add(stream);
-  if (op_kind(op)->graph_key) op_kind(op)->graph_key(op, key);
-  const mfx_op_grads none{};
-  key.add(grads ? *grads : none).add(grads != nullptr);
-  return key;
+// what a Krylov entry point holds once nothing is left to refuse: the carved workspace, the stream, the rows this process holds
+struct KrylovCall { KrylovWs ws; hipStream_t stream; int64_t nrows; };
+// comm: NULL for the unsharded entries, as for carve_ws.  `sharded` says which kind of entry calls, and exists only so that a
+// row-sharded entry handed a NULL comm is refused by check_op_sharded and does not fall through to the unsharded path.
+static int krylov_prologue(const char* fn, const mfx_operator* op, bool sharded, const mfx_comm* comm, int64_t n, int64_t k, int64_t p,
+                           void* ws, int64_t ws_bytes, void* stream, KrylovCall* call) {
+  MFX_TRY(check_common(op, n, k, p));
+  if (sharded) MFX_TRY(check_op_sharded(op, comm, n));
+  call->nrows = sharded ? shard_nrows(comm, n) : n;
+  const int64_t need = carve_ws(op, call->nrows, k, p, ws, ws_bytes, &call->ws, comm);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "%s: workspace too small: %lld bytes given, %lld needed", fn,
+              (long long)ws_bytes, (long long)need);
+  call->stream = static_cast<hipStream_t>(stream);
+  return MFX_OK;
 }
-
-#define MFX_DRIVER_PROLOGUE()                                                                   \
-  MFX_TRY(check_common(op, n, k, p));                                                           \
-  KrylovWs kws;                                                                                 \
-  const int64_t need = carve_ws(op, n, k, p, ws, ws_bytes, &kws);                                \
-  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "workspace too small: need %lld bytes", \
-              (long long)need);                                                                 \
-  hipStream_t s = static_cast<hipStream_t>(stream);                                               \
-  PrepScope prep_scope
 
 int mfx_arnoldi_forward(const mfx_operator* op, const void* v0, int64_t n, int64_t k, int64_t p,
                         int second_pass, void* Q, void* H, void* r, void* c, void* ws, int64_t ws_bytes,
                         void* stream) {
   MFX_REQUIRE(v0 && Q && H && r && c, MFX_ERR_INVALID, "null argument");
-  MFX_DRIVER_PROLOGUE();
-  GraphKey key = driver_key(1, op, n, k, p, nullptr, ws, ws_bytes, stream);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_arnoldi_forward", op, false, nullptr, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = driver_key(kIdArnoldiForward, op, n, k, p, nullptr, ws, ws_bytes, stream);
   key.add(v0).add(second_pass).add(Q).add(H).add(r).add(c);
-  return run_graphed(graph_eligible(op, n, p), key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return arnoldi_forward_t<float>(op, (const float*)v0, n, k, p, second_pass, (float*)Q, (float*)H, (float*)r, (float*)c, kws, st);
-    return arnoldi_forward_t<double>(op, (const double*)v0, n, k, p, second_pass, (double*)Q, (double*)H, (double*)r, (double*)c, kws, st);
+  return run_graphed(graph_eligible(op, n, p), key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return arnoldi_forward_t<T>(op, as<T>(v0), n, k, p, second_pass, as<T>(Q), as<T>(H), as<T>(r), as<T>(c), call.ws, st);
+    });
   });
 }
 
@@ -1063,12 +1063,13 @@ int mfx_arnoldi_forward_complex(const mfx_operator* op, const void* v0, int64_t 
   MFX_REQUIRE(k <= 65535, MFX_ERR_UNSUPPORTED, "k=%lld exceeds the grid limit 65535", (long long)k);
   ComplexWs cw;
   const int64_t need = carve_complex_ws(op, n, k, p, ws, ws_bytes, &cw);
-  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "mfx_arnoldi_forward_complex: workspace too small: need %lld bytes", (long long)need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   PrepScope prep_scope;
-  if (op->dtype == MFX_F32)
-    return arnoldi_forward_complex_t<float>(op, (const float*)v0, n, k, p, second_pass, (float*)Q, (float*)H, (float*)r, (float*)c, cw, s);
-  return arnoldi_forward_complex_t<double>(op, (const double*)v0, n, k, p, second_pass, (double*)Q, (double*)H, (double*)r, (double*)c, cw, s);
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return arnoldi_forward_complex_t<T>(op, as<T>(v0), n, k, p, second_pass, as<T>(Q), as<T>(H), as<T>(r), as<T>(c), cw, s);
+  });
 }
 
 int mfx_arnoldi_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p, const void* Q, const void* H,
@@ -1078,46 +1079,38 @@ int mfx_arnoldi_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p,
   MFX_REQUIRE(Q && H && r && c && dH && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(reortho == MFX_REORTHO_NONE || reortho == MFX_REORTHO_FULL, MFX_ERR_INVALID, "bad reortho flag %d", reortho);
   MFX_TRY(check_op_grads(op, grads, false));
-  MFX_DRIVER_PROLOGUE();
-  GraphKey key = driver_key(2, op, n, k, p, grads, ws, ws_bytes, stream);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_arnoldi_adjoint", op, false, nullptr, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = driver_key(kIdArnoldiAdjoint, op, n, k, p, grads, ws, ws_bytes, stream);
   key.add(Q).add(H).add(r).add(c).add(dQ).add(dH).add(dr).add(dc).add(reortho).add(dv).add(Lambda);
-  return run_graphed(graph_eligible(op, n, p), key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return arnoldi_adjoint_t<float>(op, n, k, p, (const float*)Q, (const float*)H, (const float*)r, (const float*)c,
-                                      (const float*)dQ, (const float*)dH, (const float*)dr, (const float*)dc, reortho,
-                                      (float*)dv, (float*)Lambda, grads, kws, st);
-    return arnoldi_adjoint_t<double>(op, n, k, p, (const double*)Q, (const double*)H, (const double*)r, (const double*)c,
-                                     (const double*)dQ, (const double*)dH, (const double*)dr, (const double*)dc, reortho,
-                                     (double*)dv, (double*)Lambda, grads, kws, st);
+  return run_graphed(graph_eligible(op, n, p), key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return arnoldi_adjoint_t<T>(op, n, k, p, as<T>(Q), as<T>(H), as<T>(r), as<T>(c), as<T>(dQ), as<T>(dH), as<T>(dr), as<T>(dc),
+                                  reortho, as<T>(dv), as<T>(Lambda), grads, call.ws, st);
+    });
   });
 }
-
-#define MFX_SHARDED_PROLOGUE()                                                                  \
-  MFX_TRY(check_common(op, n, k, p));                                                           \
-  MFX_TRY(check_op_sharded(op, comm, n));                                                       \
-  const int64_t nrows = shard_nrows(comm, n);                                                   \
-  KrylovWs kws;                                                                                 \
-  const int64_t need = carve_ws(op, nrows, k, p, ws, ws_bytes, &kws, comm);                      \
-  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "workspace too small: need %lld bytes", \
-              (long long)need);                                                                 \
-  hipStream_t s = static_cast<hipStream_t>(stream);                                               \
-  PrepScope prep_scope
 
 int64_t mfx_sharded_workspace_bytes(const mfx_operator* op, const mfx_comm* comm, int64_t n, int64_t k, int64_t p) {
   if (!op || !comm || comm->nloc < 1) return -1;
   return carve_ws(op, comm->nloc, k, p, nullptr, 0, nullptr, comm);
 }
 
+// The row-sharded entries never replay from a graph (an all-reduce through the communicator's callbacks follows every pass).
 int mfx_arnoldi_forward_sharded(const mfx_operator* op, const mfx_comm* comm, const void* v0, int64_t n, int64_t k,
                                 int64_t p, int second_pass, void* Q, void* Qfull, void* H, void* r, void* c, void* ws,
                                 int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(v0 && Q && Qfull && H && r && c, MFX_ERR_INVALID, "null argument");
-  MFX_SHARDED_PROLOGUE();
-  if (op->dtype == MFX_F32)
-    return arnoldi_forward_t<float>(op, (const float*)v0, nrows, k, p, second_pass, (float*)Q, (float*)H, (float*)r, (float*)c,
-                                    kws, s, comm, (float*)Qfull);
-  return arnoldi_forward_t<double>(op, (const double*)v0, nrows, k, p, second_pass, (double*)Q, (double*)H, (double*)r,
-                                   (double*)c, kws, s, comm, (double*)Qfull);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_arnoldi_forward_sharded", op, true, comm, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return arnoldi_forward_t<T>(op, as<T>(v0), call.nrows, k, p, second_pass, as<T>(Q), as<T>(H), as<T>(r), as<T>(c), call.ws,
+                                call.stream, comm, as<T>(Qfull));
+  });
 }
 
 int mfx_arnoldi_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, int64_t n, int64_t k, int64_t p,
@@ -1127,23 +1120,27 @@ int mfx_arnoldi_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
   MFX_REQUIRE(Q && Qfull && H && r && c && dH && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(reortho == MFX_REORTHO_NONE || reortho == MFX_REORTHO_FULL, MFX_ERR_INVALID, "bad reortho flag %d", reortho);
   MFX_TRY(check_op_grads(op, grads, true));
-  MFX_SHARDED_PROLOGUE();
-  if (op->dtype == MFX_F32)
-    return arnoldi_adjoint_t<float>(op, nrows, k, p, (const float*)Q, (const float*)H, (const float*)r, (const float*)c,
-                                    (const float*)dQ, (const float*)dH, (const float*)dr, (const float*)dc, reortho,
-                                    (float*)dv, (float*)Lambda, grads, kws, s, comm, (const float*)Qfull);
-  return arnoldi_adjoint_t<double>(op, nrows, k, p, (const double*)Q, (const double*)H, (const double*)r, (const double*)c,
-                                   (const double*)dQ, (const double*)dH, (const double*)dr, (const double*)dc, reortho,
-                                   (double*)dv, (double*)Lambda, grads, kws, s, comm, (const double*)Qfull);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_arnoldi_adjoint_sharded", op, true, comm, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return arnoldi_adjoint_t<T>(op, call.nrows, k, p, as<T>(Q), as<T>(H), as<T>(r), as<T>(c), as<T>(dQ), as<T>(dH), as<T>(dr), as<T>(dc),
+                                reortho, as<T>(dv), as<T>(Lambda), grads, call.ws, call.stream, comm, as<T>(Qfull));
+  });
 }
 
 int mfx_lanczos_forward_sharded(const mfx_operator* op, const mfx_comm* comm, const void* v0, int64_t n, int64_t k, int64_t p,
                                 void* xs, void* alpha, void* beta, void* vnorm, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(v0 && xs && alpha && beta && vnorm, MFX_ERR_INVALID, "null argument");
-  MFX_SHARDED_PROLOGUE();
-  if (op->dtype == MFX_F32)
-    return lanczos_forward_t<float>(op, (const float*)v0, nrows, k, p, (float*)xs, (float*)alpha, (float*)beta, (float*)vnorm, kws, s, comm);
-  return lanczos_forward_t<double>(op, (const double*)v0, nrows, k, p, (double*)xs, (double*)alpha, (double*)beta, (double*)vnorm, kws, s, comm);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_lanczos_forward_sharded", op, true, comm, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return lanczos_forward_t<T>(op, as<T>(v0), call.nrows, k, p, as<T>(xs), as<T>(alpha), as<T>(beta), as<T>(vnorm), call.ws, call.stream,
+                                comm);
+  });
 }
 
 int mfx_lanczos_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, int64_t n, int64_t k, int64_t p, const void* xs,
@@ -1152,26 +1149,29 @@ int mfx_lanczos_adjoint_sharded(const mfx_operator* op, const mfx_comm* comm, in
                                 int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && Lambda && Lambdafull, MFX_ERR_INVALID, "null argument");
   MFX_TRY(check_op_grads(op, grads, true));
-  MFX_SHARDED_PROLOGUE();
-  if (op->dtype == MFX_F32)
-    return lanczos_adjoint_t<float>(op, nrows, k, p, (const float*)xs, (const float*)alpha, (const float*)beta, (const float*)vnorm,
-                                    (const float*)dxs, (const float*)dalpha, (const float*)dbeta, (float*)dv, (float*)Lambda, grads,
-                                    kws, s, comm, (float*)Lambdafull);
-  return lanczos_adjoint_t<double>(op, nrows, k, p, (const double*)xs, (const double*)alpha, (const double*)beta, (const double*)vnorm,
-                                   (const double*)dxs, (const double*)dalpha, (const double*)dbeta, (double*)dv, (double*)Lambda, grads,
-                                   kws, s, comm, (double*)Lambdafull);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_lanczos_adjoint_sharded", op, true, comm, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return lanczos_adjoint_t<T>(op, call.nrows, k, p, as<T>(xs), as<T>(alpha), as<T>(beta), as<T>(vnorm), as<T>(dxs), as<T>(dalpha), as<T>(dbeta),
+                                as<T>(dv), as<T>(Lambda), grads, call.ws, call.stream, comm, as<T>(Lambdafull));
+  });
 }
 
 int mfx_lanczos_forward(const mfx_operator* op, const void* v0, int64_t n, int64_t k, int64_t p, void* xs,
                         void* alpha, void* beta, void* vnorm, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(v0 && xs && alpha && beta && vnorm, MFX_ERR_INVALID, "null argument");
-  MFX_DRIVER_PROLOGUE();
-  GraphKey key = driver_key(3, op, n, k, p, nullptr, ws, ws_bytes, stream);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_lanczos_forward", op, false, nullptr, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = driver_key(kIdLanczosForward, op, n, k, p, nullptr, ws, ws_bytes, stream);
   key.add(v0).add(xs).add(alpha).add(beta).add(vnorm);
-  return run_graphed(graph_eligible(op, n, p), key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return lanczos_forward_t<float>(op, (const float*)v0, n, k, p, (float*)xs, (float*)alpha, (float*)beta, (float*)vnorm, kws, st);
-    return lanczos_forward_t<double>(op, (const double*)v0, n, k, p, (double*)xs, (double*)alpha, (double*)beta, (double*)vnorm, kws, st);
+  return run_graphed(graph_eligible(op, n, p), key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return lanczos_forward_t<T>(op, as<T>(v0), n, k, p, as<T>(xs), as<T>(alpha), as<T>(beta), as<T>(vnorm), call.ws, st);
+    });
   });
 }
 
@@ -1180,17 +1180,17 @@ int mfx_lanczos_adjoint(const mfx_operator* op, int64_t n, int64_t k, int64_t p,
                         void* dv, void* Lambda, const mfx_op_grads* grads, void* ws, int64_t ws_bytes, void* stream) {
   MFX_REQUIRE(xs && alpha && beta && vnorm && dalpha && dbeta && Lambda, MFX_ERR_INVALID, "null argument");
   MFX_TRY(check_op_grads(op, grads, false));
-  MFX_DRIVER_PROLOGUE();
-  GraphKey key = driver_key(4, op, n, k, p, grads, ws, ws_bytes, stream);
+  KrylovCall call;
+  MFX_TRY(krylov_prologue("mfx_lanczos_adjoint", op, false, nullptr, n, k, p, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = driver_key(kIdLanczosAdjoint, op, n, k, p, grads, ws, ws_bytes, stream);
   key.add(xs).add(alpha).add(beta).add(vnorm).add(dxs).add(dalpha).add(dbeta).add(dv).add(Lambda);
-  return run_graphed(graph_eligible(op, n, p), key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return lanczos_adjoint_t<float>(op, n, k, p, (const float*)xs, (const float*)alpha, (const float*)beta,
-                                      (const float*)vnorm, (const float*)dxs, (const float*)dalpha, (const float*)dbeta,
-                                      (float*)dv, (float*)Lambda, grads, kws, st);
-    return lanczos_adjoint_t<double>(op, n, k, p, (const double*)xs, (const double*)alpha, (const double*)beta,
-                                     (const double*)vnorm, (const double*)dxs, (const double*)dalpha, (const double*)dbeta,
-                                     (double*)dv, (double*)Lambda, grads, kws, st);
+  return run_graphed(graph_eligible(op, n, p), key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return lanczos_adjoint_t<T>(op, n, k, p, as<T>(xs), as<T>(alpha), as<T>(beta), as<T>(vnorm), as<T>(dxs), as<T>(dalpha), as<T>(dbeta),
+                                  as<T>(dv), as<T>(Lambda), grads, call.ws, st);
+    });
   });
 }
 

@@ -184,11 +184,6 @@ static int lr_apply(int64_t n, int64_t rank, const void* lt, const void* mid, co
   MFX_CHECK_LAUNCH();
   return MFX_OK;
 }
-static int lr_apply(int dtype, int64_t n, int64_t rank, const void* lt, const void* mid, const void* scale, const void* v, int64_t ldv,
-                    void* z, int64_t ldz, int64_t p, const LrWs& w, hipStream_t stream) {
-  if (dtype == MFX_F64) return lr_apply<double>(n, rank, lt, mid, scale, v, ldv, z, ldz, p, w, stream);
-  return lr_apply<float>(n, rank, lt, mid, scale, v, ldv, z, ldz, p, w, stream);
-}
 
 // what the factor of a low-rank apply must satisfy, for the entry point and the operator kind alike
 static int lr_check_factor(const char* who, int dtype, int64_t n, int64_t rank, const void* lt, const void* mid, const void* scale) {
@@ -363,7 +358,8 @@ int mfx_lowrank_apply(int dtype, int64_t n, int64_t rank, const void* lt, const 
   Carver cv(ws, ws_bytes);
   const LrWs w = lr_carve(cv, dtype, n, rank, p);
   MFX_REQUIRE(ws && cv.off <= ws_bytes, MFX_ERR_WORKSPACE, "%s: workspace too small: need %lld bytes", who, (long long)cv.off);
-  return lr_apply(dtype, n, rank, lt, mid, scale, v, ldv, z, ldz, p, w, static_cast<hipStream_t>(stream));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_dtype(dtype, [&](auto t) { return lr_apply<decltype(t)>(n, rank, lt, mid, scale, v, ldv, z, ldz, p, w, s); });
 }
 
 }  // extern "C"

@@ -1078,9 +1078,10 @@ int op_cross_apply(const mfx_operator* op, const void* xnew, int64_t m, const vo
   MFX_REQUIRE(op->kind == MFX_OP_RBF, MFX_ERR_UNSUPPORTED, "cross-covariance matvec needs a kernel-Gram operator");
   MFX_TRY(check_kernel_fn(op));
   ScopedTimer t(0, stream);
-  if (op->dtype == MFX_F32)
-    return rbf_cross_apply<float>(op, (const float*)xnew, m, (const float*)v, ldv, (float*)y, ldy, p, ws, ws_bytes, stream);
-  return rbf_cross_apply<double>(op, (const double*)xnew, m, (const double*)v, ldv, (double*)y, ldy, p, ws, ws_bytes, stream);
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return rbf_cross_apply<T>(op, as<T>(xnew), m, as<T>(v), ldv, as<T>(y), ldy, p, ws, ws_bytes, stream);
+  });
 }
 
 template <typename T>
@@ -1190,9 +1191,10 @@ int op_cross_apply_t(const mfx_operator* op, const void* xnew, int64_t m, const 
                      int64_t p, void* ws, int64_t ws_bytes, hipStream_t stream) {
   MFX_TRY(check_cross_op(op));
   ScopedTimer t(0, stream);
-  if (op->dtype == MFX_F32)
-    return rbf_cross_apply_t<float>(op, (const float*)xnew, m, (const float*)u, ldu, (float*)y, ldy, p, ws, ws_bytes, stream);
-  return rbf_cross_apply_t<double>(op, (const double*)xnew, m, (const double*)u, ldu, (double*)y, ldy, p, ws, ws_bytes, stream);
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return rbf_cross_apply_t<T>(op, as<T>(xnew), m, as<T>(u), ldu, as<T>(y), ldy, p, ws, ws_bytes, stream);
+  });
 }
 
 // Column split of the cross sweep: enough workgroups (owner blocks x selections x splits) to fill the chip, every split at
@@ -1344,8 +1346,8 @@ int op_cross_vjp(const mfx_operator* op, const void* xnew, int64_t m, const void
   MFX_REQUIRE(!grads->dense_a && !grads->val, MFX_ERR_INVALID,
               "the cross-covariance VJP fills the kernel-Gram fields only (dense_a / val must be NULL)");
   ScopedTimer t(1, stream);
-  if (op->dtype == MFX_F32) return cross_vjp_factored<float>(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, stream);
-  return cross_vjp_factored<double>(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, stream);
+  return with_dtype(op->dtype,
+                    [&](auto t) { return cross_vjp_factored<decltype(t)>(op, xnew, m, L, ldl, R, ldr, batch, grads, gxnew, ws, ws_bytes, stream); });
 }
 
 // S (m, n) dense, leading dimension lds: owner X_new reads its rows, owner X its columns.  The row form's 16-byte loads: every
@@ -1365,8 +1367,7 @@ int op_cross_vjp_dense(const mfx_operator* op, const void* xnew, int64_t m, cons
   MFX_REQUIRE(!grads->dense_a && !grads->val, MFX_ERR_INVALID,
               "the cross-covariance VJP fills the kernel-Gram fields only (dense_a / val must be NULL)");
   ScopedTimer t(1, stream);
-  if (op->dtype == MFX_F32) return cross_vjp_dense<float>(op, xnew, m, S, lds, grads, gxnew, ws, ws_bytes, stream);
-  return cross_vjp_dense<double>(op, xnew, m, S, lds, grads, gxnew, ws, ws_bytes, stream);
+  return with_dtype(op->dtype, [&](auto t) { return cross_vjp_dense<decltype(t)>(op, xnew, m, S, lds, grads, gxnew, ws, ws_bytes, stream); });
 }
 
 PrepScope::PrepScope() {
@@ -1625,8 +1626,10 @@ int mfx_gram_block(const mfx_operator* op, const void* xa, int64_t ma, const voi
               "mfx_gram_block: workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
   ScopedTimer t(0, s);
-  if (op->dtype == MFX_F32) return gram_block_t<float>(op, (const float*)xa, ma, (const float*)xb, mb, (float*)out, ldo, w, s);
-  return gram_block_t<double>(op, (const double*)xa, ma, (const double*)xb, mb, (double*)out, ldo, w, s);
+  return with_dtype(op->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return gram_block_t<T>(op, as<T>(xa), ma, as<T>(xb), mb, as<T>(out), ldo, w, s);
+  });
 }
 
 }  // extern "C"

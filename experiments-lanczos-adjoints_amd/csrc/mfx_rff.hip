@@ -387,12 +387,10 @@ extern "C" int mfx_rff_apply(int dtype, const void* x, int64_t ldx, int64_t n, i
   MFX_REQUIRE(out, MFX_ERR_INVALID, "%s: out must not be NULL", who);
   MFX_REQUIRE(ldout >= n, MFX_ERR_INVALID, "%s: ldout = %lld is shorter than a row of out (n = %lld)", who, (long long)ldout,
               (long long)n);
-  if (dtype == MFX_F64) {
-    return rff_run<double>(false, who, x, ldx, n, d, omega, phase, m, lengthscale, ard, outputscale, W, ldw, S, nullptr, 0, out, ldout,
-                           (hipStream_t)stream);
-  }
-  return rff_run<float>(false, who, x, ldx, n, d, omega, phase, m, lengthscale, ard, outputscale, W, ldw, S, nullptr, 0, out, ldout,
-                        (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) -> int {
+    return rff_run<decltype(t)>(false, who, x, ldx, n, d, omega, phase, m, lengthscale, ard, outputscale, W, ldw, S, nullptr, 0, out,
+                                ldout, (hipStream_t)stream);
+  });
 }
 
 extern "C" int mfx_rff_grad_x(int dtype, const void* x, int64_t ldx, int64_t n, int64_t d, const void* omega, const void* phase,
@@ -404,10 +402,8 @@ extern "C" int mfx_rff_grad_x(int dtype, const void* x, int64_t ldx, int64_t n, 
   MFX_REQUIRE(g && dx, MFX_ERR_INVALID, "%s: g and dx must not be NULL", who);
   MFX_REQUIRE(ldg >= n, MFX_ERR_INVALID, "%s: ldg = %lld is shorter than a row of g (n = %lld)", who, (long long)ldg, (long long)n);
   MFX_REQUIRE(lddx >= d, MFX_ERR_INVALID, "%s: lddx = %lld is shorter than a row of dx (d = %lld)", who, (long long)lddx, (long long)d);
-  if (dtype == MFX_F64) {
-    return rff_run<double>(true, who, x, ldx, n, d, omega, phase, m, lengthscale, ard, outputscale, W, ldw, S, g, ldg, dx, lddx,
-                           (hipStream_t)stream);
-  }
-  return rff_run<float>(true, who, x, ldx, n, d, omega, phase, m, lengthscale, ard, outputscale, W, ldw, S, g, ldg, dx, lddx,
-                        (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) -> int {
+    return rff_run<decltype(t)>(true, who, x, ldx, n, d, omega, phase, m, lengthscale, ard, outputscale, W, ldw, S, g, ldg, dx, lddx,
+                                (hipStream_t)stream);
+  });
 }

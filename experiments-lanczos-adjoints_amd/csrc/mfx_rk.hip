@@ -310,20 +310,28 @@ static int rk_check(const mfx_operator* op, const mfx_rk_tableau* tab, const dou
   return MFX_OK;
 }
 
-static GraphKey rk_key(int fn_id, const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, int64_t n,
+// the drivers' common key (depth = the number of steps) and what a captured solve depends on beyond it
+static GraphKey rk_key(DriverId id, const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, int64_t n,
                        int64_t p, const mfx_op_grads* grads, int flags, const void* ws, int64_t ws_bytes, const void* stream) {
-  GraphKey key;
-  key.add(fn_id).add(*op).add(n).add(p).add(nsteps).add(flags).add(ws).add(ws_bytes).add(stream);
-  if (op_kind(op)->graph_key) op_kind(op)->graph_key(op, key);
-  key.add(tab->stages);
+  GraphKey key = driver_key(id, op, n, nsteps, p, grads, ws, ws_bytes, stream);
+  key.add(flags).add(tab->stages);
   for (int i = 0; i < tab->stages; ++i) {
     key.add(tab->b[i]);
     for (int j = 0; j < i; ++j) key.add(tab->a[i][j]);
   }
   for (int64_t i = 0; i < nsteps; ++i) key.add(dts[i]);  // a step size is baked into the kernel arguments of its launches
-  const mfx_op_grads none{};
-  key.add(grads ? *grads : none).add(grads != nullptr);
   return key;
+}
+
+// What a Runge-Kutta entry point holds once nothing is left to refuse.  mode: see rk_carve
+struct RkCall { RkWs ws; hipStream_t stream; };
+static int rk_prologue(const char* fn, const mfx_operator* op, const mfx_rk_tableau* tab, int64_t n, int64_t p, int mode, void* ws,
+                       int64_t ws_bytes, void* stream, RkCall* call) {
+  const int64_t need = rk_carve(op, tab->stages, n, p, mode, ws, ws_bytes, &call->ws);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "%s: workspace too small: %lld bytes given, %lld needed", fn,
+              (long long)ws_bytes, (long long)need);
+  call->stream = static_cast<hipStream_t>(stream);
+  return MFX_OK;
 }
 
 template <typename T>
@@ -346,29 +354,22 @@ int64_t mfx_rk_workspace_bytes(const mfx_operator* op, const mfx_rk_tableau* tab
   return rk_carve(op, tab->stages, n, p, adjoint, nullptr, 0, nullptr);
 }
 
-#define MFX_RK_PROLOGUE(mode)                                                                                                   \
-  RkWs w;                                                                                                                       \
-  const int64_t need = rk_carve(op, tab->stages, n, p, mode, ws, ws_bytes, &w);                                                  \
-  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "workspace too small: %lld bytes given, %lld needed", (long long)ws_bytes, \
-              (long long)need);                                                                                                 \
-  hipStream_t s = static_cast<hipStream_t>(stream);                                                                             \
-  PrepScope prep_scope
-
 int mfx_rk_solve(const mfx_operator* op, const mfx_rk_tableau* tab, const double* dts, int64_t nsteps, const void* y0, int64_t ldy0,
                  int64_t n, int64_t p, void* y1, int64_t ldy1, void* ys, int flags, void* ws, int64_t ws_bytes, void* stream) {
   MFX_TRY(rk_check(op, tab, dts, nsteps, n, p, nullptr, flags));
   MFX_REQUIRE(y0 && y1, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(ldy0 >= n && ldy1 >= n, MFX_ERR_INVALID, "leading dimensions %lld, %lld are shorter than n = %lld", (long long)ldy0,
               (long long)ldy1, (long long)n);
-  MFX_RK_PROLOGUE(0);
-  GraphKey key = rk_key(1, op, tab, dts, nsteps, n, p, nullptr, flags, ws, ws_bytes, stream);
+  RkCall call;
+  MFX_TRY(rk_prologue("mfx_rk_solve", op, tab, n, p, 0, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = rk_key(kIdRkSolve, op, tab, dts, nsteps, n, p, nullptr, flags, ws, ws_bytes, stream);
   key.add(y0).add(ldy0).add(y1).add(ldy1).add(ys);
-  return run_graphed(op_kind(op)->native, key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return rk_solve_t<float>(rk_ctx<float>(op, tab, n, p, w, st), dts, nsteps, (const float*)y0, ldy0, (float*)y1, ldy1,
-                               (float*)ys, w);
-    return rk_solve_t<double>(rk_ctx<double>(op, tab, n, p, w, st), dts, nsteps, (const double*)y0, ldy0, (double*)y1, ldy1,
-                              (double*)ys, w);
+  return run_graphed(op_kind(op)->native, key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return rk_solve_t<T>(rk_ctx<T>(op, tab, n, p, call.ws, st), dts, nsteps, as<T>(y0), ldy0, as<T>(y1), ldy1, as<T>(ys), call.ws);
+    });
   });
 }
 
@@ -379,15 +380,17 @@ int mfx_rk_adjoint(const mfx_operator* op, const mfx_rk_tableau* tab, const doub
   MFX_REQUIRE(ys && dy1, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(lddy1 >= n && (!dy0 || lddy0 >= n), MFX_ERR_INVALID, "leading dimensions %lld, %lld are shorter than n = %lld",
               (long long)lddy1, (long long)lddy0, (long long)n);
-  MFX_RK_PROLOGUE(1);
-  GraphKey key = rk_key(2, op, tab, dts, nsteps, n, p, grads, flags, ws, ws_bytes, stream);
+  RkCall call;
+  MFX_TRY(rk_prologue("mfx_rk_adjoint", op, tab, n, p, 1, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = rk_key(kIdRkAdjoint, op, tab, dts, nsteps, n, p, grads, flags, ws, ws_bytes, stream);
   key.add(ys).add(dy1).add(lddy1).add(dy0).add(lddy0);
-  return run_graphed(op_kind(op)->native, key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return rk_adjoint_t<float>(rk_ctx<float>(op, tab, n, p, w, st), dts, nsteps, (const float*)ys, (const float*)dy1, lddy1,
-                                 (float*)dy0, lddy0, grads, w);
-    return rk_adjoint_t<double>(rk_ctx<double>(op, tab, n, p, w, st), dts, nsteps, (const double*)ys, (const double*)dy1,
-                                lddy1, (double*)dy0, lddy0, grads, w);
+  return run_graphed(op_kind(op)->native, key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return rk_adjoint_t<T>(rk_ctx<T>(op, tab, n, p, call.ws, st), dts, nsteps, as<T>(ys), as<T>(dy1), lddy1, as<T>(dy0), lddy0, grads,
+                             call.ws);
+    });
   });
 }
 
@@ -398,15 +401,17 @@ int mfx_rk_backsolve(const mfx_operator* op, const mfx_rk_tableau* tab, const do
   MFX_REQUIRE(y1 && dy1, MFX_ERR_INVALID, "null argument");
   MFX_REQUIRE(ldy1 >= n && lddy1 >= n && (!dy0 || lddy0 >= n), MFX_ERR_INVALID, "leading dimensions %lld, %lld, %lld are shorter than n = %lld",
               (long long)ldy1, (long long)lddy1, (long long)lddy0, (long long)n);
-  MFX_RK_PROLOGUE(2);
-  GraphKey key = rk_key(3, op, tab, dts, nsteps, n, p, grads, flags, ws, ws_bytes, stream);
+  RkCall call;
+  MFX_TRY(rk_prologue("mfx_rk_backsolve", op, tab, n, p, 2, ws, ws_bytes, stream, &call));
+  PrepScope prep_scope;
+  GraphKey key = rk_key(kIdRkBacksolve, op, tab, dts, nsteps, n, p, grads, flags, ws, ws_bytes, stream);
   key.add(y1).add(ldy1).add(dy1).add(lddy1).add(dy0).add(lddy0);
-  return run_graphed(op_kind(op)->native, key, s, [&](hipStream_t st) {
-    if (op->dtype == MFX_F32)
-      return rk_backsolve_t<float>(rk_ctx<float>(op, tab, n, p, w, st), dts, nsteps, (const float*)y1, ldy1, (const float*)dy1,
-                                   lddy1, (float*)dy0, lddy0, grads, w);
-    return rk_backsolve_t<double>(rk_ctx<double>(op, tab, n, p, w, st), dts, nsteps, (const double*)y1, ldy1,
-                                  (const double*)dy1, lddy1, (double*)dy0, lddy0, grads, w);
+  return run_graphed(op_kind(op)->native, key, call.stream, [&](hipStream_t st) {
+    return with_dtype(op->dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return rk_backsolve_t<T>(rk_ctx<T>(op, tab, n, p, call.ws, st), dts, nsteps, as<T>(y1), ldy1, as<T>(dy1), lddy1, as<T>(dy0), lddy0,
+                               grads, call.ws);
+    });
   });
 }
 

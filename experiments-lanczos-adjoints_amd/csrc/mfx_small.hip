@@ -177,23 +177,16 @@ int mfx_tridiag_eigh(const void* alpha, const void* beta, int64_t ldbeta, int64_
   MFX_REQUIRE(k <= kSmallMaxDepth, MFX_ERR_UNSUPPORTED, "tridiagonal eigensolver supports k <= %d (got %lld)", kSmallMaxDepth, (long long)k);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t sh = (size_t)(2 * k + (deep ? 0 : k * (k | 1))) * sizeof(double);
-  if (dtype == MFX_F32) {
-    MFX_TRY(allow_big_lds(k_tridiag_eigh<float, false>, sh));
-    k_tridiag_eigh<float, false><<<(unsigned)p, 64, sh, s>>>((const float*)alpha, (const float*)beta, ldbeta, (int)k,
-                                                             (float*)evals, (float*)evecs);
-  } else if (dtype == MFX_F64 && deep) {
-    k_tridiag_eigh<double, true><<<(unsigned)p, 64, sh, s>>>((const double*)alpha, (const double*)beta, ldbeta, (int)k,
-                                                             (double*)evals, (double*)evecs);
-  } else if (dtype == MFX_F64) {
-    MFX_TRY(allow_big_lds(k_tridiag_eigh<double, false>, sh));
-    k_tridiag_eigh<double, false><<<(unsigned)p, 64, sh, s>>>((const double*)alpha, (const double*)beta, ldbeta, (int)k,
-                                                              (double*)evals, (double*)evecs);
-  } else {
-    set_error("unsupported dtype %d", dtype);
-    return MFX_ERR_UNSUPPORTED;
-  }
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return with_flag(deep, [&](auto deep_tag) -> int {
+      constexpr bool DEEP = decltype(deep_tag)::value && sizeof(T) == 8;  // fp32 is never deep: refused above
+      if constexpr (!DEEP) MFX_TRY(allow_big_lds(k_tridiag_eigh<T, DEEP>, sh));  // the deep kernel stays under 64 KiB
+      k_tridiag_eigh<T, DEEP><<<(unsigned)p, 64, sh, s>>>(as<T>(alpha), as<T>(beta), ldbeta, (int)k, as<T>(evals), as<T>(evecs));
+      MFX_CHECK_LAUNCH();
+      return MFX_OK;
+    });
+  });
 }
 
 int mfx_slq_quadform_bwd(const void* evals, const void* evecs, const void* fvals, const void* dfvals,
@@ -204,30 +197,17 @@ int mfx_slq_quadform_bwd(const void* evals, const void* evecs, const void* fvals
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool deep = k > kSmallLdsDepth;
   const size_t sh = (size_t)(deep ? 4 * k : k * k) * sizeof(double);
-#define MFX_QF_LAUNCH(T, DEEP)                                                                                                 \
-  k_quadform_bwd<T, DEEP><<<(unsigned)p, 64, sh, s>>>((const T*)evals, (const T*)evecs, (const T*)fvals, (const T*)dfvals,    \
-                                                      (const T*)gout, (int)k, (T*)dalpha, (T*)dbeta, lddbeta)
-  if (dtype == MFX_F32) {
-    if (deep) {
-      MFX_QF_LAUNCH(float, true);
-    } else {
-      MFX_TRY(allow_big_lds(k_quadform_bwd<float, false>, sh));
-      MFX_QF_LAUNCH(float, false);
-    }
-  } else if (dtype == MFX_F64) {
-    if (deep) {
-      MFX_QF_LAUNCH(double, true);
-    } else {
-      MFX_TRY(allow_big_lds(k_quadform_bwd<double, false>, sh));
-      MFX_QF_LAUNCH(double, false);
-    }
-  } else {
-    set_error("unsupported dtype %d", dtype);
-    return MFX_ERR_UNSUPPORTED;
-  }
-#undef MFX_QF_LAUNCH
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    return with_flag(deep, [&](auto deep_tag) -> int {
+      constexpr bool DEEP = decltype(deep_tag)::value;
+      if constexpr (!DEEP) MFX_TRY(allow_big_lds(k_quadform_bwd<T, DEEP>, sh));  // the deep kernel stays under 64 KiB
+      k_quadform_bwd<T, DEEP><<<(unsigned)p, 64, sh, s>>>(as<T>(evals), as<T>(evecs), as<T>(fvals), as<T>(dfvals), as<T>(gout), (int)k,
+                                                          as<T>(dalpha), as<T>(dbeta), lddbeta);
+      MFX_CHECK_LAUNCH();
+      return MFX_OK;
+    });
+  });
 }
 
 int mfx_rademacher(uint64_t seed, int64_t first_probe, int64_t p, int64_t n, int dtype, void* out, void* stream) {
@@ -235,16 +215,12 @@ int mfx_rademacher(uint64_t seed, int64_t first_probe, int64_t p, int64_t n, int
   hipStream_t s = static_cast<hipStream_t>(stream);
   int64_t gx = (n + 255) / 256;
   if (gx > 2048) gx = 2048;
-  if (dtype == MFX_F32) {
-    k_rademacher<float><<<dim3((unsigned)gx, (unsigned)p), 256, 0, s>>>(seed, first_probe, n, (float*)out);
-  } else if (dtype == MFX_F64) {
-    k_rademacher<double><<<dim3((unsigned)gx, (unsigned)p), 256, 0, s>>>(seed, first_probe, n, (double*)out);
-  } else {
-    set_error("unsupported dtype %d", dtype);
-    return MFX_ERR_UNSUPPORTED;
-  }
-  MFX_CHECK_LAUNCH();
-  return MFX_OK;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    k_rademacher<T><<<dim3((unsigned)gx, (unsigned)p), 256, 0, s>>>(seed, first_probe, n, as<T>(out));
+    MFX_CHECK_LAUNCH();
+    return MFX_OK;
+  });
 }
 
 }  // extern "C"

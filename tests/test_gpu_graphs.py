@@ -107,3 +107,72 @@ def test_graph_replay_hessenberg_matches_the_eager_first_call(reortho):
         del Q, H, r, c, dv, dA, got
     cap1, rep1 = _lib.graph_stats()
     assert cap1 - cap0 >= 1 and rep1 - rep0 >= 2  # (which calls repeat an address pattern is the allocator's business)
+
+
+def _three_drivers_one_workspace():
+    """mfx_arnoldi_forward, mfx_rk_solve and mfx_lanczos_forward, three calls each, on ONE dense operator, workspace and stream
+    (n = 96, depth 4, one vector, fp64: launch-bound) -> (their outputs after the third call, graphs captured per sequence)"""
+    import ctypes
+
+    lib, n, k, p = _lib.get(), 96, 4, 1
+    g = torch.Generator().manual_seed(3)
+    B = torch.randn(n, n, dtype=torch.float64, generator=g)
+    A = (B @ B.T / n + torch.eye(n, dtype=torch.float64)).to(DEV)
+    v0 = torch.randn(p, n, dtype=torch.float64, generator=g).to(DEV)
+    desc = _lib.Operator()
+    desc.kind, desc.dtype, desc.n, desc.dense_a, desc.lda = _lib.OP_DENSE, _lib.MFX_F64, n, A.data_ptr(), n
+    tab = _lib.RkTableau()  # Heun
+    tab.stages = 2
+    tab.a[1][0] = 1.0
+    tab.b[0] = tab.b[1] = 0.5
+    dts = (ctypes.c_double * 2)(-0.01, -0.01)
+    op, ptr = ctypes.byref(desc), _lib.ptr
+    need = max(lib.mfx_workspace_bytes(op, n, k, p), lib.mfx_rk_workspace_bytes(op, ctypes.byref(tab), n, p, 0))
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    stream = _lib.stream_ptr(DEV)
+    new = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=DEV)
+    Q, H, r, c = new(p, k, n), new(p, k, k), new(p, n), new(p)
+    y1 = new(p, n)
+    xs, alpha, beta, vnorm = new(p, k + 1, n), new(p, k), new(p, k), new(p)
+    sequences = (
+        lambda: lib.mfx_arnoldi_forward(op, ptr(v0), n, k, p, 1, ptr(Q), ptr(H), ptr(r), ptr(c), ptr(ws), need, stream),
+        lambda: lib.mfx_rk_solve(op, ctypes.byref(tab), dts, 2, ptr(v0), n, n, p, ptr(y1), n, None, 0, ptr(ws), need, stream),
+        lambda: lib.mfx_lanczos_forward(op, ptr(v0), n, k, p, ptr(xs), ptr(alpha), ptr(beta), ptr(vnorm), ptr(ws), need, stream),
+    )
+    captured = []
+    with torch.cuda.device(DEV):
+        for call in sequences:
+            cap0, _ = _lib.graph_stats()
+            for _ in range(3):  # eager, captured, replayed
+                _lib.check(call())
+            torch.cuda.synchronize()
+            captured.append(_lib.graph_stats()[0] - cap0)
+    return [t.cpu() for t in (Q, H, r, c, y1, xs, alpha, beta, vnorm)], captured
+
+
+def test_drivers_that_share_operator_workspace_and_stream_capture_their_own_graphs(tmp_path):
+    """The graph keys of the Krylov and the Runge-Kutta drivers start with ids from one enum: after an Arnoldi forward has been
+    captured and replayed, a Runge-Kutta solve and a Lanczos forward on the same operator, workspace and stream each capture a
+    graph of their own, and give bit for bit what eager launches give (MFX_GRAPHS=0 is read once per process: a fresh child)."""
+    import os
+    import subprocess
+    import sys
+
+    got, captured = _three_drivers_one_workspace()
+    assert captured == [1, 1, 1], captured
+    out = tmp_path / "eager.pt"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = os.pathsep.join([root, os.path.join(root, "experiments-lanczos-adjoints_amd"), os.environ.get("PYTHONPATH", "")])
+    subprocess.run([sys.executable, os.path.abspath(__file__), str(out)], check=True, env=dict(os.environ, MFX_GRAPHS="0", PYTHONPATH=path),
+                   timeout=120)
+    eager = torch.load(out)
+    assert eager["captured"] == [0, 0, 0]
+    for a, b in zip(got, eager["outputs"]):
+        assert torch.equal(a, b)
+
+
+if __name__ == "__main__":  # the eager child of the test above
+    import sys
+
+    outputs, captured = _three_drivers_one_workspace()
+    torch.save({"outputs": outputs, "captured": captured}, sys.argv[1])

@@ -270,6 +270,30 @@ def test_tridiag_eigh_and_quadform_backward(dtype, tol, k):
             assert close(ge[b], re, tol * 20, atol_rel=tol * 20)
 
 
+@pytest.mark.parametrize("p", [1, 3])
+def test_quadform_backward_fp32_buffers_beyond_depth_120(p):
+    """mfx_slq_quadform_bwd on fp32 buffers at k = 121, the first depth whose divided differences are evaluated in place and not in
+    LDS.  lanczos._QuadformFn casts an fp32 problem to fp64 beyond depth 120 (the eigensolver needs fp64 buffers there), so no
+    other test runs this kernel in fp32.  Eigenpairs from the fp64 oracle, rounded to fp32; the gradient against the oracle's at the
+    fp32 tolerance of test_tridiag_eigh_and_quadform_backward."""
+    k, tol = 121, 3e-5
+    rng = np.random.default_rng(k + p)
+    d = rng.uniform(1.0, 3.0, size=(p, k))
+    e = rng.uniform(0.1, 0.5, size=(p, k - 1))
+    refs = [orc.quadform_from_tridiag(d[b], e[b], "log") for b in range(p)]
+    f32 = torch.float32
+    evals = T(np.stack([lam for _, _, (lam, _) in refs]), f32)
+    evecs = T(np.stack([U for _, _, (_, U) in refs]), f32).contiguous()
+    fx, dfx, gout = torch.log(evals), 1.0 / evals, torch.ones(p, dtype=f32, device=DEV)
+    dalpha, dbeta = torch.empty((p, k), dtype=f32, device=DEV), torch.empty((p, k - 1), dtype=f32, device=DEV)
+    _lib.check(_lib.get().mfx_slq_quadform_bwd(_lib.ptr(evals), _lib.ptr(evecs), _lib.ptr(fx), _lib.ptr(dfx), _lib.ptr(gout), p, k,
+                                               _lib.dtype_code(f32), _lib.ptr(dalpha), _lib.ptr(dbeta), k - 1, _lib.stream_ptr(DEV)))
+    torch.cuda.synchronize()
+    for b, (_, (rd, re), _) in enumerate(refs):
+        assert close(dalpha[b], rd, tol * 20, atol_rel=tol * 20)
+        assert close(dbeta[b], re, tol * 20, atol_rel=tol * 20)
+
+
 def test_rademacher_bit_exact_and_shardable():
     x_like = torch.empty(1000, dtype=torch.float32, device=DEV)
     full = hutchinson.sampler_rademacher(x_like, num=6)(11)
