@@ -155,7 +155,7 @@ struct Carver {
 
 // operator layer (mfx_ops.hip)
 // The rules of ONE operator kind (MFX_OP_*).  Each kind fills in one of these next to its kernels (dense, CSR, callback:
-// mfx_ops.hip; kernel-Gram: mfx_rbf_valu.hip; stencil: mfx_stencil.hip; GGN: mfx_ggn.hip; preconditioned: mfx_lowrank.hip); the drivers reach a kind through the generic functions below only.
+// mfx_ops.hip; kernel-Gram: mfx_rbf_valu.hip; stencil: mfx_stencil.hip; GGN: mfx_ggn.hip; preconditioned: mfx_lowrank.hip; affine: mfx_affine.hip); the drivers reach a kind through the generic functions below only.
 struct OpKind {
   int (*check)(const mfx_operator* op);  // every refusal of the descriptor that is specific to the kind, before any launch
   // the gradient fields the kind does not have (NULL: every field but grads->x, the input gradient of a kernel-Gram operator)

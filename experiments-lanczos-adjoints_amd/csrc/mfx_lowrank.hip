@@ -210,6 +210,9 @@ static int pc_check(const mfx_operator* op) {
   MFX_REQUIRE(in, MFX_ERR_INVALID, "%s: pc_inner is NULL", kPcWho);
   MFX_REQUIRE(in->kind != MFX_OP_PRECOND && in->kind != MFX_OP_CALLBACK, MFX_ERR_INVALID,
               "%s: the inner operator must be native and not itself preconditioned (kind %d)", kPcWho, in->kind);
+  MFX_REQUIRE(in->kind != MFX_OP_AFFINE, MFX_ERR_INVALID,
+              "%s: the inner operator must not be affine (its bordered matrix is not symmetric, and the drift gradient belongs to the "
+              "affine kind alone)", kPcWho);
   MFX_TRY(check_op(in));
   MFX_REQUIRE(op_kind(in)->native, MFX_ERR_INVALID, "%s: the inner operator must be native", kPcWho);
   MFX_REQUIRE(in->dtype == op->dtype, MFX_ERR_INVALID, "%s: dtype %d, inner operator %d", kPcWho, op->dtype, in->dtype);

@@ -1,7 +1,7 @@
 // libmfx: operators A(theta) -- apply, transpose-apply and the deferred parameter-gradient sweep
 //   d/dtheta sum_b L_b^T A(theta) R_b        (arnoldi.py:207-209, lanczos.py:328-329)
 // The table of operator kinds and the generic functions every driver goes through, with the DENSE and CSR kinds and the CALLBACK
-// trampoline.  The other kinds stand next to their kernels: kernel-Gram in mfx_rbf_valu.hip, stencil, GGN, preconditioned.
+// trampoline.  The other kinds stand next to their kernels: kernel-Gram in mfx_rbf_valu.hip, stencil, GGN, preconditioned, affine.
 #include "mfx_internal.h"
 #include "mfx_rbf.h"
 
@@ -217,11 +217,11 @@ static const OpKind kCallbackKind = {callback_check, nullptr, nullptr, {op_apply
                                      "row sharding needs a native operator", false, nullptr};
 
 // ---- the table and the generic functions every driver goes through -----------------------------------
-const OpKind *stencil_kind(), *ggn_kind(), *precond_kind();  // mfx_stencil.hip, mfx_ggn.hip, mfx_lowrank.hip
+const OpKind *stencil_kind(), *ggn_kind(), *precond_kind(), *affine_kind();  // mfx_stencil.hip, mfx_ggn.hip, mfx_lowrank.hip, mfx_affine.hip
 
 const OpKind* op_kind(const mfx_operator* op) {
   static const OpKind* const kinds[] = {&kDenseKind, &kCsrKind, gram_kind(), &kCallbackKind, stencil_kind(), ggn_kind(),
-                                       precond_kind()};  // by MFX_OP_*
+                                       precond_kind(), affine_kind()};  // by MFX_OP_*
   return op->kind >= 0 && op->kind < (int)(sizeof(kinds) / sizeof(kinds[0])) ? kinds[op->kind] : nullptr;
 }
 
@@ -247,6 +247,7 @@ int check_op_sharded(const mfx_operator* op, const mfx_comm* cm, int64_t n) {
 int check_op_grads(const mfx_operator* op, const mfx_op_grads* grads, bool sharded) {
   if (!op || !grads) return MFX_OK;
   const OpKind* kind = op_kind(op);
+  MFX_REQUIRE(!grads->drift || op->kind == MFX_OP_AFFINE, MFX_ERR_INVALID, "the drift gradient (grads->drift) needs an affine operator");
   if (kind && kind->check_grads) return kind->check_grads(op, grads, sharded);
   MFX_REQUIRE(!grads->x, MFX_ERR_INVALID, "the input gradient (grads->x) needs a kernel-Gram operator");
   return MFX_OK;

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFX_LIBRARY_PATH") or os.path.join(_HERE, "libmfx.so")  # override: A/B builds
 
 MFX_F32, MFX_F64 = 0, 1
-OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL, OP_GGN, OP_PRECOND = 0, 1, 2, 3, 4, 5, 6
+OP_DENSE, OP_CSR, OP_RBF, OP_CALLBACK, OP_STENCIL, OP_GGN, OP_PRECOND, OP_AFFINE = 0, 1, 2, 3, 4, 5, 6, 7
 STENCIL_HEAT, STENCIL_HEAT2, STENCIL_WAVE = 0, 1, 2
 BOUNDARY_DIRICHLET, BOUNDARY_NEUMANN = 0, 1
 GGN_CROSS_ENTROPY, GGN_MSE = 0, 1
@@ -93,6 +93,15 @@ class Precond(C.Structure):
     ]
 
 
+class Affine(C.Structure):
+    """mirror of ``struct mfx_affine``: what ``Operator.ctx`` points at for ``OP_AFFINE`` (a host struct)."""
+
+    _fields_ = [
+        ("af_inner", C.c_void_p),  # const mfx_operator* (host): ctypes.addressof of the inner descriptor, which the owner keeps alive
+        ("af_b", C.c_void_p),
+    ]
+
+
 class GgnNet(C.Structure):
     """mirror of ``struct mfx_ggn_net``: what ``Operator.ctx`` points at for ``OP_GGN`` (a host struct of device pointers)."""
 
@@ -142,6 +151,7 @@ class OpGrads(C.Structure):
         ("lengthscale", C.c_void_p),
         ("outputscale", C.c_void_p),
         ("noise", C.c_void_p),
+        ("drift", C.c_void_p),
         ("x", C.c_void_p),
     ]
 

@@ -16,6 +16,7 @@ whole Krylov loop, the transposed matvec and the parameter-gradient sweep run as
   StencilOp(shape, stencil, ...)    params = (coef,) or ()        util/pde_util.py:74-157 (3x3 heat / wave systems, matrix-free)
   GgnMlpOp(x_train, theta, widths)  params = (alpha,)             util/bnn_util.py:263-293,477-499 (GGN of an MLP + alpha I, theta fixed)
   PreconditionedOp(op, pre, s)      params = those of ``op``      P^-1/2 A P^-1/2 for a low_rank.Preconditioner held constant
+  AffineOp(op)                      params = (*those of ``op``, drift)  util/pde_util.py:90-103 (y' = A y + b as [[A, b], [0, 0]] on (y, 1))
   CallbackOp(fn)                    any Python ``fn(v, *params)`` (torch ops); per-step host control
 
 ``MlpJacobian(x, theta, widths)`` is not an operator (it is rectangular): the Jacobian of the same MLP at the points x as the pair of
@@ -114,6 +115,9 @@ class RowShardedOp:
         if isinstance(op, PreconditionedOp):
             raise NotImplementedError("row sharding a PreconditionedOp is not implemented: L would need its rows sharded and L^T v "
                                       "all-reduced, as the row-sharded PCG does; shard the probes")
+        if isinstance(op, AffineOp):
+            raise NotImplementedError("row sharding an AffineOp is not implemented: the border row and column belong to no shard; "
+                                      "shard the probes")
         if isinstance(op, GgnMlpOp):
             raise NotImplementedError("row sharding a GgnMlpOp is not implemented: every output row sums over all samples; shard the probes")
         _refuse_input_grad(op)
@@ -1152,6 +1156,9 @@ class PreconditionedOp(NativeOp):
         if not isinstance(op, NativeOp) or isinstance(op, PreconditionedOp):
             raise TypeError("PreconditionedOp needs a native operator (DenseOp, CsrOp, RbfGramOp, StencilOp, GgnMlpOp) that is not "
                             "itself preconditioned")
+        if isinstance(op, AffineOp):
+            raise TypeError("PreconditionedOp does not take an AffineOp: the bordered matrix [[A, b], [0, 0]] is not symmetric, and "
+                            "the drift gradient belongs to the affine operator alone")
         self.op, self.pre = op, pre
         self.s = s.detach() if torch.is_tensor(s) else s
         self._factor = None
@@ -1186,6 +1193,73 @@ class PreconditionedOp(NativeOp):
         pc.pc_rank = self.pre.rank
         desc.ctx = C.addressof(pc)
         desc._keep = (pc, inner, mid, scale)  # the host struct and the inner descriptor live as long as the outer one
+        return desc
+
+
+class AffineOp(NativeOp):
+    """The affine vector field y' = A(theta) y + b as a LINEAR operator on the state (y, 1), one entry longer:
+
+      B (y, s) = (A y + s b, 0)          exp(t B) (y0, 1) = (e^{tA} y0 + t phi_1(tA) b, 1)
+
+    so ``arnoldi.hessenberg``, ``expm_arnoldi``, ``solver_expm`` and ``solver_rk`` with both adjoints integrate the affine field through
+    the drivers of linear ones (every explicit Runge-Kutta scheme on B is, stage by stage, the same scheme on y' = A y + b).  ``op`` is
+    a ``DenseOp``, ``CsrOp``, ``StencilOp``, ``RbfGramOp`` or ``GgnMlpOp``; the parameters are ``(*params of op, drift)``, the drift
+    with ``op``'s number of unknowns in any shape, all differentiable; ``size`` is ``op``'s plus one.  ``lift`` / ``drop`` move between
+    y and (y, 1).  The border runs in libmfx (``MFX_OP_AFFINE``, csrc/mfx_affine.hip) behind the inner operator's own kernels."""
+
+    kind = _lib.OP_AFFINE
+
+    def __init__(self, op):
+        if not isinstance(op, NativeOp) or isinstance(op, (PreconditionedOp, AffineOp)):
+            raise TypeError("AffineOp needs a native operator (DenseOp, CsrOp, StencilOp, RbfGramOp, GgnMlpOp) that is neither "
+                            "preconditioned nor affine itself")
+        self.op = op
+        self._refuse_inputs()
+
+    def _refuse_inputs(self):
+        if differentiable_inputs(self.op):
+            raise NotImplementedError("AffineOp does not return the gradient with respect to the kernel inputs X of its inner "
+                                      "RbfGramOp; pass X.detach()")
+
+    @staticmethod
+    def lift(y):
+        """(..., n) -> (..., n + 1): a 1 appended to the last axis."""
+        return torch.cat([y, y.new_ones((*y.shape[:-1], 1))], dim=-1)
+
+    @staticmethod
+    def drop(z):
+        """(..., n + 1) -> (..., n): the last entry removed."""
+        return z[..., :-1]
+
+    def constrain(self, *params):
+        self._refuse_inputs()
+        if not params:
+            raise TypeError("AffineOp: the drift is the last parameter")
+        return (*self.op.constrain(*params[:-1]), params[-1].reshape(-1).contiguous())
+
+    def size(self, *cparams):
+        return self.op.size(*cparams[:-1]) + 1
+
+    def new_grads(self, *cparams):
+        s, grads = self.op.new_grads(*cparams[:-1])
+        g = torch.zeros_like(cparams[-1])
+        s.drift = g.data_ptr()
+        return s, (*grads, g)
+
+    def descriptor(self, cparams, dtype, n):
+        drift = cparams[-1]
+        inner = self.op.descriptor(cparams[:-1], dtype, n - 1)
+        desc = _lib.Operator()
+        desc.kind, desc.dtype, desc.n = self.kind, _lib.dtype_code(dtype), n
+        _check_dtype(desc, drift, "AffineOp: the drift")
+        if drift.numel() != n - 1:
+            raise ValueError(f"AffineOp: a drift of {drift.numel()} values around an operator of {n - 1} unknowns")
+        _lib.require_device(drift)
+        af = _lib.Affine()
+        af.af_inner, af.af_b = C.addressof(inner), drift.data_ptr()
+        desc.ctx = C.addressof(af)
+        desc._keep = (af, inner)  # the host struct and the inner descriptor live as long as the outer one
+        desc._params = tuple(cparams)
         return desc
 
 

@@ -13,8 +13,9 @@ The reference's stencil vector fields themselves -- ``pde_heat`` / ``pde_heat_af
 The fixed-step Runge-Kutta baselines of the work-precision study (``solver_euler`` / ``solver_diffrax``, :177-237) are ``solver_rk``:
 the whole solve, its discrete adjoint and the continuous ("backsolve") adjoint are single libmfx driver calls (``mfx_rk_solve`` /
 ``mfx_rk_adjoint`` / ``mfx_rk_backsolve``, csrc/mfx_rk.hip) on LINEAR autonomous fields y' = A y, A a native, bound or callback
-operator.  Out of scope: adaptive step sizes, nonlinear or affine fields (``pde_heat_affine`` has no ``rhs.flat``), gradients with
-respect to the times, row-sharded operators.
+operator.  AFFINE fields y' = A y + b go through ``operators.AffineOp``, the bordered linear operator on (y, 1): ``rhs.flat`` of
+``pde_heat_affine`` is one, and ``solver_expm`` / ``solver_rk`` / ``solver_euler`` lift the state, solve and drop the last entry.
+Out of scope: adaptive step sizes, nonlinear fields, gradients with respect to the times, row-sharded operators.
 """
 
 from __future__ import annotations
@@ -25,7 +26,7 @@ import torch
 import ctypes as C
 
 from .. import _lib, arnoldi, lanczos
-from ..operators import (BoundOp, CallbackOp, CsrOp, DriverCall, NativeOp, RbfGramOp, RowShardedOp, StencilOp, as_operator, rebuild_params,
+from ..operators import (AffineOp, BoundOp, CallbackOp, CsrOp, DriverCall, NativeOp, RbfGramOp, RowShardedOp, StencilOp, as_operator, rebuild_params,
                          stash_params)
 from . import rk_tableaux
 
@@ -107,8 +108,14 @@ def solver_expm(t0, t1, vector_field, /, expm):
     a bound one (``rhs.flat`` of the stencil vector fields below) acts on the flattened state and goes to ``expm`` as it is: the
     Krylov loop then applies it natively instead of calling back into Python."""
 
+    affine, bound = as_operator(vector_field) if isinstance(vector_field, (NativeOp, BoundOp)) else (None, None)
+
     def solve(y0, *p):
         shape = y0.shape
+        if isinstance(affine, AffineOp):  # exp(dt B) (y0, 1) = (y(t1), 1) on the bordered operator
+            m = affine.size(*affine.constrain(*(bound or ()), *p)) - 1
+            out, info = expm(vector_field, t1 - t0, AffineOp.lift(_states_of(y0, m)), *p)
+            return AffineOp.drop(out).reshape(shape), info
         if isinstance(vector_field, (NativeOp, BoundOp, RowShardedOp)):
             out, info = expm(vector_field, t1 - t0, y0.reshape(-1), *p)
             return out.reshape(shape), info
@@ -116,6 +123,15 @@ def solver_expm(t0, t1, vector_field, /, expm):
         return out.reshape(shape), info
 
     return solve
+
+
+def _states_of(y0, n):
+    """y0 as one state (n,) or, with one more dimension than the operator's state, a batch (p, n)."""
+    if y0.numel() == n:
+        return y0.reshape(n)
+    if y0.dim() >= 2 and y0.shape[0] * n == y0.numel():
+        return y0.reshape(y0.shape[0], n)
+    raise ValueError(f"a state of shape {tuple(y0.shape)} does not match the operator's {n} unknowns")
 
 
 _RK_ADJOINTS = {"discrete": "discrete", "recursive_checkpoint": "discrete", "direct": "discrete", "backsolve": "backsolve"}
@@ -209,7 +225,8 @@ def _rk_solver(dts, vector_field, method, adjoint):
     if not isinstance(vector_field, (NativeOp, BoundOp, CallbackOp, RowShardedOp)):
         raise TypeError("solver_rk integrates LINEAR autonomous fields y' = A y: vector_field must be a linear operator -- a native "
                         "operator, op.bind(*params) (rhs.flat of the stencil vector fields) or operators.CallbackOp(fn) -- not a "
-                        f"plain callable ({type(vector_field).__name__}); nonlinear and affine fields are out of scope")
+                        f"plain callable ({type(vector_field).__name__}); affine fields y' = A y + b go through operators.AffineOp (rhs.flat of "
+                        "pde_heat_affine), nonlinear fields are out of scope")
     op, bound = as_operator(vector_field)
     if isinstance(op, RowShardedOp):
         raise NotImplementedError("solver_rk does not take row-sharded operators (the stage kernels have no halo exchange or "
@@ -222,6 +239,10 @@ def _rk_solver(dts, vector_field, method, adjoint):
         params = (tuple(bound) if bound is not None else ()) + tuple(p)
         cparams = op.constrain(*params)
         n = op.size(*cparams) if isinstance(op, NativeOp) else y0.numel()  # a callback's state is whatever it is handed
+        if isinstance(op, AffineOp):  # the scheme on (y, 1) is, stage by stage, the scheme on y' = A y + b
+            Y0 = AffineOp.lift(_states_of(y0, n - 1).reshape(-1, n - 1))
+            y1 = AffineOp.drop(fn.apply(op, tab, dts, Y0, *cparams))
+            return y1.reshape(y0.shape), {"num_matvecs": len(dts) * tab.order, "num_applies": len(dts) * len(tab.b)}
         if y0.numel() == n:
             Y0 = y0.reshape(1, n)
         elif y0.dim() >= 2 and y0.shape[0] * n == y0.numel():  # one more dimension than the operator's state: a batch
@@ -325,7 +346,8 @@ def _boundary_kind(boundary):
 
 def _stencil_rhs(form, stencil, boundary, coef, shape, drift=None):
     """rhs(x) on (ny, nx) / (2, ny, nx) states through StencilOp; ``rhs.flat`` (when the grid is known up front): the bound
-    operator on flattened states, for solver_expm / expm_arnoldi / arnoldi.hessenberg."""
+    operator on flattened states, for solver_expm / expm_arnoldi / arnoldi.hessenberg -- with a drift the bordered AffineOp on
+    (state, 1)."""
     kind = _boundary_kind(boundary)
     blocks = 1 if form == "heat" else 2
     ops = {}
@@ -344,6 +366,8 @@ def _stencil_rhs(form, stencil, boundary, coef, shape, drift=None):
 
     if shape is not None and drift is None:
         rhs.flat = operator(tuple(shape)).bind(*(() if coef is None else (coef,)))
+    elif shape is not None:
+        rhs.flat = AffineOp(operator(tuple(shape))).bind(*(() if coef is None else (coef,)), drift.reshape(-1))
     return rhs
 
 
@@ -358,10 +382,11 @@ def pde_heat(c: float, /, stencil, *, boundary, shape=None):
 
 
 def pde_heat_affine(c: float, drift_like, /, stencil, *, boundary):
-    """util/pde_util.py:90-103: pde_heat plus a drift field, added in torch (affine, so there is no ``rhs.flat``)."""
+    """util/pde_util.py:90-103: pde_heat plus a drift field.  ``rhs(x)`` adds it in torch; ``rhs.flat`` is the bordered linear
+    operator ``AffineOp(StencilOp(...))`` on (u, 1), bound to the drift, for solver_expm / solver_rk / solver_euler."""
 
     def parametrize(*, drift):
-        return _stencil_rhs("heat", c * torch.as_tensor(stencil, dtype=torch.float64), boundary, None, None, drift=drift)
+        return _stencil_rhs("heat", c * torch.as_tensor(stencil, dtype=torch.float64), boundary, None, tuple(drift_like.shape), drift=drift)
 
     return parametrize, {"drift": torch.empty_like(drift_like)}
 

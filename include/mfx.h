@@ -36,6 +36,7 @@ extern "C" {
 enum { MFX_F32 = 0, MFX_F64 = 1 };
 enum { MFX_OP_DENSE = 0, MFX_OP_CSR = 1, MFX_OP_RBF = 2, MFX_OP_CALLBACK = 3, MFX_OP_STENCIL = 4, MFX_OP_GGN = 5 };
 enum { MFX_OP_PRECOND = 6 }; /* S A S around a native operator, S = P^-1/2 of the partial-Cholesky preconditioner: struct mfx_precond */
+enum { MFX_OP_AFFINE = 7 };  /* [[A, b], [0, 0]] around a native operator A: the affine field y' = A y + b as a linear one: struct mfx_affine */
 /* Matrix-free 3x3 stencil operator (MFX_OP_STENCIL; util/pde_util.py:18-157).  With S the padded 3x3 correlation below and coef
  * the coefficient field:
  *   MFX_STENCIL_HEAT   state u,       n = ny nx:    y = coef o (S u)                  pde_heat                (:74-87)
@@ -171,6 +172,7 @@ int mfx_ggn_diag(const mfx_ggn_net* net, int dtype, void* diag, void* ws, int64_
  *   STENCIL  coef o conv3x3(pad(u))         util/pde_util.py:74-157 (heat / wave systems, both boundaries)
  *   GGN      (sum_i J_i^T H_i J_i + alpha I) x  util/bnn_util.py:263-293,477-499 (MLP, fixed theta; struct mfx_ggn_net above)
  *   PRECOND  S A S x, S = P^-1/2 held constant  (not in the reference) a native operator A between two low-rank applies (struct mfx_precond below)
+ *   AFFINE   (A x + x_last b, 0)            util/pde_util.py:90-103 (pde_heat_affine): a native operator A in a rank-one border (struct mfx_affine below)
  *   CALLBACK any Python callable                                                              */
 typedef struct mfx_operator {
   int32_t kind;  /* MFX_OP_* */
@@ -208,7 +210,7 @@ typedef struct mfx_operator {
   const void* outputscale;
   const void* noise; /* GGN: the shift alpha (1) */
 
-  /* CALLBACK; GGN: ctx = const mfx_ggn_net* (host); PRECOND: ctx = const mfx_precond* (host) */
+  /* CALLBACK; GGN: ctx = const mfx_ggn_net* (host); PRECOND: ctx = const mfx_precond* (host); AFFINE: ctx = const mfx_affine* (host) */
   mfx_callback_fn callback;
   void* ctx;
 
@@ -247,7 +249,7 @@ typedef struct mfx_operator {
  * mode 0: y = S A S x;  transpose: y = S A^T S x.  mfx_op_grads means what it means for A (grads->x of a kernel-Gram inner
  * included); the sweep applies S to both factors 64 batch rows at a time, so its scratch is 2 * 64 * n elements.  A's per-call
  * preparation still runs once per driver call.
- * Refused before any launch: MFX_ERR_INVALID for a NULL ctx, a NULL, CALLBACK or PRECOND inner operator, an inner operator its own
+ * Refused before any launch: MFX_ERR_INVALID for a NULL ctx, a NULL, CALLBACK, PRECOND or AFFINE inner operator, an inner operator its own
  * kind refuses, a dtype or n that differs, an inner row block, pc_rank outside [1, n], a NULL pc_lt, pc_mid or pc_scale;
  * MFX_ERR_UNSUPPORTED for pc_rank > 4096, a row block (nrows > 0) and the row-sharded drivers (L would need its rows sharded and
  * L^T v all-reduced, as mfx_pcg_solve_sharded does).  The element access of mfx_partial_cholesky and the Gram-only entry points
@@ -260,6 +262,28 @@ typedef struct mfx_precond {
   int64_t pc_rank;
 } mfx_precond;
 
+/* Affine operator (MFX_OP_AFFINE; the reference's pde_heat_affine, util/pde_util.py:90-103, is the one field that needs it): the
+ * bordered matrix B = [[A, b], [0, 0]] of the affine vector field y' = A y + b with A = *af_inner, so that d/dt (y, 1) = B (y, 1):
+ * exp(t B) (y0, 1) = (e^{tA} y0 + t phi_1(tA) b, 1), and every explicit Runge-Kutta scheme on B is the same scheme on the affine
+ * field.  mfx_operator.ctx points at this HOST struct (borrowed, valid for the call), as for MFX_OP_PRECOND; the operator has
+ * n = af_inner->n + 1 unknowns.  With m = af_inner->n:
+ *   mode 0:     y[:m] = A x[:m] + x[m] b,   y[m] = 0            (x[m] is read on the device: no host synchronisation)
+ *   transpose:  y[:m] = A^T x[:m],          y[m] = b . x[:m]    (a two-stage sum in a fixed order, no atomics)
+ *   gradients:  those of A on the first m entries of every L_b and R_b (same leading dimensions, no copies), and
+ *               mfx_op_grads.drift[i] += sum_b R_b[m] L_b[i].
+ *   af_inner  HOST pointer to the descriptor of A (borrowed, valid for the call): any native kind except PRECOND and AFFINE, with
+ *             the dtype of the outer descriptor and nrows == 0;
+ *   af_b      the drift b, m values in the operator's dtype (device pointer).
+ * Workspace: A's own, then one double per probe and per 4096 entries of b for the partial sums of the transposed application.
+ * Refused before any launch: MFX_ERR_INVALID for a NULL ctx, af_b or af_inner, a CALLBACK, PRECOND or AFFINE inner operator, an inner
+ * operator its own kind refuses, a dtype that differs, n != af_inner->n + 1, an inner row block; MFX_ERR_UNSUPPORTED for a row block
+ * (nrows > 0), the row-sharded drivers (the border row and column belong to no shard), grads->x of a kernel-Gram inner operator and
+ * more than 65535 vectors in one application.  MFX_OP_PRECOND refuses an affine inner operator (MFX_ERR_INVALID). */
+typedef struct mfx_affine {
+  const mfx_operator* af_inner;
+  const void* af_b;
+} mfx_affine;
+
 /* Parameter-gradient outputs (device pointers, ACCUMULATED into, caller zero-fills).  NULL = skip.
  *   dense_a (n, n) row-major, leading dimension = n;  val (CSR: nnz stored values; STENCIL: the (st_ny, st_nx) coefficient field,
  *     val[i] += sigma sum_b L_b[blk + i] (S R_b.u)[i] with (sigma, blk) = (+1, 0) HEAT, (-1, 0) HEAT2, (+1, st_ny st_nx) WAVE);
@@ -270,15 +294,22 @@ typedef struct mfx_precond {
  *     Every entry point that takes grads honours it (mfx_op_vjp_params, mfx_arnoldi_adjoint, mfx_lanczos_adjoint; the PCG backward
  *     goes through mfx_op_vjp_params).  Refused before any launch: MFX_ERR_INVALID on any other operator kind, MFX_ERR_UNSUPPORTED
  *     on a row block (nrows > 0) and on the row-sharded drivers.  grads->x == NULL runs exactly the kernels of the other fields.
+ *   drift (n - 1 values): the gradient with respect to af_b of an MFX_OP_AFFINE operator, drift[i] += sum_b R_b[n - 1] L_b[i]; the
+ *     other fields then mean what they mean for its inner operator.  MFX_ERR_INVALID on every other kind.  It stands BEFORE x: the
+ *     layout contract of this struct is that x is its LAST field (tests/test_input_grad_host.py holds the header and the ctypes
+ *     mirror to it), so a new field cannot be appended after it.  The offset of x therefore moved by one pointer: callers that name
+ *     the fields must be rebuilt against this header (the library, its ctypes mirror and the C programs of tests/cabi live and
+ *     build in one tree; there is no other caller).  The offsets of the five fields before it are unchanged.
  * d/dtheta of  sum_b L_b^T A(theta) R_b   (arnoldi.py:207-209, lanczos.py:328-329).
- * The struct grew by `x` at the end without a version bump (MFX_VERSION stays 201): C callers must zero-fill it
- * (mfx_op_grads g = {0}; or memset) so that fields they do not know are NULL. */
+ * The struct grew by `x` at the end, and later by `drift` before it, without a version bump (MFX_VERSION stays 201): C callers must
+ * zero-fill it (mfx_op_grads g = {0}; or memset) so that fields they do not know are NULL. */
 typedef struct mfx_op_grads {
   void* dense_a;
   void* val;
   void* lengthscale;
   void* outputscale;
   void* noise;
+  void* drift;
   void* x;
 } mfx_op_grads;
 
