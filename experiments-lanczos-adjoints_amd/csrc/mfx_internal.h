@@ -65,7 +65,7 @@ struct GraphKey {
 // it is given and nothing else (no synchronisation, no allocation).
 int run_graphed(bool eligible, const GraphKey& key, hipStream_t stream, const std::function<int(hipStream_t)>& fn);
 // One id per driver that replays from a graph, across all files: a key starts with it, so no two drivers can share a graph.
-enum DriverId : int { kIdArnoldiForward = 1, kIdArnoldiAdjoint, kIdLanczosForward, kIdLanczosAdjoint, kIdRkSolve, kIdRkAdjoint, kIdRkBacksolve };
+enum DriverId : int { kIdArnoldiForward = 1, kIdArnoldiAdjoint, kIdLanczosForward, kIdLanczosAdjoint, kIdRkSolve, kIdRkAdjoint, kIdRkBacksolve, kIdRkAdaptive };
 // What every driver's key starts with: the id, *op and what its kind adds (OpKind::graph_key), the sizes (depth: Krylov depth or
 // number of steps), the workspace, the stream and the gradient request (NULL: none).  The driver appends its own pointers and flags.
 GraphKey driver_key(DriverId id, const mfx_operator* op, int64_t n, int64_t depth, int64_t p, const mfx_op_grads* grads,

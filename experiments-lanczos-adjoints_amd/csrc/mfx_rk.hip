@@ -10,6 +10,10 @@
 // body is not shared; the thread-owned loads and stores are.)  The operator is applied through op_apply only.  A stage kernel that
 // fuses the combination into the stencil apply was measured and is slower or within the noise: tools/experiments/rk_fused_stage,
 // DESIGN.md section 3.4b.  No atomics anywhere.
+//
+// mfx_rk_solve_adaptive runs the same scheme on an embedded pair with the step size on the device: a
+// control block in the workspace, k_rk_combine_dev (k_rk_combine with h read from the block), k_rk_err_partials, k_rk_control and
+// k_rk_commit; the host polls the block once per chunk of attempts.
 #include <math.h>
 
 #include "mfx_vec.h"
@@ -66,6 +70,208 @@ __global__ __launch_bounds__(kBlock) void k_rk_combine(RkCoef<T> k, const T* bas
 }
 
 // ------------------------------------------------------------------------------------------------
+// adaptive steps (mfx_rk_solve_adaptive): the step size lives on the device
+// ------------------------------------------------------------------------------------------------
+// The control block, at the start of the workspace.  h is the step of the attempt in flight (already clipped to t1 - t), h_abs the
+// controller's unclipped proposal; `commit` and `row` are what k_rk_control hands to k_rk_commit.
+struct RkCtl {
+  double t, t_new, h, h_abs, t1;
+  int64_t n_accepted, n_rejected, n_attempts, max_attempts, row;
+  int32_t done, status, rejected, commit;
+};
+
+// the tableau numbers of one combination; the kernel multiplies them by the block's h.  mask as RkCoef::mask (c0 = 1 when present)
+struct RkCoefDev {
+  unsigned mask;
+  double a[MFX_RK_MAX_STAGES];
+};
+
+// What every attempt starts with (scipy's _step_impl): refuse a proposal below 10 ulp(t), clip to t1, take h as the difference.
+__device__ __forceinline__ void rk_ctl_propose(RkCtl* c) {
+  const double t = c->t;
+  if (c->h_abs < 10.0 * (nextafter(t, INFINITY) - t)) {
+    c->status = MFX_RK_STEP_TOO_SMALL;
+    c->done = 1;
+    return;
+  }
+  double t_new = t + c->h_abs;
+  if (t_new > c->t1) t_new = c->t1;
+  c->t_new = t_new;
+  c->h = t_new - t;
+}
+
+__global__ void k_rk_ctl_init(RkCtl* c, double t0, double t1, double dt0, int64_t max_attempts) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  c->t = t0, c->t_new = t0, c->h = 0.0, c->h_abs = dt0, c->t1 = t1;
+  c->n_accepted = c->n_rejected = c->n_attempts = 0;
+  c->max_attempts = max_attempts;
+  c->row = 0;
+  c->done = 0, c->status = MFX_RK_OK, c->rejected = 0, c->commit = 0;
+  rk_ctl_propose(c);
+}
+
+// k_rk_combine with c_j = T(h a_j), the fp64 product rounded once as rk_coef rounds the host's: the same bits as k_rk_combine
+// launched with the step size the block holds.  Returns at once when the solve is over.
+template <typename T, int VEC, int EPT>
+__global__ __launch_bounds__(kBlock) void k_rk_combine_dev(const RkCtl* __restrict__ ctl, RkCoefDev k, const T* base, int64_t ldbase,
+                                                           const T* __restrict__ rows, int64_t rows_ldb, int64_t row_stride, T* out,
+                                                           int64_t ldout, int64_t n) {
+  if (ctl->done) return;
+  const double h = ctl->h;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.y;
+  const int64_t slice0 = (int64_t)blockIdx.x * ((int64_t)blockDim.x * EPT);
+  T acc[EPT];
+  if (k.mask >> kRkBaseBit & 1u) {
+    load_own<T, VEC>(acc, base + b * ldbase, slice0, n, tid);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) acc[e] = rk_scale<T>(T(1), acc[e]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) acc[e] = T(0);
+  }
+  const T* rb = rows + b * rows_ldb;
+#pragma unroll
+  for (int j = 0; j < MFX_RK_MAX_STAGES; ++j) {
+    const double cj = h * k.a[j];
+    if ((k.mask >> j & 1u) && cj != 0.0) {
+      T v[EPT];
+      load_own<T, VEC>(v, rb + (int64_t)j * row_stride, slice0, n, tid);
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) acc[e] = rk_axpy<T>((T)cj, v[e], acc[e]);
+    }
+  }
+  store_own<T, VEC>(acc, out + b * ldout, slice0, n, tid);
+}
+
+// partial[b][blk] = sum over the block's elements of (err_i / scale_i)^2 in fp64, err = h sum_j e_j K_j over the rows with e_j != 0,
+// scale_i = atol + rtol max(|y_i|, |y+_i|): one pass over y, y+ and those rows.  Fixed order inside the block, no atomics.
+template <typename T, int VEC, int EPT>
+__global__ __launch_bounds__(kBlock) void k_rk_err_partials(const RkCtl* __restrict__ ctl, RkCoefDev k, const T* __restrict__ y,
+                                                            const T* __restrict__ ynew, int64_t ldy, const T* __restrict__ rows,
+                                                            int64_t rows_ldb, int64_t row_stride, double rtol, double atol, int64_t n,
+                                                            double* __restrict__ partial, int nblk) {
+  __shared__ double sm[kBlock / 64];
+  if (ctl->done) return;
+  const double h = ctl->h;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t b = blockIdx.y;
+  const int64_t slice0 = (int64_t)blockIdx.x * ((int64_t)blockDim.x * EPT);
+  double err[EPT];
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) err[e] = 0.0;
+  const T* rb = rows + b * rows_ldb;
+#pragma unroll
+  for (int j = 0; j < MFX_RK_MAX_STAGES; ++j) {
+    if (k.mask >> j & 1u) {
+      const double cj = h * k.a[j];
+      T v[EPT];
+      load_own<T, VEC>(v, rb + (int64_t)j * row_stride, slice0, n, tid);
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) err[e] = fma(cj, (double)v[e], err[e]);
+    }
+  }
+  T ya[EPT], yb[EPT];
+  load_own<T, VEC>(ya, y + b * ldy, slice0, n, tid);
+  load_own<T, VEC>(yb, ynew + b * ldy, slice0, n, tid);
+  double sum = 0.0;
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) {
+    const int64_t off = slice0 + (int64_t)((e / VEC) * (int)blockDim.x + tid) * VEC + (e % VEC);
+    if (off < n) {  // an element past the end has no scale (atol may be 0)
+      const double r = err[e] / (atol + rtol * fmax(fabs((double)ya[e]), fabs((double)yb[e])));
+      sum = fma(r, r, sum);
+    }
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) sm[wid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += sm[w];
+    partial[b * (int64_t)nblk + blockIdx.x] = tot;
+  }
+}
+
+// One workgroup: the per-state sums of the partials in a fixed order (a wave per state, lanes strided over the blocks), their
+// maximum, then thread 0 applies the controller to the block and appends the step size of an accepted attempt to dts.
+__global__ __launch_bounds__(kBlock) void k_rk_control(RkCtl* ctl, const double* __restrict__ partial, int nblk, int64_t p, int64_t n,
+                                                       double expo, double* __restrict__ dts, int64_t max_steps) {
+  __shared__ double smax[kBlock / 64];
+  __shared__ int sbad[kBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (ctl->done) {  // nothing reads `commit` before this kernel of the next attempt
+    if (tid == 0) ctl->commit = 0;
+    return;
+  }
+  double vmax = 0.0;
+  int bad = 0;
+  for (int64_t b = wid; b < p; b += kBlock / 64) {
+    double s = 0.0;
+    for (int q = lane; q < nblk; q += 64) s += partial[b * (int64_t)nblk + q];
+    s = wave_sum_all(s);
+    if (!isfinite(s)) bad = 1;
+    else if (s > vmax) vmax = s;
+  }
+  if (lane == 0) smax[wid] = vmax, sbad[wid] = bad;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 0; w < kBlock / 64; ++w) {
+    bad |= sbad[w];
+    if (smax[w] > vmax) vmax = smax[w];
+  }
+  RkCtl c = *ctl;
+  c.n_attempts += 1;
+  c.commit = 0;
+  if (bad) {
+    c.status = MFX_RK_NONFINITE;
+    c.done = 1;
+    *ctl = c;
+    return;
+  }
+  const double norm = sqrt(vmax / (double)n);
+  if (norm < 1.0) {
+    double factor = norm == 0.0 ? 10.0 : fmin(10.0, 0.9 * pow(norm, expo));
+    if (c.rejected) factor = fmin(1.0, factor);
+    dts[c.n_accepted] = c.h;
+    c.n_accepted += 1;
+    c.row = c.n_accepted;
+    c.commit = 1;
+    c.rejected = 0;
+    c.t = c.t_new;
+    c.h_abs = c.h * factor;
+    if (c.t >= c.t1) c.done = 1;  // status stays MFX_RK_OK
+  } else {
+    c.h_abs = c.h * fmax(0.2, 0.9 * pow(norm, expo));
+    c.rejected = 1;
+    c.n_rejected += 1;
+  }
+  if (!c.done) {
+    if (c.n_attempts >= c.max_attempts || c.n_accepted >= max_steps) {
+      c.status = MFX_RK_MAX_ATTEMPTS;
+      c.done = 1;
+    } else {
+      rk_ctl_propose(&c);
+    }
+  }
+  *ctl = c;
+}
+
+// an accepted attempt: y <- y+, and row `row` of the kept iterates
+template <typename T, int VEC, int EPT>
+__global__ __launch_bounds__(kBlock) void k_rk_commit(const RkCtl* __restrict__ ctl, const T* __restrict__ ynew, T* __restrict__ y,
+                                                      int64_t ldy, T* __restrict__ ys, int64_t ldys, int64_t n) {
+  if (!ctl->commit) return;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.y;
+  const int64_t slice0 = (int64_t)blockIdx.x * ((int64_t)blockDim.x * EPT);
+  T v[EPT];
+  load_own<T, VEC>(v, ynew + b * ldy, slice0, n, tid);
+  store_own<T, VEC>(v, y + b * ldy, slice0, n, tid);
+  if (ys) store_own<T, VEC>(v, ys + b * ldys + ctl->row * n, slice0, n, tid);
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 struct RkGeom {  // what MFX_VEC_EPT_SWITCH reads
@@ -95,23 +301,33 @@ static RkCoef<T> rk_coef(double c0, bool has_base, const double* coef, int nrows
   return k;
 }
 
+// launch geometry of a pass over (p, n) vectors and panel rows: 16-byte access when every pointer, leading dimension and the row
+// stride allow it; Ctx::fine slicing when the coarse one leaves most CUs idle
+template <typename T>
+static RkGeom rk_geom(int64_t n, int64_t p, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds, int64_t row_stride) {
+  constexpr int V = VecWidth<T>::value;
+  RkGeom g;
+  g.vec = pick_vec<T>(n, ptrs);
+  if (p > 1)
+    for (int64_t ld : lds)
+      if (ld % V) g.vec = 1;
+  if (row_stride % V) g.vec = 1;
+  g.wg = pick_wg(n, p);
+  g.ept = kEpt;
+  g.nblk = (int)((n + (int64_t)g.wg * kEpt - 1) / ((int64_t)g.wg * kEpt));
+  if (g.vec > 1 && g.wg == kBlock && (int64_t)g.nblk * p < 128) {  // Ctx::fine: one 16-byte load per thread and row
+    g.ept = V;
+    g.nblk = (int)((n + (int64_t)g.wg * V - 1) / ((int64_t)g.wg * V));
+  }
+  return g;
+}
+
 // out = c0 base + sum_{j < nrows} coef[j] rows[:, j, :]   (base NULL: no base term; nrows 0: no rows)
 template <typename T>
 static int rk_combine(const RkCtx<T>& c, double c0, const T* base, int64_t ldbase, const double* coef, int nrows, const T* rows,
                       int64_t rows_ldb, int64_t row_stride, T* out, int64_t ldout) {
   const RkCoef<T> k = rk_coef<T>(c0, base != nullptr, coef, nrows);
-  constexpr int V = VecWidth<T>::value;
-  RkGeom g;
-  g.vec = pick_vec<T>(c.n, {base, rows, out});
-  if (c.p > 1 && (ldbase % V || rows_ldb % V || ldout % V)) g.vec = 1;
-  if (row_stride % V) g.vec = 1;
-  g.wg = pick_wg(c.n, c.p);
-  g.ept = kEpt;
-  g.nblk = (int)((c.n + (int64_t)g.wg * kEpt - 1) / ((int64_t)g.wg * kEpt));
-  if (g.vec > 1 && g.wg == kBlock && (int64_t)g.nblk * c.p < 128) {  // Ctx::fine: one 16-byte load per thread and row
-    g.ept = V;
-    g.nblk = (int)((c.n + (int64_t)g.wg * V - 1) / ((int64_t)g.wg * V));
-  }
+  const RkGeom g = rk_geom<T>(c.n, c.p, {base, rows, out}, {ldbase, rows_ldb, ldout}, row_stride);
   const dim3 grid((unsigned)g.nblk, (unsigned)c.p);
   if (!base) base = out;  // never read (the base bit is clear)
   if (!rows) rows = out;  // never read (no row bit is set)
@@ -342,6 +558,116 @@ static RkCtx<T> rk_ctx(const mfx_operator* op, const mfx_rk_tableau* tab, int64_
   return c;
 }
 
+// ---- adaptive steps ------------------------------------------------------------------------------------------------------------------
+struct RkAdaptiveWs {
+  RkCtl* ctl;
+  double *dts, *partial;
+  void *y, *ynew, *ytmp, *K, *opws;
+  int64_t opws_bytes;
+};
+
+// an upper bound of rk_geom's nblk: 512 elements per workgroup is the finest slicing it picks
+static int64_t rk_partial_slots(int64_t n) { return (n + 511) / 512; }
+
+static int64_t rk_adaptive_carve(const mfx_operator* op, int s, int64_t n, int64_t p, int64_t max_steps, void* ws, int64_t ws_bytes,
+                                 RkAdaptiveWs* out) {
+  const int64_t es = (int64_t)dtype_size(op->dtype), vec = p * n * es;
+  Carver cv(ws, ws_bytes);
+  RkAdaptiveWs w{};
+  w.ctl = static_cast<RkCtl*>(cv.take((int64_t)sizeof(RkCtl)));
+  w.dts = static_cast<double*>(cv.take(max_steps * (int64_t)sizeof(double)));
+  w.partial = static_cast<double*>(cv.take(p * rk_partial_slots(n) * (int64_t)sizeof(double)));
+  w.y = cv.take(vec);
+  w.ynew = cv.take(vec);
+  w.ytmp = cv.take(vec);
+  w.K = cv.take(vec * s);
+  w.opws_bytes = op_workspace_bytes(op, 1, p);
+  w.opws = cv.take(w.opws_bytes);
+  if (out) *out = w;
+  return cv.off;
+}
+
+static RkCoefDev rk_coef_dev(bool has_base, const double* coef, int nrows) {
+  RkCoefDev k{};
+  if (has_base) k.mask |= 1u << kRkBaseBit;
+  for (int j = 0; j < nrows; ++j) {
+    k.a[j] = coef[j];
+    if (coef[j] != 0.0) k.mask |= 1u << j;
+  }
+  return k;
+}
+
+// out = base + h sum_{j < nrows} coef[j] K[:, j, :] with the block's h; every vector is a (p, n) workspace buffer
+template <typename T>
+static int rk_combine_dev(const RkCtx<T>& c, const RkCtl* ctl, const double* coef, int nrows, const T* base, const T* K, T* out) {
+  const int64_t ldk = (int64_t)c.s * c.n;
+  const RkCoefDev k = rk_coef_dev(true, coef, nrows);
+  const RkGeom g = rk_geom<T>(c.n, c.p, {base, K, out}, {c.n, ldk, c.n}, c.n);
+  const dim3 grid((unsigned)g.nblk, (unsigned)c.p);
+  MFX_VEC_EPT_SWITCH(g, (k_rk_combine_dev<T, VEC, EPT><<<grid, g.wg, 0, c.stream>>>(ctl, k, base, c.n, K, ldk, c.n, out, c.n, c.n)));
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+// ONE attempt: the stages and the update of rk_solve_t's step with the block's h, the error partials, the controller, the commit
+template <typename T>
+static int rk_attempt(const RkCtx<T>& c, const mfx_rk_pair* pair, double rtol, double atol, int64_t max_steps, T* ys, const RkAdaptiveWs& w) {
+  const int64_t n = c.n, ldk = (int64_t)c.s * n;
+  T *y = (T*)w.y, *ynew = (T*)w.ynew, *ytmp = (T*)w.ytmp, *K = (T*)w.K;
+  for (int i = 0; i < c.s; ++i) {
+    bool any = false;
+    for (int j = 0; j < i; ++j) any = any || c.tab->a[i][j] != 0.0;
+    const T* x = y;
+    if (any) {  // as rk_stage: Y_i = y needs no combination
+      MFX_TRY(rk_combine_dev<T>(c, w.ctl, c.tab->a[i], i, y, K, ytmp));
+      x = ytmp;
+    }
+    MFX_TRY(op_apply(c.op, 0, x, n, nullptr, 0, K + (int64_t)i * n, ldk, c.p, c.opws, c.opws_bytes, c.stream));
+  }
+  MFX_TRY(rk_combine_dev<T>(c, w.ctl, c.tab->b, c.s, y, K, ynew));
+  const RkCoefDev ke = rk_coef_dev(false, pair->e, c.s);
+  const RkGeom g = rk_geom<T>(n, c.p, {y, ynew, K}, {n, ldk}, n);
+  MFX_REQUIRE(g.nblk <= rk_partial_slots(n), MFX_ERR_INVALID, "mfx_rk_solve_adaptive: %d slices exceed the partial sums' %lld slots", g.nblk,
+              (long long)rk_partial_slots(n));
+  const dim3 grid((unsigned)g.nblk, (unsigned)c.p);
+  MFX_VEC_EPT_SWITCH(g, (k_rk_err_partials<T, VEC, EPT><<<grid, g.wg, 0, c.stream>>>(w.ctl, ke, y, ynew, n, K, ldk, n, rtol, atol, n, w.partial,
+                                                                                   g.nblk)));
+  MFX_CHECK_LAUNCH();
+  k_rk_control<<<1, kBlock, 0, c.stream>>>(w.ctl, w.partial, g.nblk, c.p, n, -1.0 / (double)pair->order, w.dts, max_steps);
+  MFX_CHECK_LAUNCH();
+  const int64_t ldys = (max_steps + 1) * n;
+  const RkGeom gc = rk_geom<T>(n, c.p, {y, ynew, ys}, {n, ldys}, n);
+  MFX_VEC_EPT_SWITCH(gc, (k_rk_commit<T, VEC, EPT><<<dim3((unsigned)gc.nblk, (unsigned)c.p), gc.wg, 0, c.stream>>>(w.ctl, ynew, y, n, ys, ldys, n)));
+  MFX_CHECK_LAUNCH();
+  return MFX_OK;
+}
+
+static const char* rk_status_text(int status) {
+  switch (status) {
+    case MFX_RK_OK: return "ok";
+    case MFX_RK_MAX_ATTEMPTS: return "max_attempts exhausted before t1";
+    case MFX_RK_STEP_TOO_SMALL: return "step size below 10 ulp(t)";
+    case MFX_RK_NONFINITE: return "non-finite error norm";
+  }
+  return "unknown status";
+}
+
+static int rk_check_adaptive(const mfx_operator* op, const mfx_rk_pair* pair, double t0, double t1, double dt0, double rtol, double atol,
+                             int64_t max_steps, int64_t max_attempts, int64_t chunk, int64_t n, int64_t p, int flags) {
+  MFX_REQUIRE(pair != nullptr, MFX_ERR_INVALID, "Runge-Kutta pair is NULL");
+  MFX_TRY(rk_check(op, &pair->tab, &dt0, 1, n, p, nullptr, flags));
+  for (int i = 0; i < pair->tab.stages; ++i) MFX_REQUIRE(std::isfinite(pair->e[i]), MFX_ERR_INVALID, "Runge-Kutta pair: e[%d] is not finite", i);
+  MFX_REQUIRE(pair->order >= 1, MFX_ERR_INVALID, "Runge-Kutta pair: order = %d must be at least 1", pair->order);
+  MFX_REQUIRE(rtol >= 0.0 && atol >= 0.0 && std::isfinite(rtol + atol) && rtol + atol > 0.0, MFX_ERR_INVALID,
+              "rtol = %g, atol = %g: both must be non-negative and their sum finite and positive", rtol, atol);
+  MFX_REQUIRE(dt0 > 0.0, MFX_ERR_INVALID, "dt0 = %g must be positive", dt0);
+  MFX_REQUIRE(std::isfinite(t0) && std::isfinite(t1) && t1 > t0, MFX_ERR_INVALID, "t1 = %g must be finite and greater than t0 = %g", t1, t0);
+  MFX_REQUIRE(max_steps >= 1, MFX_ERR_INVALID, "max_steps = %lld must be at least 1", (long long)max_steps);
+  MFX_REQUIRE(max_attempts >= 1, MFX_ERR_INVALID, "max_attempts = %lld must be at least 1", (long long)max_attempts);
+  MFX_REQUIRE(chunk >= 1, MFX_ERR_INVALID, "chunk = %lld must be at least 1", (long long)chunk);
+  return MFX_OK;
+}
+
 }  // namespace mfx
 
 using namespace mfx;
@@ -413,6 +739,74 @@ int mfx_rk_backsolve(const mfx_operator* op, const mfx_rk_tableau* tab, const do
                                grads, call.ws);
     });
   });
+}
+
+int64_t mfx_rk_adaptive_workspace_bytes(const mfx_operator* op, const mfx_rk_pair* pair, int64_t n, int64_t p, int64_t max_steps) {
+  if (!op || !pair || pair->tab.stages < 1 || pair->tab.stages > MFX_RK_MAX_STAGES || n < 1 || p < 1 || max_steps < 1) return -1;
+  if (check_op(op) != MFX_OK || op->n != n) return -1;
+  return rk_adaptive_carve(op, pair->tab.stages, n, p, max_steps, nullptr, 0, nullptr);
+}
+
+int mfx_rk_solve_adaptive(const mfx_operator* op, const mfx_rk_pair* pair, double t0, double t1, double dt0, double rtol, double atol,
+                          int64_t max_steps, int64_t max_attempts, int64_t chunk, const void* y0, int64_t ldy0, int64_t n, int64_t p,
+                          void* y1, int64_t ldy1, void* ys, double* dts, mfx_rk_adaptive_info* info, int flags, void* ws,
+                          int64_t ws_bytes, void* stream) {
+  MFX_TRY(rk_check_adaptive(op, pair, t0, t1, dt0, rtol, atol, max_steps, max_attempts, chunk, n, p, flags));
+  MFX_REQUIRE(y0 && y1 && info, MFX_ERR_INVALID, "null argument");
+  MFX_REQUIRE(ldy0 >= n && ldy1 >= n, MFX_ERR_INVALID, "leading dimensions %lld, %lld are shorter than n = %lld", (long long)ldy0,
+              (long long)ldy1, (long long)n);
+  const mfx_rk_tableau* tab = &pair->tab;
+  RkAdaptiveWs w;
+  const int64_t need = rk_adaptive_carve(op, tab->stages, n, p, max_steps, ws, ws_bytes, &w);
+  MFX_REQUIRE(ws && need <= ws_bytes, MFX_ERR_WORKSPACE, "mfx_rk_solve_adaptive: workspace too small: %lld bytes given, %lld needed",
+              (long long)ws_bytes, (long long)need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (chunk > max_attempts) chunk = max_attempts;
+  PrepScope prep_scope;
+  // what a chunk's launches depend on: nothing of t0, t1, dt0, max_attempts (those are in the control block)
+  GraphKey key = driver_key(kIdRkAdaptive, op, n, max_steps, p, nullptr, ws, ws_bytes, stream);
+  key.add(flags).add(tab->stages).add(pair->order).add(rtol).add(atol).add(chunk).add(ys);
+  for (int i = 0; i < tab->stages; ++i) {
+    key.add(tab->b[i]).add(pair->e[i]);
+    for (int j = 0; j < i; ++j) key.add(tab->a[i][j]);
+  }
+  RkWs shared{};
+  shared.opws = w.opws, shared.opws_bytes = w.opws_bytes;
+  RkCtl host{};
+  const int rc = with_dtype(op->dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    const size_t row = (size_t)n * sizeof(T);
+    k_rk_ctl_init<<<1, 1, 0, st>>>(w.ctl, t0, t1, dt0, max_attempts);
+    MFX_CHECK_LAUNCH();
+    MFX_TRY(copy_rows_async(w.y, row, y0, (size_t)ldy0 * sizeof(T), row, p, st));
+    if (ys) MFX_TRY(copy_rows_async(ys, (size_t)(max_steps + 1) * row, y0, (size_t)ldy0 * sizeof(T), row, p, st));
+    const int64_t max_chunks = (max_attempts + chunk - 1) / chunk;
+    for (int64_t q = 0; q < max_chunks; ++q) {
+      MFX_TRY(run_graphed(op_kind(op)->native, key, st, [&](hipStream_t s) -> int {
+        const RkCtx<T> c = rk_ctx<T>(op, tab, n, p, shared, s);
+        for (int64_t a = 0; a < chunk; ++a) MFX_TRY(rk_attempt<T>(c, pair, rtol, atol, max_steps, as<T>(ys), w));
+        return MFX_OK;
+      }));
+      MFX_CHECK_HIP(hipMemcpyAsync(&host, w.ctl, sizeof(RkCtl), hipMemcpyDeviceToHost, st));
+      MFX_CHECK_HIP(hipStreamSynchronize(st));
+      if (host.done) break;
+    }
+    MFX_REQUIRE(host.done, MFX_ERR_HIP, "mfx_rk_solve_adaptive: the controller did not finish within max_attempts = %lld attempts",
+                (long long)max_attempts);
+    MFX_TRY(copy_rows_async(y1, (size_t)ldy1 * sizeof(T), w.y, row, row, p, st));
+    if (dts && host.n_accepted > 0)
+      MFX_CHECK_HIP(hipMemcpyAsync(dts, w.dts, (size_t)host.n_accepted * sizeof(double), hipMemcpyDeviceToHost, st));
+    MFX_CHECK_HIP(hipStreamSynchronize(st));
+    return MFX_OK;
+  });
+  MFX_TRY(rc);
+  info->status = host.status;
+  info->n_accepted = host.n_accepted, info->n_rejected = host.n_rejected, info->n_attempts = host.n_attempts;
+  info->t_reached = host.t;
+  if (host.status != MFX_RK_OK)
+    set_error("mfx_rk_solve_adaptive: %s (t = %.17g of [%.17g, %.17g], %lld accepted, %lld rejected)", rk_status_text(host.status), host.t,
+              t0, t1, (long long)host.n_accepted, (long long)host.n_rejected);
+  return MFX_OK;
 }
 
 }  // extern "C"

@@ -166,10 +166,26 @@ class RkTableau(C.Structure):
     ]
 
 
+class RkPair(C.Structure):
+    """mirror of ``struct mfx_rk_pair``: an embedded pair (``e = b - bhat``, ``order`` the controller's exponent)."""
+
+    _fields_ = [("tab", RkTableau), ("e", C.c_double * RK_MAX_STAGES), ("order", C.c_int32)]
+
+
+class RkAdaptiveInfo(C.Structure):
+    """mirror of ``struct mfx_rk_adaptive_info`` (a HOST struct the adaptive solve fills)."""
+
+    _fields_ = [("status", C.c_int32), ("n_accepted", C.c_int64), ("n_rejected", C.c_int64), ("n_attempts", C.c_int64),
+                ("t_reached", C.c_double)]
+
+
+RK_OK, RK_MAX_ATTEMPTS, RK_STEP_TOO_SMALL, RK_NONFINITE = 0, 1, 2, 3
+
 # every symbol include/mfx.h declares: (name, restype, argtypes)
 _P, _I64, _I = C.c_void_p, C.c_int64, C.c_int
 _OPP, _GRP, _CMP, _NETP = C.POINTER(Operator), C.POINTER(OpGrads), C.POINTER(Comm), C.POINTER(GgnNet)
 _RKP, _DP = C.POINTER(RkTableau), C.POINTER(C.c_double)
+_RKPP, _RKIP, _D = C.POINTER(RkPair), C.POINTER(RkAdaptiveInfo), C.c_double
 SYMBOLS = {
     "mfx_last_error": (C.c_char_p, []),
     "mfx_version": (_I, []),
@@ -253,6 +269,9 @@ SYMBOLS = {
     "mfx_rk_solve": (_I, [_OPP, _RKP, _DP, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _I, _P, _I64, _P]),
     "mfx_rk_adjoint": (_I, [_OPP, _RKP, _DP, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _GRP, _I, _P, _I64, _P]),
     "mfx_rk_backsolve": (_I, [_OPP, _RKP, _DP, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _GRP, _I, _P, _I64, _P]),
+    "mfx_rk_adaptive_workspace_bytes": (_I64, [_OPP, _RKPP, _I64, _I64, _I64]),
+    "mfx_rk_solve_adaptive": (_I, [_OPP, _RKPP, _D, _D, _D, _D, _D, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _DP, _RKIP, _I, _P,
+                                   _I64, _P]),
     "mfx_timing_enable": (_I, [_I]),
     "mfx_timing_reset": (_I, []),
     "mfx_timing_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

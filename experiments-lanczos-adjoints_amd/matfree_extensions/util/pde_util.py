@@ -15,7 +15,9 @@ the whole solve, its discrete adjoint and the continuous ("backsolve") adjoint a
 ``mfx_rk_adjoint`` / ``mfx_rk_backsolve``, csrc/mfx_rk.hip) on LINEAR autonomous fields y' = A y, A a native, bound or callback
 operator.  AFFINE fields y' = A y + b go through ``operators.AffineOp``, the bordered linear operator on (y, 1): ``rhs.flat`` of
 ``pde_heat_affine`` is one, and ``solver_expm`` / ``solver_rk`` / ``solver_euler`` lift the state, solve and drop the last entry.
-Out of scope: adaptive step sizes, nonlinear fields, gradients with respect to the times, row-sharded operators.
+ADAPTIVE steps are ``solver_rk_adaptive``: an embedded pair under scipy's step-size controller, the step size held on the device
+(``mfx_rk_solve_adaptive``), gradients by the fixed-step adjoints on the accepted steps.
+Out of scope: nonlinear fields, gradients with respect to the times, row-sharded operators.
 """
 
 from __future__ import annotations
@@ -272,6 +274,135 @@ def solver_rk(t0, t1, vector_field, /, *, num_steps, method, adjoint="discrete")
 
 
 solver_diffrax = solver_rk
+
+
+RK_STATUS = {_lib.RK_OK: "ok", _lib.RK_MAX_ATTEMPTS: "max_attempts", _lib.RK_STEP_TOO_SMALL: "step_too_small", _lib.RK_NONFINITE: "nonfinite"}
+RK_ADAPTIVE_CHUNK = 8  # attempts the driver enqueues between two reads of its control block
+
+
+def _rk_adaptive_forward(op, cparams, pair, cfg, Y0, keep_ys):
+    """One mfx_rk_solve_adaptive call on detached tensors -> (y1 (p, n), ys (p, n_accepted + 1, n) or None, dts, info struct)."""
+    lib = _lib.get()
+    Y0 = Y0.contiguous()
+    p, n = Y0.shape
+    dt, dev = Y0.dtype, Y0.device
+    max_steps = int(cfg["max_steps"])
+    call = DriverCall(op, cparams, dt, n)
+    pstruct = rk_tableaux.pair_struct(pair)
+    y1 = torch.empty_like(Y0)
+    ys = torch.empty((p, max_steps + 1, n), dtype=dt, device=dev) if keep_ys else None
+    dts = (C.c_double * max_steps)()
+    info = _lib.RkAdaptiveInfo()
+    ws = call.take(lambda desc: lib.mfx_rk_adaptive_workspace_bytes(desc, C.byref(pstruct), n, p, max_steps), device=dev, visible=(Y0, y1, ys))
+    call.run(lib.mfx_rk_solve_adaptive, C.byref(pstruct), cfg["t0"], cfg["t1"], cfg["dt0"], cfg["rtol"], cfg["atol"], max_steps, max_steps,
+             int(cfg.get("chunk", RK_ADAPTIVE_CHUNK)), _lib.ptr(Y0), n, n, p, _lib.ptr(y1), n, _lib.ptr(ys), dts, C.byref(info), 0,
+             _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    if info.status != _lib.RK_OK:
+        raise RuntimeError(f"{RK_STATUS.get(info.status, info.status)}: {lib.mfx_last_error().decode()}")
+    steps = int(info.n_accepted)
+    if ys is not None:
+        ys = ys[:, : steps + 1].contiguous()  # what mfx_rk_solve would have kept for these steps
+    return y1, ys, tuple(dts[:steps]), info
+
+
+def _adaptive_fn(base):
+    """``base`` (_RkFn or _RkBacksolveFn) with the forward replaced by the adaptive solve: the backward is ``base``'s, on the accepted
+    steps as constants.  ``cfg`` (a dict) carries the controller's settings in and ``dts`` / the counters out."""
+
+    class _Fn(base):
+        @staticmethod
+        def forward(ctx, op, pair, cfg, Y0, *cparams):
+            tensors = stash_params(ctx, cparams)
+            _lib.require_device(Y0, *tensors)
+            keep = base is _RkFn and any(ctx.needs_input_grad)
+            y1, ys, dts, info = _rk_adaptive_forward(op, cparams, pair, cfg, Y0, keep)
+            cfg["dts"], cfg["num_rejected"] = dts, int(info.n_rejected)
+            ctx.op, ctx.tab, ctx.dts = op, pair.tab, dts
+            ctx.save_for_backward(ys if base is _RkFn else y1, *tensors)
+            return y1
+
+    return _Fn
+
+
+_RkAdaptiveFn, _RkAdaptiveBacksolveFn = _adaptive_fn(_RkFn), _adaptive_fn(_RkBacksolveFn)
+
+
+def _initial_step(apply, Y0, t0, t1, order, rtol, atol):
+    """scipy's select_initial_step (Hairer, Norsett & Wanner, Solving ODEs I, II.4) per state, the smallest over the batch: two
+    operator applications in torch, fp64 norms."""
+    def rms(x):
+        return torch.sqrt(torch.mean(x.double() ** 2, dim=-1))
+
+    interval = t1 - t0
+    scale = atol + Y0.abs().double() * rtol
+    f0 = apply(Y0)
+    d0, d1 = rms(Y0.double() / scale), rms(f0.double() / scale)
+    h0 = torch.where((d0 < 1e-5) | (d1 < 1e-5), torch.full_like(d0, 1e-6), 0.01 * d0 / d1).clamp(max=interval)
+    f1 = apply((Y0.double() + h0[:, None] * f0.double()).to(Y0.dtype))
+    d2 = rms((f1.double() - f0.double()) / scale) / h0
+    dmax = torch.maximum(d1, d2)
+    h1 = torch.where(dmax <= 1e-15, torch.clamp(h0 * 1e-3, min=1e-6), (0.01 / dmax.clamp(min=1e-300)) ** (1.0 / order))
+    return float(torch.minimum(100 * h0, h1).clamp(max=interval).min())
+
+
+def solver_rk_adaptive(t0, t1, vector_field, /, *, method="dopri5", rtol, atol, dt0=None, max_steps=4096, adjoint="discrete"):
+    """Adaptive-step explicit Runge-Kutta solve of y' = A y from t0 to t1 on the embedded pair ``method`` (``rk_tableaux.get_pair``:
+    dopri5, bosh3, heun) with the step-size controller of scipy's ``solve_ivp``: one ``mfx_rk_solve_adaptive`` call, the step size held
+    and updated on the device.  A batch shares ONE step sequence (the largest error norm over the states decides).  ``dt0``: the first
+    proposal; None takes scipy's ``select_initial_step`` (two operator applications).  ``max_steps`` bounds the ATTEMPTS, rejected ones
+    included, and the iterates kept for the discrete adjoint ((max_steps + 1) states while the solve runs, n_accepted + 1 afterwards).
+    Operators, batches and the AffineOp lift are ``solver_rk``'s; for an AffineOp the error norm runs over the lifted state (y, 1).
+
+    ``solve(y0, *p)`` -> ``(y1, info)``, info: ``num_steps`` (accepted), ``num_rejected``, ``num_applies`` (attempts x stages),
+    ``num_matvecs`` (num_steps x order, the reference's proxy), ``dts`` (the accepted step sizes) and ``status``.  Any end other than
+    reaching t1 raises ``RuntimeError`` that starts with the status: max_attempts, step_too_small, nonfinite.
+
+    Gradients are those of the FIXED-step solve on the accepted steps: ``mfx_rk_adjoint`` on the kept iterates (adjoint="discrete") or
+    ``mfx_rk_backsolve`` from y1 (adjoint="backsolve"), each with the recorded ``dts``.  The controller is NOT differentiated: the
+    dependence of the step sizes on y0 and on the parameters is ignored, as in the usual discretise-then-differentiate adjoints."""
+    if adjoint not in _RK_ADJOINTS:
+        raise ValueError(f"adjoint must be one of {sorted(_RK_ADJOINTS)}, got {adjoint!r}")
+    pair = rk_tableaux.get_pair(method)
+    t0, t1, rtol, atol, max_steps = float(t0), float(t1), float(rtol), float(atol), int(max_steps)
+    if not t1 > t0:
+        raise ValueError(f"t1 = {t1} must be greater than t0 = {t0}")
+    if max_steps < 1:
+        raise ValueError("max_steps must be at least 1")
+    if not isinstance(vector_field, (NativeOp, BoundOp, CallbackOp, RowShardedOp)):
+        raise TypeError("solver_rk_adaptive integrates LINEAR autonomous fields y' = A y: vector_field must be a linear operator -- a native "
+                        "operator, op.bind(*params) (rhs.flat of the stencil vector fields) or operators.CallbackOp(fn) -- not a "
+                        f"plain callable ({type(vector_field).__name__})")
+    op, bound = as_operator(vector_field)
+    if isinstance(op, RowShardedOp):
+        raise NotImplementedError("solver_rk_adaptive does not take row-sharded operators (the stage kernels have no halo exchange or "
+                                  "all-gather, the error norm no all-reduce)")
+    if isinstance(op, RbfGramOp) and op.X.requires_grad:
+        raise NotImplementedError("solver_rk_adaptive does not return the gradient with respect to the kernel inputs X; pass X.detach()")
+    fn = _RkAdaptiveFn if _RK_ADJOINTS[adjoint] == "discrete" else _RkAdaptiveBacksolveFn
+
+    def solve(y0, *p, chunk=RK_ADAPTIVE_CHUNK):
+        params = (tuple(bound) if bound is not None else ()) + tuple(p)
+        cparams = op.constrain(*params)
+        n = op.size(*cparams) if isinstance(op, NativeOp) else y0.numel()
+        affine = isinstance(op, AffineOp)
+        Y0 = _states_of(y0, n - 1 if affine else n).reshape(-1, n - 1 if affine else n)
+        if affine:
+            Y0 = AffineOp.lift(Y0)
+        cfg = {"t0": t0, "t1": t1, "rtol": rtol, "atol": atol, "max_steps": max_steps, "chunk": chunk}
+        if dt0 is None:
+            with torch.no_grad():
+                cfg["dt0"] = _initial_step(lambda Y: op(Y, *params), Y0.detach(), t0, t1, pair.order, rtol, atol)
+        else:
+            cfg["dt0"] = float(dt0)
+        y1 = fn.apply(op, pair, cfg, Y0, *cparams)
+        if affine:
+            y1 = AffineOp.drop(y1)
+        steps, rejected = len(cfg["dts"]), cfg["num_rejected"]
+        info = {"num_steps": steps, "num_rejected": rejected, "num_applies": (steps + rejected) * len(pair.tab.b),
+                "num_matvecs": steps * pair.order, "dts": cfg["dts"], "status": "ok"}
+        return y1.reshape(y0.shape), info
+
+    return solve
 
 
 def solver_euler(ts, vector_field, /):

@@ -1,7 +1,12 @@
 """Butcher tableaux of the fixed-step explicit Runge-Kutta baselines of the PDE work-precision study (``pde_util.solver_rk``).
 
 ``get(name)`` -> ``Tableau(name, order, a, b)`` with ``a`` strictly lower triangular (row i holds the i coefficients a_i0 .. a_i,i-1)
-and ``b`` the weights of the propagated solution.  Only what a fixed-step solve needs: no embedded error estimators, no dense output.
+and ``b`` the weights of the propagated solution.  ``get`` serves the fixed-step solves: no embedded error estimators, no dense output.
+``get_pair(name)`` -> ``Pair(name, order, tab, e)`` serves ``pde_util.solver_rk_adaptive``: ``tab`` the propagated method, ``e = b - bhat``
+the error weights (the local error estimate of a step is h sum_i e_i K_i) and ``order`` the controller's exponent (the order of the
+error estimator + 1).  The pairs: dopri5 (e = scipy 1.15's ``RK45.E``), bosh3 (Bogacki & Shampine 1989; scipy's ``RK23`` A, B, E with the
+fourth stage row equal to B, the stage scipy evaluates as f(y+)), heun (Heun's method with its embedded Euler step).  dopri8 is refused:
+DOP853 estimates its error from two formulae, which is another controller.
 
   euler, heun (explicit trapezoid), midpoint, rk4   the textbook coefficients
   dopri5   Dormand & Prince (1980), "A family of embedded Runge-Kutta formulae", J. Comput. Appl. Math. 6: the 5th-order solution
@@ -57,6 +62,19 @@ _TABLEAUX = {
 }
 NAMES = tuple(_TABLEAUX)
 
+Pair = collections.namedtuple("Pair", "name order tab e")
+
+_DOPRI5_E = (-0.0012326388888888888, 0.0, 0.0042527702905061394, -0.03697916666666667, 0.05086379716981132, -0.0419047619047619, 0.025)
+_BOSH3_B = (0.2222222222222222, 0.3333333333333333, 0.4444444444444444)
+_BOSH3_E = (0.06944444444444445, -0.08333333333333333, -0.1111111111111111, 0.125)
+
+_PAIRS = {
+    "dopri5": Pair("dopri5", 5, _TABLEAUX["dopri5"], _DOPRI5_E),
+    "bosh3": Pair("bosh3", 3, Tableau("bosh3", 3, ((), (0.5,), (0.0, 0.75), _BOSH3_B), _BOSH3_B + (0.0,)), _BOSH3_E),
+    "heun": Pair("heun", 2, _TABLEAUX["heun"], (-0.5, 0.5)),
+}
+PAIR_NAMES = tuple(_PAIRS)
+
 
 def get(name):
     if name == "tsit5":
@@ -76,4 +94,23 @@ def struct(tab):
             out.a[i][j] = float(v)
     for i, v in enumerate(tab.b):
         out.b[i] = float(v)
+    return out
+
+
+def get_pair(name):
+    if name == "dopri8":
+        raise NotImplementedError("dopri8 has no embedded pair here: DOP853 combines two error estimators, which is a different "
+                                  f"controller; one of {PAIR_NAMES}")
+    if name not in _PAIRS:
+        raise ValueError(f"unknown embedded Runge-Kutta pair {name!r}: one of {PAIR_NAMES}")
+    return _PAIRS[name]
+
+
+def pair_struct(pair):
+    """``struct mfx_rk_pair`` of a Pair"""
+    out = _lib.RkPair()
+    out.tab = struct(pair.tab)
+    for i, v in enumerate(pair.e):
+        out.e[i] = float(v)
+    out.order = int(pair.order)
     return out

@@ -8,6 +8,10 @@ disk (`./data/pde_wave/<res>x<res>_data_{inputs,targets,parameter}.npy`) a synth
 `diffrax:tsit5+recursive_checkpoint` is accepted and refused with the reason (`rk_tableaux`): its coefficients are not available.
 
   python workprecision.py --resolution 32 --method diffrax:dopri5+backsolve [--num_steps_max 10] [--num_runs 1]
+
+`--adaptive` (off by default; nothing else changes without it) replaces the sweep over step counts of a `diffrax:` method by a sweep
+over tolerances: `pde_util.solver_rk_adaptive` on the method's embedded pair (dopri5, heun) at rtol = 10^-1 .. 10^-(num_steps_max - 1),
+atol = 1e-3 rtol, the arrays saved as `wp_<method>+adaptive_*`.
 """
 
 import argparse
@@ -52,7 +56,10 @@ def main():
     ap.add_argument("--method", type=str, required=True)
     ap.add_argument("--num_runs", type=int, default=1)
     ap.add_argument("--num_steps_max", type=int, default=10)
+    ap.add_argument("--adaptive", action="store_true", help="sweep tolerances of the adaptive-step solver instead of step counts")
     args = ap.parse_args()
+    if args.adaptive and args.method == "arnoldi":
+        raise ValueError("--adaptive sweeps the tolerance of a Runge-Kutta pair; arnoldi has no step size")
     if args.method != "arnoldi" and args.method not in METHODS:
         raise ValueError(f"The method {args.method} is not supported.")
     dev = torch.device("cuda:0")
@@ -91,7 +98,11 @@ def main():
         if nstp > parameter.numel():
             print("The Krylov depth would exceed the matrix size.")
             break
-        if args.method == "arnoldi":
+        if args.adaptive:
+            method, adjoint = METHODS[args.method]
+            make = lambda field: pde_util.solver_rk_adaptive(0.0, 1.0, field, method=method, rtol=10.0**-nstp, atol=10.0 ** -(nstp + 3),  # noqa: E731
+                                                             adjoint=adjoint, max_steps=100000 if adjoint == "backsolve" else 4096)
+        elif args.method == "arnoldi":
             make = lambda field: pde_util.solver_expm(0.0, 1.0, field, expm=pde_util.expm_arnoldi(nstp))  # noqa: E731
         else:
             method, adjoint = METHODS[args.method]
@@ -107,6 +118,8 @@ def main():
         print(f"N={Ns[-1]}, fwd={fwd:.1e}, rev={rev:.1e}, t={min(ts_all[-1]):.2e} s", flush=True)
     directory = exp_util.matching_directory(__file__, "results/")
     os.makedirs(directory, exist_ok=True)
+    if args.adaptive:
+        args.method += "+adaptive"
     np.save(f"{directory}/wp_{args.method}_Ns", np.asarray(Ns))
     np.save(f"{directory}/wp_{args.method}_ts", np.asarray(ts_all))
     np.save(f"{directory}/wp_{args.method}_errors_fwd", np.asarray(errors_fwd))

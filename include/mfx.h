@@ -789,6 +789,54 @@ int mfx_rk_backsolve(const mfx_operator* op, const mfx_rk_tableau* tab, const do
                      int64_t n, int64_t p, const void* dy1, int64_t lddy1, void* dy0, int64_t lddy0, const mfx_op_grads* grads,
                      int flags, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- adaptive-step explicit Runge-Kutta solve of y' = A y on an embedded pair ----------------------------
+ * Additive: new symbols, no struct or existing signature changes, MFX_VERSION stays 201.
+ *
+ * Pair (HOST struct): `tab` the propagated method, e = b - bhat the error weights (the local error estimate of a step of size h is
+ * h sum_i e[i] K_i), `order` the exponent of the controller (error estimator order + 1: 5 for dopri5).
+ *
+ * Controller: the rule of scipy 1.15's scipy.integrate._ivp.rk.RungeKutta._step_impl.  An attempt from (t, y) with the proposal H:
+ *   t+ = min(t + H, t1), h = t+ - t;  y+ = the step of size h;  scale_i = atol + rtol max(|y_i|, |y+_i|);
+ *   norm = max over the p states of sqrt(mean_i (err_i / scale_i)^2)    (the batch shares ONE step sequence);
+ *   norm < 1: accept (t, y) <- (t+, y+), H <- h f with f = 10 if norm == 0 else min(10, 0.9 norm^(-1/order)), capped at 1 when an
+ *   attempt was rejected since the last accepted step;  otherwise reject: H <- h max(0.2, 0.9 norm^(-1/order)).
+ * A clipped step that is accepted leaves t == t1 exactly.  The estimate, the scale and the norm are formed in fp64 from the stored
+ * (fp32 or fp64) y, y+ and K rows.  Stage and update coefficients are the fp64 products h a[i][j], h b[i] rounded to the dtype once
+ * and applied in the order of mfx_rk_solve: the accepted iterates are bit for bit those of mfx_rk_solve with the returned dts.
+ *
+ * t, h, the counters, the status and the accepted step sizes live in a control block in the workspace; the kernels of an attempt read
+ * them there, so an attempt is one fixed launch sequence.  The host enqueues `chunk` attempts, copies the block back and synchronises
+ * ONCE per chunk (THE CALL SYNCHRONISES `stream`); after completion inside a chunk the vector kernels return at once and the operator
+ * applications run on unchanged data.  For a native operator a chunk is replayed from one hipGraph whose key holds the pair, rtol,
+ * atol, chunk, max_steps, all pointers and sizes and the operator's key -- not t0, t1, dt0 or max_attempts.
+ *
+ * Outputs: y1 = the state at info->t_reached; ys, when not NULL, (p, max_steps + 1, n) contiguous: rows 0 .. n_accepted are the
+ * accepted iterates (row 0 = y0), later rows are not written; dts (HOST, max_steps doubles, may be NULL): the n_accepted accepted step
+ * sizes; info (HOST, required).  The return value is MFX_OK whenever the solve ran; how it ended is info->status, never silent:
+ *   MFX_RK_OK; MFX_RK_MAX_ATTEMPTS (max_attempts attempts, or max_steps accepted steps, without reaching t1); MFX_RK_STEP_TOO_SMALL
+ *   (a proposal below 10 ulp(t)); MFX_RK_NONFINITE (a non-finite error norm).  mfx_last_error() names a status other than MFX_RK_OK.
+ * No atomics, fixed reduction orders: bit-identical from run to run and for every chunk.
+ *   mfx_rk_adaptive_workspace_bytes   host arithmetic; -1 for arguments the call would refuse.
+ * Refused before the workspace is carved and before any launch: everything mfx_rk_solve refuses; MFX_ERR_INVALID: a NULL pair or
+ * info, a non-finite e, order < 1, rtol or atol negative or rtol + atol not finite or not positive, dt0 <= 0, t1 <= t0 (or either not
+ * finite), max_steps < 1, max_attempts < 1, chunk < 1, flags != 0.  MFX_ERR_WORKSPACE: ws NULL or ws_bytes below the query. */
+typedef struct mfx_rk_pair {
+  mfx_rk_tableau tab;
+  double e[MFX_RK_MAX_STAGES];
+  int32_t order;
+} mfx_rk_pair;
+enum { MFX_RK_OK = 0, MFX_RK_MAX_ATTEMPTS = 1, MFX_RK_STEP_TOO_SMALL = 2, MFX_RK_NONFINITE = 3 };
+typedef struct mfx_rk_adaptive_info {
+  int32_t status;
+  int64_t n_accepted, n_rejected, n_attempts;
+  double t_reached;
+} mfx_rk_adaptive_info;
+int64_t mfx_rk_adaptive_workspace_bytes(const mfx_operator* op, const mfx_rk_pair* pair, int64_t n, int64_t p, int64_t max_steps);
+int mfx_rk_solve_adaptive(const mfx_operator* op, const mfx_rk_pair* pair, double t0, double t1, double dt0, double rtol, double atol,
+                          int64_t max_steps, int64_t max_attempts, int64_t chunk, const void* y0, int64_t ldy0, int64_t n, int64_t p,
+                          void* y1, int64_t ldy1, void* ys, double* dts, mfx_rk_adaptive_info* info, int flags, void* ws,
+                          int64_t ws_bytes, void* stream);
+
 /* Per-kernel-class device timing with hipEvents recorded on the caller's stream (no host syncs
  * while enabled; events are read back in mfx_timing_read, which synchronises the events).
  * classes: 0 = operator apply, 1 = operator parameter-gradient sweep, 2 = Krylov vector kernels. */
